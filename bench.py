@@ -22,6 +22,12 @@ phi ~ U[-1,1] seeded, distinct seeded bitstrings (U = B exactly).
 Launched without torchrun, `--gpus N` (N > 1) starts its own N ranks through
 `python -m torch.distributed.run` as a child process -- decided before anything
 touches the GPU -- and fails loudly if fewer than N GPUs are visible.
+
+A plain run sets up, warms up, times --steps steps and prints the line;
+--dump-outputs DIR also writes what the last timed step returned (inputs are
+seeded, so two builds can be compared output for output).  --full adds what
+the headline does not need: the roofline, the CPU baseline and the oracle's
+parity check of the timed step, the mirror's VQT step and, for N > 1, --verify.
 """
 import argparse
 import hashlib
@@ -192,6 +198,139 @@ def parity_check(eng, E, mode, ops, bits_k, params, timed_vals_k, timed_grad_row
   return out
 
 
+def roofline_record(eng, args, kt, probe, gates, n_params, n_terms, spg, n, layers):
+  """`--full`: the roofline of the step's dominant kernel from the timed run's HIP events, the byte and flop models
+  and the clock probe taken after the timed region, next to the stored counter profiles."""
+  # Bytes a launch must move: every tile it touches read once and written once (qhbm_traffic_model;
+  # it agrees with the rocprofv3 FETCH_SIZE / WRITE_SIZE counters of profiles/ to < 1 %).  The
+  # per-gate byte model of SURVEY.md 8(d) -- what an UNFUSED gate-by-gate sweep would move -- is
+  # reported beside it as `unfused_bytes_per_launch`; their ratio is the fusion factor, not a
+  # roofline fraction.
+  n_gate = len(gates)
+  amp = float(1 << n)
+  shift_factor = (1 + 2 * n_params) if args.mode == "shift" else 1
+  fwd_unfused = spg * (16.0 * n_gate + 8.0 * n_terms + 8.0) * amp * shift_factor
+  bwd_unfused = spg * 48.0 * n_gate * amp
+  adjoint_mode = args.mode in ("vqt", "qmhl")
+  tm = eng.traffic_model(spg, with_vjp=adjoint_mode)
+  fm = eng.flop_model(spg, with_vjp=adjoint_mode)
+  # the dominant kernel family of the step: forward passes, adjoint passes, or the observable kernel (lambda = O psi /
+  # values: config 4's 480 X-masks make it the largest)
+  families = {
+      "pass_fwd_kernel": (kt["fwd_launches"], kt["fwd_ms"], fwd_unfused, tm["fwd_bytes"] * shift_factor, fm["fwd_flops"] * shift_factor),
+      "pass_adj_kernel": (kt["bwd_launches"], kt["bwd_ms"], bwd_unfused, tm["bwd_bytes"], fm["bwd_flops"]),
+      "apply_observable_kernel": (kt["obs_launches"], kt["obs_ms"], spg * 8.0 * n_terms * amp * shift_factor,
+                                  tm["obs_bytes"] * shift_factor, fm["obs_flops"] * shift_factor),
+  }
+  name = max(families, key=lambda k: families[k][1])
+  launches, ms, unfused, model, flops = families[name]
+  kernel_label = name
+  observable_family = name == "apply_observable_kernel"
+  if observable_family:  # which of the two observable kernels ran (qhbm_describe_schedule's last line)
+    m = re.search(r"observable kernel: lambda = (\w+) values = ([\w ]+)", eng.describe_schedule())
+    if m:
+      kernel_label = m.group(1) if adjoint_mode else m.group(2).strip()
+  per_step_launches = max(1, launches // max(1, args.steps))
+  avg_ms = ms / max(1, launches)
+  bytes_per_launch = model / per_step_launches
+  achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+  # compute roofline of the same kernel: the fp32 operations its gate arithmetic executes
+  # (qhbm_flop_model: counted from the plan's instance records, FMA = 2; reductions and address
+  # arithmetic not counted) over the same HIP-event launch time, against the fp32 vector peak
+  flops_per_launch = flops / per_step_launches
+  achieved_tfs = flops_per_launch / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
+  hbm_frac, compute_frac = achieved / HBM_PEAK_GBPS, achieved_tfs / FP32_PEAK_TFLOPS
+  compute_bound = compute_frac > hbm_frac
+  # PMC traffic and VALU utilisation come from committed rocprofv3 runs of THIS command
+  # (scripts/profile_bench.sh -> profiles/): stored values, not measured in this run.
+  traffic, traffic_src, valu = None, None, None
+  def family(profile):  # "pass_adj_kernel" also matches the exchange-layout kernel "pass_adjx_kernel"
+    keys = [k for k in (profile or {}) if k.startswith(name[:-len("_kernel")]) and isinstance(profile[k], dict)]
+    return max(keys, key=lambda k: profile[k].get("calls", 0)) if keys else None
+
+  tj = stored_profile("traffic.json", n, layers, args.hamiltonian, args.mode)
+  if family(tj):
+    scale = spg / float(tj["states_per_gpu"])
+    traffic = tj[family(tj)]["hbm_bytes_per_launch"] * scale
+    traffic_src = (f"stored profile profiles/traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, "
+                   f"{tj['states_per_gpu']} states, git {tj.get('git_head', '?')}, bench.py sha "
+                   f"{tj.get('bench_py_sha16', '?')}), scaled x{scale:g} in states; NOT measured in this run")
+  vj = stored_profile("valu.json", n, layers, args.hamiltonian, args.mode)
+  if family(vj):
+    valu = dict(vj[family(vj)], source=f"stored profile profiles/valu.json (git {vj.get('git_head', '?')})")
+  # (VERDICT r4 #7) the stored counters go stale with every kernel change: say so in the line when they were taken on
+  # other engine sources than the ones in this tree
+  src_sha = kernel_sources_sha16()
+  stale = [nm for nm, pj in (("traffic.json", tj), ("valu.json", vj))
+           if family(pj) and pj.get("kernel_sources_sha16") not in (None, src_sha)]
+  return {
+      # the bound is whichever ceiling the dominant kernel sits closer to; achieved / peak / unit /
+      # frac are those of that ceiling, and both are spelled out in "hbm" and "compute"
+      "bound": "fp32_valu" if compute_bound else "hbm", "kernel": kernel_label,
+      "achieved": achieved_tfs if compute_bound else achieved,
+      "peak": FP32_PEAK_TFLOPS if compute_bound else HBM_PEAK_GBPS,
+      "unit": "TFLOP/s" if compute_bound else "GB/s",
+      "frac": compute_frac if compute_bound else hbm_frac,
+      "hbm": {"achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": hbm_frac},
+      "compute": {"flops_per_launch": flops_per_launch, "achieved_TFs": achieved_tfs, "peak": FP32_PEAK_TFLOPS,
+                  "unit": "TFLOP/s", "frac": compute_frac,
+                  # measured in THIS run (qhbm_clock_probe): every SIMD issuing v_pk_fma_f32 from four waves --
+                  # what the chip sustains under packed fp32 at the clock it holds right after the timed region
+                  "attainable_peak": (probe or {}).get("tflops"),
+                  "attainable_frac": (achieved_tfs / probe["tflops"]) if probe and probe.get("tflops") else None,
+                  "probe": probe,
+                  "flops_definition": "fp32 operations of the gate arithmetic (FMA = 2) from the plan's instance "
+                                      "records (qhbm_flop_model), skipped tiles and dead waves excluded; peak = "
+                                      "fp32 vector rate = dense f32 MFMA rate on gfx950",
+                  "flops_per_step": {"forward": fm["fwd_flops"] * shift_factor, "apply_observable": fm["obs_flops"],
+                                     "adjoint": fm["bwd_flops"]},
+                  "achieved_TFs_by_kernel": {
+                      k: (f / (kt[t] / args.steps * 1e-3) / 1e12 if kt[t] > 0 else None)
+                      for k, f, t in (("forward", fm["fwd_flops"] * shift_factor, "fwd_ms"),
+                                      ("apply_observable", fm["obs_flops"], "obs_ms"),
+                                      ("adjoint", fm["bwd_flops"], "bwd_ms"))}},
+      "traffic": traffic, "traffic_source": traffic_src,
+      **({"stored_profile_warning": "STALE: " + ", ".join(stale) + " taken on other engine sources than this tree's "
+                                    f"(kernel_sources_sha16 {src_sha}): re-run scripts/profile_bench.sh"} if stale else {}),
+      "avg_launch_ms": avg_ms, "launches_per_step": per_step_launches,
+      "bytes_per_launch": bytes_per_launch,
+      "bytes_definition": (
+          "the final states read once (+ lambda written once in a VJP call): the least this kernel could move "
+          "(qhbm_traffic_model); what it does move through L2 and the fabric is in the committed counter profiles"
+          if observable_family else
+          "every tile the launch touches read once + written once (qhbm_traffic_model); "
+          "achieved = bytes_per_launch / avg_launch_ms (HIP events on the launch stream)"),
+      "unfused_bytes_per_launch": unfused / per_step_launches,
+      "fusion_factor": unfused / model if model > 0 else None,
+      "gates_per_launch": None if observable_family else n_gate / per_step_launches,
+      "valu": valu,
+      "note": (("the observable kernel is the largest launch of this step: compute.frac counts one complex "
+                "multiply-add per Pauli term and amplitude against the fp32 peak; the block-grouped kernel is bound "
+                "by its LDS pipeline (store burst of the partner block, the masks' reads, barrier skew: DESIGN.md "
+                "section 5.2), the gather kernel by the fabric reads of its partner runs -- neither by HBM nor by VALU issue")
+               if observable_family else
+               ("the pass kernels are bound by fp32 VALU issue (valu.valu_active_frac), not by HBM: "
+                "hbm.frac is the HBM rate of a launch that applies gates_per_launch gates per tile round "
+                "trip, and it FALLS when the scheduler fuses more gates into a launch while the step "
+                "gets faster; compute.frac is the share of the fp32 peak the gate arithmetic reaches "
+                "(DESIGN.md section 5)")),
+  }
+
+
+def dump_outputs(out_dir, vals, grad):
+  """`--dump-outputs DIR`: what the last timed step returned to its caller -- values [U, T] and, unless the step is
+  forward-only, the [P] gradient -- as DIR/<name>.npy in float32.  Values of more than 48 MiB are cut to a fixed,
+  seeded sample of rows (row order kept) so that the dump stays below 64 MB."""
+  os.makedirs(out_dir, exist_ok=True)
+  values = vals.detach().float().cpu().numpy()
+  max_rows = max(1, (48 << 20) // max(1, values[0].nbytes if values.shape[0] else 1))
+  if values.shape[0] > max_rows:
+    values = values[np.sort(np.random.default_rng(0).choice(values.shape[0], max_rows, replace=False))]
+  np.save(os.path.join(out_dir, "values.npy"), np.ascontiguousarray(values, np.float32))
+  if grad is not None:
+    np.save(os.path.join(out_dir, "grad.npy"), grad.detach().float().cpu().numpy())
+
+
 def gpus_visible_without_hip():
   """GPU count read from the KFD topology (sysfs), narrowed by HIP_/ROCR_VISIBLE_DEVICES -- no HIP or HSA
   call, so the launching process holds no GPU context.  None when sysfs cannot tell."""
@@ -300,7 +439,7 @@ def mirror_model(n, layers, samples, ham_kind, ebm_kind):
 
 
 def mirror_step_sample(n, layers, samples, ham_kind, steps=3):
-  """`vqt_step_through_mirror` of the DEFAULT line (round 5's review, "what's missing" 4): BASELINE.md section 3 defines
+  """`vqt_step_through_mirror` of the `--full` line (round 5's review, "what's missing" 4): BASELINE.md section 3 defines
   "VQT step time" as loss + both gradients through `vqt()`, sampler excluded -- the engine's share is `ms_per_step`, this is
   the whole: `steps` eager `inference.vqt(qhbm, [H], 1.0)` + `backward()` on one fixed multiset of `samples` samples of a
   KOBE-2 (Bernoulli below 14 qubits) EBM, after one untimed step.  Runs AFTER the timed region, the probe and the parity
@@ -437,24 +576,37 @@ def main():
                   help="N > 1, strong scaling: equal row blocks (default), or blocks proportional to every rank's MEASURED "
                        "speed -- one probing step on the equal blocks, kernel time per state all-gathered once "
                        "(parallel.measured_weights) -- so that a GPU that sustains a lower clock gets fewer states")
-  ap.add_argument("--cpu-sample-states", type=int, default=64)
-  ap.add_argument("--no-cpu-baseline", action="store_true")
+  ap.add_argument("--full", action="store_true",
+                  help="measure and check beyond the headline, after the timed steps: the roofline of the dominant "
+                       "kernel (with the clock probe), the CPU baseline and the oracle's parity check of the timed step, "
+                       "`vqt_step_through_mirror`, and --verify by default for N > 1.  Without it a run sets up, warms up, "
+                       "times the steps, writes --dump-outputs and prints the line")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="write what the last timed step returned -- values [U, T] as DIR/values.npy and the [P] gradient "
+                       "as DIR/grad.npy (not in --mode forward), float32")
+  ap.add_argument("--cpu-sample-states", type=int, default=64, help="--full: states of the CPU baseline")
+  ap.add_argument("--no-cpu-baseline", action="store_true",
+                  help="--full without the CPU baseline and the parity check")
   ap.add_argument("--verify", dest="verify", action="store_true", default=None,
                   help="rank 0 re-evaluates the whole batch alone (outside the timed region) and compares with the "
-                       "sharded result; default: on for --gpus N > 1, off for N = 1")
+                       "sharded result; default: on with --full for --gpus N > 1, off otherwise")
   ap.add_argument("--no-verify", dest="verify", action="store_false")
   ap.add_argument("--no-mirror-step", action="store_true",
-                  help="skip `vqt_step_through_mirror` (three eager vqt() + backward() steps through the host mirror after "
-                       "the timed region: BASELINE.md's 'VQT step time', sampler excluded)")
+                  help="--full without `vqt_step_through_mirror` (three eager vqt() + backward() steps through the host "
+                       "mirror after the timed region: BASELINE.md's 'VQT step time', sampler excluded)")
   ap.add_argument("--through-mirror", choices=["c1", "c2", "c3"], default=None,
                   help="a SECOND, separately labelled measurement (the default line is unchanged): the step a user calls -- "
                        "inference.vqt(qhbm, H, beta) + backward() through the host mirror on a fixed sample multiset (sampler "
                        "excluded: BASELINE.md section 3 'VQT step time') -- for BASELINE configs[0], [1] or [2], eager and as a "
                        "replayed hipGraph (inference.CapturedLoss), beside the engine's own time on the same rows")
   args = ap.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    ap.error("--steps must be at least 1 and --warmup at least 0")
   if args.through_mirror:
     if args.gpus != 1:
       raise SystemExit("bench.py --through-mirror is a one-GPU measurement")
+    if args.dump_outputs:
+      raise SystemExit("bench.py --dump-outputs writes the engine step's outputs, not those of --through-mirror")
     return mirror_bench(args)
 
   if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -605,18 +757,21 @@ def main():
   # the chip's sustained packed-fp32 rate and clock, probed straight after the timed region (as warm as the timed
   # kernels left it): the ATTAINABLE compute ceiling of this run, next to the nominal 157.3 TFLOP/s
   probe = None
-  if rank == 0:
+  if rank == 0 and args.full:
     try:
       probe = eng.clock_probe()
     except Exception as exc:  # pylint: disable=broad-except
       probe = {"error": f"{type(exc).__name__}: {exc}"}
   if args.verify is None:
-    args.verify = world > 1
+    args.verify = args.full and world > 1
+  check_parity = args.full and not args.no_cpu_baseline
   # per-state gradient rows of the LAST TIMED step, read before anything else runs on the engine (parity_check)
   timed_grad_rows = None
-  if rank == 0 and args.mode in ("vqt", "qmhl") and not args.no_cpu_baseline and spg > 0:
+  if rank == 0 and check_parity and args.mode in ("vqt", "qmhl") and spg > 0:
     k_rows = max(1, min(args.cpu_sample_states, spg, os.cpu_count() or 1))
     timed_grad_rows = eng.state_gradients(spg)[:k_rows].float().cpu().numpy()
+  if rank == 0 and args.dump_outputs:
+    dump_outputs(args.dump_outputs, vals, grad)
 
   # which physical device each rank ran on (PCI bus id), as the ranks themselves report it
   prop = torch.cuda.get_device_properties(local_rank)
@@ -638,69 +793,6 @@ def main():
     n_terms = sum(len(op) for op in ops)
     evals_per_step = total_states * n_terms
     ms_per_step = dt / args.steps * 1e3
-    # ---- roofline of the dominant kernel -------------------------------------------------------
-    # Bytes a launch must move: every tile it touches read once and written once (qhbm_traffic_model;
-    # it agrees with the rocprofv3 FETCH_SIZE / WRITE_SIZE counters of profiles/ to < 1 %).  The
-    # per-gate byte model of SURVEY.md 8(d) -- what an UNFUSED gate-by-gate sweep would move -- is
-    # reported beside it as `unfused_bytes_per_launch`; their ratio is the fusion factor, not a
-    # roofline fraction.
-    n_gate = len(gates)
-    amp = float(1 << n)
-    shift_factor = (1 + 2 * n_params) if args.mode == "shift" else 1
-    fwd_unfused = spg * (16.0 * n_gate + 8.0 * n_terms + 8.0) * amp * shift_factor
-    bwd_unfused = spg * 48.0 * n_gate * amp
-    adjoint_mode = args.mode in ("vqt", "qmhl")
-    tm = eng.traffic_model(spg, with_vjp=adjoint_mode)
-    fm = eng.flop_model(spg, with_vjp=adjoint_mode)
-    # the dominant kernel family of the step: forward passes, adjoint passes, or the observable kernel (lambda = O psi /
-    # values: config 4's 480 X-masks make it the largest)
-    families = {
-        "pass_fwd_kernel": (kt["fwd_launches"], kt["fwd_ms"], fwd_unfused, tm["fwd_bytes"] * shift_factor, fm["fwd_flops"] * shift_factor),
-        "pass_adj_kernel": (kt["bwd_launches"], kt["bwd_ms"], bwd_unfused, tm["bwd_bytes"], fm["bwd_flops"]),
-        "apply_observable_kernel": (kt["obs_launches"], kt["obs_ms"], spg * 8.0 * n_terms * amp * shift_factor,
-                                    tm["obs_bytes"] * shift_factor, fm["obs_flops"] * shift_factor),
-    }
-    name = max(families, key=lambda k: families[k][1])
-    launches, ms, unfused, model, flops = families[name]
-    kernel_label = name
-    observable_family = name == "apply_observable_kernel"
-    if observable_family:  # which of the two observable kernels ran (qhbm_describe_schedule's last line)
-      m = re.search(r"observable kernel: lambda = (\w+) values = ([\w ]+)", eng.describe_schedule())
-      if m:
-        kernel_label = m.group(1) if adjoint_mode else m.group(2).strip()
-    per_step_launches = max(1, launches // max(1, args.steps))
-    avg_ms = ms / max(1, launches)
-    bytes_per_launch = model / per_step_launches
-    achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-    # compute roofline of the same kernel: the fp32 operations its gate arithmetic executes
-    # (qhbm_flop_model: counted from the plan's instance records, FMA = 2; reductions and address
-    # arithmetic not counted) over the same HIP-event launch time, against the fp32 vector peak
-    flops_per_launch = flops / per_step_launches
-    achieved_tfs = flops_per_launch / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
-    hbm_frac, compute_frac = achieved / HBM_PEAK_GBPS, achieved_tfs / FP32_PEAK_TFLOPS
-    compute_bound = compute_frac > hbm_frac
-    # PMC traffic and VALU utilisation come from committed rocprofv3 runs of THIS command
-    # (scripts/profile_bench.sh -> profiles/): stored values, not measured in this run.
-    traffic, traffic_src, valu = None, None, None
-    def family(profile):  # "pass_adj_kernel" also matches the exchange-layout kernel "pass_adjx_kernel"
-      keys = [k for k in (profile or {}) if k.startswith(name[:-len("_kernel")]) and isinstance(profile[k], dict)]
-      return max(keys, key=lambda k: profile[k].get("calls", 0)) if keys else None
-
-    tj = stored_profile("traffic.json", n, layers, args.hamiltonian, args.mode)
-    if family(tj):
-      scale = spg / float(tj["states_per_gpu"])
-      traffic = tj[family(tj)]["hbm_bytes_per_launch"] * scale
-      traffic_src = (f"stored profile profiles/traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, "
-                     f"{tj['states_per_gpu']} states, git {tj.get('git_head', '?')}, bench.py sha "
-                     f"{tj.get('bench_py_sha16', '?')}), scaled x{scale:g} in states; NOT measured in this run")
-    vj = stored_profile("valu.json", n, layers, args.hamiltonian, args.mode)
-    if family(vj):
-      valu = dict(vj[family(vj)], source=f"stored profile profiles/valu.json (git {vj.get('git_head', '?')})")
-    #  the stored counters go stale with every kernel change: say so in the line when they were taken on
-    # other engine sources than the ones in this tree
-    src_sha = kernel_sources_sha16()
-    stale = [nm for nm, pj in (("traffic.json", tj), ("valu.json", vj))
-             if family(pj) and pj.get("kernel_sources_sha16") not in (None, src_sha)]
     with open(os.path.abspath(__file__), "rb") as f:
       bench_sha = hashlib.sha256(f.read()).hexdigest()[:16]
     mode_name = {"vqt": "VQT step = values + adjoint VJP", "forward": "forward values only",
@@ -765,59 +857,9 @@ def main():
                      "argmax": int(max(range(len(per_rank)), key=lambda r: per_rank[r][0])),
                      "balance": args.balance if world > 1 else None,
                      "weights": shard_weights},
-        "roofline": {
-            # the bound is whichever ceiling the dominant kernel sits closer to; achieved / peak / unit /
-            # frac are those of that ceiling, and both are spelled out in "hbm" and "compute"
-            "bound": "fp32_valu" if compute_bound else "hbm", "kernel": kernel_label,
-            "achieved": achieved_tfs if compute_bound else achieved,
-            "peak": FP32_PEAK_TFLOPS if compute_bound else HBM_PEAK_GBPS,
-            "unit": "TFLOP/s" if compute_bound else "GB/s",
-            "frac": compute_frac if compute_bound else hbm_frac,
-            "hbm": {"achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": hbm_frac},
-            "compute": {"flops_per_launch": flops_per_launch, "achieved_TFs": achieved_tfs, "peak": FP32_PEAK_TFLOPS,
-                        "unit": "TFLOP/s", "frac": compute_frac,
-                        # measured in THIS run (qhbm_clock_probe): every SIMD issuing v_pk_fma_f32 from four waves --
-                        # what the chip sustains under packed fp32 at the clock it holds right after the timed region
-                        "attainable_peak": (probe or {}).get("tflops"),
-                        "attainable_frac": (achieved_tfs / probe["tflops"]) if probe and probe.get("tflops") else None,
-                        "probe": probe,
-                        "flops_definition": "fp32 operations of the gate arithmetic (FMA = 2) from the plan's instance "
-                                            "records (qhbm_flop_model), skipped tiles and dead waves excluded; peak = "
-                                            "fp32 vector rate = dense f32 MFMA rate on gfx950",
-                        "flops_per_step": {"forward": fm["fwd_flops"] * shift_factor, "apply_observable": fm["obs_flops"],
-                                           "adjoint": fm["bwd_flops"]},
-                        "achieved_TFs_by_kernel": {
-                            k: (f / (kt[t] / args.steps * 1e-3) / 1e12 if kt[t] > 0 else None)
-                            for k, f, t in (("forward", fm["fwd_flops"] * shift_factor, "fwd_ms"),
-                                            ("apply_observable", fm["obs_flops"], "obs_ms"),
-                                            ("adjoint", fm["bwd_flops"], "bwd_ms"))}},
-            "traffic": traffic, "traffic_source": traffic_src,
-            **({"stored_profile_warning": "STALE: " + ", ".join(stale) + " taken on other engine sources than this tree's "
-                                          f"(kernel_sources_sha16 {src_sha}): re-run scripts/profile_bench.sh"} if stale else {}),
-            "avg_launch_ms": avg_ms, "launches_per_step": per_step_launches,
-            "bytes_per_launch": bytes_per_launch,
-            "bytes_definition": (
-                "the final states read once (+ lambda written once in a VJP call): the least this kernel could move "
-                "(qhbm_traffic_model); what it does move through L2 and the fabric is in the committed counter profiles"
-                if observable_family else
-                "every tile the launch touches read once + written once (qhbm_traffic_model); "
-                "achieved = bytes_per_launch / avg_launch_ms (HIP events on the launch stream)"),
-            "unfused_bytes_per_launch": unfused / per_step_launches,
-            "fusion_factor": unfused / model if model > 0 else None,
-            "gates_per_launch": None if observable_family else n_gate / per_step_launches,
-            "valu": valu,
-            "note": (("the observable kernel is the largest launch of this step: compute.frac counts one complex "
-                      "multiply-add per Pauli term and amplitude against the fp32 peak; the block-grouped kernel is bound "
-                      "by its LDS pipeline (store burst of the partner block, the masks' reads, barrier skew: DESIGN.md "
-                      "section 5.2), the gather kernel by the fabric reads of its partner runs -- neither by HBM nor by VALU issue")
-                     if observable_family else
-                     ("the pass kernels are bound by fp32 VALU issue (valu.valu_active_frac), not by HBM: "
-                      "hbm.frac is the HBM rate of a launch that applies gates_per_launch gates per tile round "
-                      "trip, and it FALLS when the scheduler fuses more gates into a launch while the step "
-                      "gets faster; compute.frac is the share of the fp32 peak the gate arithmetic reaches "
-                      "(DESIGN.md section 5)")),
-        },
     }
+    if args.full:
+      line["roofline"] = roofline_record(eng, args, kt, probe, gates, n_params, n_terms, spg, n, layers)
     if args.verify:
       # the sharded step against one process evaluating every state (same engine, same inputs)
       full_bits = torch.from_numpy(all_bits).cuda()
@@ -832,7 +874,7 @@ def main():
       err_g = float((grad - ref_grad).abs().max()) if ref_grad is not None else 0.0
       line["verify"] = {"max_err_values": err_v, "max_err_grad": err_g,
                         "ok": bool(err_v < 1e-4 * max(len(op) for op in ops) and err_g < 1e-4)}
-    if not args.no_cpu_baseline:
+    if check_parity:
       # The oracle must be there when the check is asked for: a missing checker is an error of its own, never a
       # silently absent parity_check.
       from oracle import qhbm_cpu as C  # pylint: disable=import-outside-toplevel
@@ -870,7 +912,8 @@ def main():
     # "VQT step time" as BASELINE.md section 3 defines it -- loss + both gradients through vqt(), sampler excluded: the
     # same circuit and Hamiltonian through the host mirror, after everything above (the bench's engine is closed first: the
     # mirror builds its own).  A reported companion of ms_per_step (the engine's share), never the headline.
-    if (world == 1 and args.mode == "vqt" and args.hamiltonian in ("xxz", "tfim") and n <= 20 and not args.no_mirror_step):
+    if (args.full and world == 1 and args.mode == "vqt" and args.hamiltonian in ("xxz", "tfim") and n <= 20
+        and not args.no_mirror_step):
       try:
         eng.close()
         torch.cuda.empty_cache()

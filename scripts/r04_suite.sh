@@ -10,7 +10,7 @@ timeout 1500 python -m pytest tests -m gpu -x -q > "$OUT/pytest_gpu.log" 2>&1
 tail -5 "$OUT/pytest_gpu.log"
 run() {  # name, args...
   local name=$1; shift
-  timeout 900 python bench.py "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"
+  timeout 900 python bench.py --full "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"
   python - "$OUT/$name.json" <<'PY'
 import json,sys
 try:

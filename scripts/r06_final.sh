@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 cd "$R"
 (time timeout 900 python -m pytest tests/test_bench_gpu.py tests/test_captured_gpu.py -q -x) > "$OUT/pytest.log" 2>&1
 tail -6 "$OUT/pytest.log"
-timeout 600 python bench.py --steps 20 --warmup 5 > "$OUT/c3_default.json" 2> "$OUT/c3_default.err"
+timeout 600 python bench.py --full --steps 20 --warmup 5 > "$OUT/c3_default.json" 2> "$OUT/c3_default.err"
 python - "$OUT/c3_default.json" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print("default", round(d["ms_per_step"],2), d["kernel_ms_per_step"], d["parity_check"]["ok"], d["cpu_baseline"]["value"], d["cpu_baseline"]["checker"], d.get("vqt_step_through_mirror"), d["roofline"].get("stored_profile_warning"))

@@ -17,7 +17,7 @@ try:
 except Exception as e: print(sys.argv[1], "FAILED", e); print(open(sys.argv[1][:-5]+".err").read()[-1500:])
 PY
 done
-timeout 600 python bench.py --steps 5 --warmup 2 > "$OUT/c3.json" 2> "$OUT/c3.err"
+timeout 600 python bench.py --full --steps 5 --warmup 2 > "$OUT/c3.json" 2> "$OUT/c3.err"
 python - "$OUT/c3.json" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print("c3", round(d["ms_per_step"],2), {k:round(v,2) for k,v in d["kernel_ms_per_step"].items()}, d["parity_check"]["ok"], d["cpu_baseline"])

@@ -12,7 +12,7 @@ tail -60 "$OUT/pytest_gpu.log"
 fi
 run() {  # name, args...
   local name=$1; shift
-  timeout 900 python bench.py "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"
+  timeout 900 python bench.py --full "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"
   python - "$OUT/$name.json" <<'PY'
 import json,sys
 try:

@@ -13,7 +13,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = ["--qubits", "12", "--layers", "2", "--states-per-gpu", "16", "--steps", "2", "--warmup", "1",
-         "--hamiltonian", "tfim", "--verify"]
+         "--hamiltonian", "tfim", "--verify", "--full"]
 
 
 def _line(out):
@@ -65,10 +65,39 @@ def test_bench_single_process_line():
   assert through["over_engine_ms_per_step"] == pytest.approx(through["ms_per_step"] / line["ms_per_step"])
 
 
+def test_bench_plain_line_is_lean_and_dumps_what_the_timed_step_returned(tmp_path):
+  """Without --full: the headline only (no roofline, CPU baseline, parity check, verify or mirror step), and
+  --dump-outputs writes the last timed step's values and gradient, which match the C oracle on bench.py's seeded
+  inputs (parameters 1234, bitstrings 4321, upstream 1 / states)."""
+  args = ["--qubits", "12", "--layers", "2", "--states-total", "16", "--steps", "3", "--warmup", "1",
+          "--hamiltonian", "tfim", "--dump-outputs", str(tmp_path)]
+  out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True,
+                       timeout=600, cwd=ROOT)
+  assert out.returncode == 0, out.stderr[-2000:]
+  line = _line(out.stdout)
+  assert line["unit"] == "evals/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+  assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+  assert line["value"] == pytest.approx(16 * 24 / (line["ms_per_step"] * 1e-3))
+  for key in ("roofline", "cpu_baseline", "parity_check", "verify", "vqt_step_through_mirror"):
+    assert key not in line, key
+  import numpy as np
+  import bench
+  from oracle import qhbm_cpu as C
+  vals, grad = np.load(tmp_path / "values.npy"), np.load(tmp_path / "grad.npy")
+  gates, n_params = bench.hea_gates(12, 2)
+  assert vals.dtype == np.float32 and vals.shape == (16, 1) and grad.dtype == np.float32 and grad.shape == (n_params,)
+  params = np.random.default_rng(1234).uniform(-1, 1, n_params).astype(np.float32)
+  bits = bench.distinct_bitstrings(12, 16, 4321)
+  ops = [bench.tfim_op(12)]
+  want_vals, want_grad = C.expectation_vjp(12, gates, params, bits, ops, np.full((16, 1), 1 / 16, np.float32))
+  np.testing.assert_allclose(vals, want_vals, rtol=0, atol=5e-5 * 24)
+  np.testing.assert_allclose(grad, want_grad, rtol=0, atol=1e-4 * max(1.0, float(np.abs(want_grad).max())))
+
+
 def test_bench_parameter_shift_mode_says_where_its_checked_gradient_comes_from():
   out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--qubits", "12", "--layers", "1",
                         "--states-total", "4", "--steps", "1", "--warmup", "0", "--hamiltonian", "tfim", "--mode", "shift",
-                        "--cpu-sample-states", "2"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--cpu-sample-states", "2", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
   assert out.returncode == 0, out.stderr[-2000:]
   pc = _line(out.stdout)["parity_check"]
   assert pc["ok"] and pc["grad_from"].startswith("engine VJP of these K states")
@@ -79,7 +108,7 @@ def test_bench_config3_timed_batch_against_the_oracle():
   the timed step and the VJP of the same states against the C oracle, inside the bench run itself
   (reference pattern simulate / compare / assert, tests/inference/qnn_test.py:183-264)."""
   out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--states-total", "96", "--steps", "1",
-                        "--warmup", "1", "--cpu-sample-states", "8"],
+                        "--warmup", "1", "--cpu-sample-states", "8", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
   assert out.returncode == 0, out.stderr[-2000:]
   line = _line(out.stdout)
@@ -153,7 +182,7 @@ def test_bench_eight_ranks_as_the_driver_launches_it():
     port = s.getsockname()[1]
   env = dict(os.environ, QHBM_BENCH_SHARE_DEVICE="1", QHBM_BENCH_BACKEND="gloo")
   args = ["--qubits", "12", "--layers", "2", "--states-total", "36", "--steps", "2", "--warmup", "1",
-          "--hamiltonian", "tfim", "--cpu-sample-states", "2"]
+          "--hamiltonian", "tfim", "--cpu-sample-states", "2", "--full"]
   cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
          "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8"] + args
   out = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
@@ -181,7 +210,7 @@ def test_bench_balance_measured_deals_blocks_by_measured_speed():
     port = s.getsockname()[1]
   env = dict(os.environ, QHBM_BENCH_SHARE_DEVICE="1", QHBM_BENCH_BACKEND="gloo")
   args = ["--qubits", "12", "--layers", "2", "--states-total", "90", "--steps", "2", "--warmup", "1",
-          "--hamiltonian", "tfim", "--cpu-sample-states", "2", "--balance", "measured"]
+          "--hamiltonian", "tfim", "--cpu-sample-states", "2", "--balance", "measured", "--full"]
   cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3",
          "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "3"] + args
   out = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
@@ -237,7 +266,7 @@ def test_bench_qmhl_mode_checks_the_masked_gradient_of_the_timed_step():
   respect to the model's parameters only (qmhl_loss.py:33-34, qnn.py:120-139).  Values [U, T] and the gradient rows of
   the timed step against the C oracle; the frozen (data) half of the gradient is exactly zero."""
   out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "qmhl", "--qubits", "13", "--layers", "2",
-                        "--states-total", "24", "--steps", "1", "--warmup", "1", "--cpu-sample-states", "4"],
+                        "--states-total", "24", "--steps", "1", "--warmup", "1", "--cpu-sample-states", "4", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
   assert out.returncode == 0, out.stderr[-2000:]
   line = _line(out.stdout)
@@ -254,7 +283,7 @@ def test_bench_three_observables_in_one_call():
   normal usage, tests/inference/qnn_test.py:187-190): values of the timed step per observable and the VJP against
   the oracle; the three values come from the observable kernel (one launch), not from measuring passes."""
   out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--hamiltonian", "xxz3", "--qubits", "14",
-                        "--layers", "3", "--states-total", "16", "--steps", "1", "--warmup", "1", "--cpu-sample-states", "4"],
+                        "--layers", "3", "--states-total", "16", "--steps", "1", "--warmup", "1", "--cpu-sample-states", "4", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
   assert out.returncode == 0, out.stderr[-2000:]
   line = _line(out.stdout)
@@ -267,7 +296,7 @@ def test_bench_names_the_block_kernel_when_the_pauli_sum_has_hundreds_of_masks()
   """Config 4's operator (512 random strings) on 16 qubits: lambda = O psi is the largest kernel of the step and
   `roofline.kernel` names the kernel that ran -- the block-grouped one (engine.cpp block_kernel), not the family label."""
   out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--qubits", "16", "--layers", "2", "--hamiltonian", "random512",
-                        "--states-total", "8", "--steps", "1", "--warmup", "1", "--cpu-sample-states", "2"],
+                        "--states-total", "8", "--steps", "1", "--warmup", "1", "--cpu-sample-states", "2", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
   assert out.returncode == 0, out.stderr[-2000:]
   line = _line(out.stdout)
