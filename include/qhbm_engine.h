@@ -270,6 +270,23 @@ int qhbm_sample_counts(qhbm_engine* h, const int8_t* d_bits, int U, const float*
                        int n_programs, const int32_t* shift_gates, const float* shifts,
                        int n_shots, uint64_t seed, int32_t* d_out_counts, void* stream);
 
+/* One adjoint VJP per parameter-shifted program, all programs in one launch set -- the rows of the BKM information
+ * matrix of a QHBM (baselines/train.py:161-249: every circuit variable shifted by +-1/2, a full gradient per shifted
+ * expectation).  Program q is the installed circuit with `shifts[q]` added to the exponent of gate `shift_gates[q]`
+ * (HOST arrays of n_programs entries; gate < 0 = the unshifted circuit), as in qhbm_sample_counts:
+ *   d_prog_grad [n_programs, n_params] float (device):  d_prog_grad[q, p] = sum_{u,k} d_upstream[u,k] * d out_q[u,k] / d params[p]
+ *       (entries of parameters frozen by qhbm_set_gradient_mask are 0; a shift may target a frozen parameter's gate)
+ *   d_prog_vals [n_programs, n_ops]   float (device, may be NULL):  d_prog_vals[q, k] = sum_u row_weights[u] * out_q[u,k]
+ *   d_upstream [U, n_ops] float, d_row_weights [U] float or NULL (= 1).
+ * States are added in state order in fp64 and no atomics are used: the outputs do not depend on chunk_states or
+ * shift_prefix_sharing, and a program with shift_gates[q] < 0 returns the d_grad of qhbm_expectation_vjp(method 0)
+ * bit for bit.  Errors: a gate index out of range, a shifted ISWAPPOW gate (no two-term rule), n_programs < 0, no
+ * observables installed. */
+int qhbm_program_vjps(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params,
+                      int n_programs, const int32_t* shift_gates, const float* shifts,
+                      const float* d_upstream, const float* d_row_weights,
+                      float* d_prog_vals, float* d_prog_grad, void* stream);
+
 /* ---- EBM side -------------------------------------------- */
 /* Spin-parity energies of bitstrings on the current HIP device (no engine handle):
  *   d_energy[i] = sum_k d_thetas[k] * prod_{q in S_k} (1 - 2 x_i[q]),  S_k = set bits of d_masks[k]

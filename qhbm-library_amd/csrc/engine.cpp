@@ -173,6 +173,13 @@ struct qhbm_engine {
   std::vector<float> h_op_scale, h_op_inv_scale;
   DevBuf<double> block_cum;
   DevBuf<int> param_slot_begin, param_slots;
+  // qhbm_program_vjps: per-element copies of bitstrings and upstream rows, the base program's states of a shared prefix,
+  // the gradient rows of the programs in flight, fp64 value accumulators, the programs' shift tables
+  DevBuf<int8_t> pv_bits;
+  DevBuf<float> pv_upstream, pv_rows, pv_shifts;
+  DevBuf<float2> pv_base;
+  DevBuf<double> pv_vals;
+  DevBuf<int> pv_gates, pv_dst;
   std::vector<TimedEvent> events;
   std::vector<TimedEvent> free_events;
 };
@@ -205,7 +212,9 @@ size_t own_bytes(const qhbm_engine* h) {
          buf_bytes(h->slot_factor) + buf_bytes(h->phase_cs) + buf_bytes(h->shift_phases) + buf_bytes(h->terms) +
          buf_bytes(h->global_terms) + buf_bytes(h->obs_groups) + buf_bytes(h->far[0].terms) + buf_bytes(h->far[0].groups) +
          buf_bytes(h->far[1].terms) + buf_bytes(h->far[1].groups) + buf_bytes(h->far[2].terms) + buf_bytes(h->far[2].groups) + buf_bytes(h->obs_bterms) + buf_bytes(h->obs_bgroups) + buf_bytes(h->op_scale) + buf_bytes(h->op_inv_scale) +
-         buf_bytes(h->param_slot_begin) + buf_bytes(h->param_slots) + plan_bytes(h->fwd) + plan_bytes(h->adj) + [&] {
+         buf_bytes(h->param_slot_begin) + buf_bytes(h->param_slots) + buf_bytes(h->pv_bits) + buf_bytes(h->pv_upstream) +
+         buf_bytes(h->pv_rows) + buf_bytes(h->pv_shifts) + buf_bytes(h->pv_base) + buf_bytes(h->pv_vals) +
+         buf_bytes(h->pv_gates) + buf_bytes(h->pv_dst) + plan_bytes(h->fwd) + plan_bytes(h->adj) + [&] {
            size_t cached = 0;  // backward plans of other gradient masks, kept with their device copies (adj_cache)
            for (const auto& kv : h->adj_cache) cached += plan_bytes(*kv.second);
            return cached;
@@ -1025,8 +1034,9 @@ int run_values_chunk(qhbm_engine* h, uint32_t row0, uint32_t c, hipStream_t stre
   return 0;
 }
 
-// The backward passes of a chunk whose (psi, lambda) pair is in the workspace.
-int run_adjoint_chunk(qhbm_engine* h, const int8_t* d_bits, uint32_t s0, uint32_t c, hipStream_t stream) {
+// The backward passes of a chunk whose (psi, lambda) pair is in the workspace.  `e0`: the chunk's pairs start at that
+// element of the workspace (qhbm_program_vjps runs a sub-range of a launch set's elements; 0 everywhere else).
+int run_adjoint_chunk(qhbm_engine* h, const int8_t* d_bits, uint32_t s0, uint32_t c, hipStream_t stream, uint32_t e0 = 0) {
   DevicePlan& b = h->adj;
   const uint32_t n_slots = uint32_t(b.plan.slot_gate.size());
   size_t rows = 0;  // tile_grad: one row of the pass's slots per workgroup
@@ -1038,8 +1048,9 @@ int run_adjoint_chunk(qhbm_engine* h, const int8_t* d_bits, uint32_t s0, uint32_
     hipEvent_t* ev = timer_begin(h, 1, stream);
     PassArgs ba = b.args[i];
     if (h->opt_force_general) ba.flags |= PASS_GENERAL;
-    HIPCHK(launch_pass_adj(b.plan.K, h->opt_adj_exchange != 0, ba, c, h->psi.p, h->lam.p, d_bits, h->model.n, b.prog.p,
-                           b.tables.p, b.coef.p, h->tile_grad.p, s0, stream));
+    const size_t off = size_t(e0) << h->fwd.plan.n_eff;
+    HIPCHK(launch_pass_adj(b.plan.K, h->opt_adj_exchange != 0, ba, c, h->psi.p + off, h->lam.p + off, d_bits, h->model.n,
+                           b.prog.p, b.tables.p, b.coef.p, h->tile_grad.p, s0, stream));
     timer_end(ev, stream);
     // tiles of a state are added in tile order (bit-reproducible, no atomics)
     HIPCHK(launch_reduce_tiles(h->tile_grad.p, c, 1u << ba.n_free, ba.n_slots, h->state_grad.p, n_slots, ba.slot_base,
@@ -1764,6 +1775,217 @@ int qhbm_expectation_vjp(qhbm_engine* h, const int8_t* d_bits, int U, const floa
     }
   }
   HIPCHK(launch_shift_combine(h->prog_acc.p, h->shift_param.p, h->shift_weight.p, int(n_shift_gates), d_grad, P, s));
+  return 0;
+}
+
+// One adjoint VJP per parameter-shifted program (the information matrix of a QHBM: every shifted occurrence of the
+// first half of circuit + inverse, gradient taken over the second half).  The (program, state) pairs are the ELEMENTS
+// of a launch set, as in the parameter-shift VJP: the forward passes run on per-program coefficient copies
+// (PassArgs::prog_states), sharing the base program's prefix; lambda = O psi and the backward sweep then run over the
+// same elements.  The observable and adjoint kernels index their per-state rows by element, so they read per-element
+// copies of the bitstrings and the upstream (launch_replicate_rows) -- no kernel of the default path learns a new map.
+// The backward sweep runs on the shared, unshifted coefficients: gates in front of the first live gate (circuit order)
+// are never un-applied into a gradient.  A program whose shifted gate lies at or behind that gate gets the backward
+// sweep of its own coefficients, one sweep per such program.
+int qhbm_program_vjps(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, int n_programs,
+                      const int32_t* shift_gates, const float* shifts, const float* d_upstream,
+                      const float* d_row_weights, float* d_prog_vals, float* d_prog_grad, void* stream) {
+  if (!h) return 1;
+  if (n_programs < 0) return fail(h, "n_programs must be >= 0");
+  if (n_programs && (!shift_gates || !shifts)) return fail(h, "shift_gates / shifts are NULL");
+  if (int rc = check_call(h, U)) return rc;
+  const int n_gates = int(h->model.gates.size());
+  for (int q = 0; q < n_programs; ++q) {
+    const int g = shift_gates[q];
+    if (g >= n_gates) return fail(h, "shift_gates entry out of range");
+    if (g < 0) continue;
+    const Gate& G = h->model.gates[size_t(g)];
+    if (shifts[q] != 0.f && G.kind == QHBM_GATE_ISWAPPOW)
+      return fail(h, "the two-term parameter-shift rule does not apply to ISWAPPOW; use the adjoint method");
+    if (shifts[q] != 0.f && G.param_idx < 0)
+      return fail(h, "shift_gates entry addresses a gate with a constant exponent: only parametrised gates have shifted programs");
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int P = h->model.n_params;
+  const uint32_t T = uint32_t(h->model.n_ops), n_prog = uint32_t(n_programs);
+  if (n_prog == 0) return 0;
+  if (P) HIPCHK(launch_zero_fill(d_prog_grad, size_t(n_prog) * size_t(P) * sizeof(float), s));
+  if (U == 0) {
+    if (d_prog_vals) HIPCHK(launch_zero_fill(d_prog_vals, size_t(n_prog) * T * sizeof(float), s));
+    return 0;
+  }
+  DevicePlan& d = h->fwd;
+  DevicePlan& b = h->adj;
+  h->retained_U = 0;
+  h->state_grad_U = 0;
+  const int n_pass = int(d.plan.passes.size());
+  const uint32_t n_slots = uint32_t(b.plan.slot_gate.size()), ns1 = std::max<uint32_t>(n_slots, 1);
+  // values and lambda exactly as the adjoint VJP (adjoint_sweep) takes them: an unshifted program is its d_grad bit for bit
+  const bool vm = value_mode(h), mv = multi_value_mode(h), gm = mv && gather_multi_mode(h), skip = vm || mv;
+  // Prefix sharing.  Only when the first forward pass has PASS_NO_ZERO_FILL: without it (an index bit no non-diagonal
+  // gate acts on) later passes rely on pass 0 having zero-filled every tile of an element's OWN state, which a program
+  // that starts behind it from the base state never did.
+  const bool can_share = h->opt_shift_prefix != 0 && n_pass > 1 && (d.plan.passes[0].flags & PASS_NO_ZERO_FILL);
+  int first_measuring = n_pass;
+  std::vector<int> first;
+  if (can_share) first = first_dependent_pass(d.plan, size_t(n_gates), &first_measuring);
+  auto start_of = [&](int g) {
+    if (!can_share) return 0;
+    int k = g < 0 ? n_pass - 1 : std::min(first[size_t(g)], n_pass - 1);
+    if (!skip) k = std::min(k, first_measuring);  // measuring passes write the program's own accumulators
+    while (k > 0 && d.plan.passes[size_t(k)].is_measure_only) --k;  // a program starts at a pass that stores its state
+    return std::max(k, 0);
+  };
+  int first_live = n_gates;  // the backward sweep un-applies gates behind this one only
+  for (int g = 0; g < n_gates; ++g) {
+    const Gate& G = h->model.gates[size_t(g)];
+    if (G.param_idx >= 0 && !h->model.frozen(G.param_idx)) { first_live = g; break; }
+  }
+  std::vector<int> order(n_prog);
+  for (uint32_t q = 0; q < n_prog; ++q) order[q] = int(q);
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return start_of(shift_gates[x]) < start_of(shift_gates[y]); });
+  std::vector<int> sg(n_prog), dst(n_prog);
+  std::vector<float> sv(n_prog);
+  std::vector<char> swept(n_prog);
+  std::vector<uint32_t> group_end(size_t(std::max(n_pass, 1)), 0u);
+  for (uint32_t q = 0; q < n_prog; ++q) {
+    sg[q] = std::max(shift_gates[order[q]], -1);
+    sv[q] = shifts[order[q]];
+    dst[q] = order[q];
+    swept[q] = sg[q] >= first_live && sv[q] != 0.f;
+    group_end[size_t(start_of(sg[q]))] = q + 1;
+  }
+  for (size_t i = 1; i < group_end.size(); ++i) group_end[i] = std::max(group_end[i], group_end[i - 1]);
+  HIPCHK(hipStreamSynchronize(s));  // synchronous copies into buffers an earlier call on this stream may still read
+  HIPCHK(h->pv_gates.upload(sg));
+  HIPCHK(h->pv_shifts.upload(sv));
+  HIPCHK(h->pv_dst.upload(dst));
+
+  // launch-set geometry: Uc states x Pc programs, every element with psi and lambda (+ Uc base states when sharing)
+  const uint32_t stride = uint32_t((d.plan.coef_init.size() + 64 + 63) / 64 * 64);
+  const size_t states_cap = std::max<size_t>(1, budget_bytes(h) / state_bytes(h));
+  uint32_t max_nl = 0;
+  for (const PassArgs& a : d.args) max_nl = std::max(max_nl, a.n_nonlocal);
+  for (const PassArgs& a : b.args) max_nl = std::max(max_nl, a.n_nonlocal);
+  size_t el_cap = std::max<size_t>(1, states_cap / 2);
+  el_cap = std::min<size_t>(el_cap, (size_t(1) << 30) >> max_nl);                         // grid.x = elements << n_nonlocal
+  el_cap = std::min<size_t>(el_cap, (size_t(2) << 30) / (size_t(stride) * sizeof(float)));  // <= 2 GiB of coefficient copies
+  el_cap = std::min<size_t>(el_cap, 65535);                                                // per-state grids of the observable kernels
+  if (h->opt_chunk > 0) el_cap = std::min<size_t>(el_cap, size_t(h->opt_chunk));
+  el_cap = std::max<size_t>(el_cap, 1);
+  const bool share = can_share && group_end[0] < n_prog && states_cap >= 3;
+  const uint32_t Uc = uint32_t(std::min<size_t>(size_t(U), share ? std::max<size_t>(1, std::min(el_cap, states_cap / 3)) : el_cap));
+  const uint32_t Pc = uint32_t(std::max<size_t>(
+      1, std::min<size_t>(n_prog, std::min<size_t>(el_cap, (states_cap - (share ? Uc : 0)) / 2) / Uc)));
+  // gradient rows of the programs in flight: [R, U, n_slots] (a quarter of the budget, at least one program)
+  const size_t row_bytes = size_t(U) * ns1 * sizeof(float);
+  const uint32_t R = uint32_t(std::max<size_t>(1, std::min<size_t>(std::min<size_t>(n_prog, 65535), budget_bytes(h) / 4 / row_bytes)));
+  const uint32_t n_eff = uint32_t(d.plan.n_eff), n = uint32_t(h->model.n);
+  const size_t ne_max = size_t(Uc) * Pc;
+  if (int rc = ensure_state_buffers(h, uint32_t(ne_max), true)) return rc;
+  if (share) HIPCHK(h->pv_base.reserve(size_t(Uc) << n_eff, false));
+  HIPCHK(h->pv_bits.reserve(ne_max * n));
+  HIPCHK(h->pv_upstream.reserve(ne_max * T));
+  HIPCHK(h->vals64.reserve(ne_max * T));
+  HIPCHK(h->vals_batch.reserve(ne_max * T));
+  HIPCHK(h->state_grad.reserve(ne_max * ns1));
+  HIPCHK(h->pv_rows.reserve(size_t(R) * U * ns1, false));
+  HIPCHK(h->pv_vals.reserve(size_t(n_prog) * T));
+  HIPCHK(launch_zero_fill(h->pv_vals.p, size_t(n_prog) * T * sizeof(double), s));
+  // coefficients: the base program's (forward) and the shared backward ones
+  HIPCHK(launch_prep_coefs(d.jobs.p, int(d.plan.jobs.size()), d_params, d.coef.p, -1, 0.0, s));
+  HIPCHK(launch_combine_diag(d.coef.p, d.rec_offsets.p, int(d.plan.record_offsets.size()), 1u, 0u, s));
+  auto prep_adjoint = [&](int gate, double shift) {
+    hipError_t e = launch_prep_coefs(b.jobs.p, int(b.plan.jobs.size()), d_params, b.coef.p, gate, shift, s);
+    if (e == hipSuccess) e = launch_combine_diag(b.coef.p, b.rec_offsets.p, int(b.plan.record_offsets.size()), 1u, 0u, s);
+    return e;
+  };
+  HIPCHK(prep_adjoint(-1, 0.0));
+  bool adjoint_shifted = false;
+  if (h->coef_batch_programs < Pc) {
+    HIPCHK(h->coef_batch.reserve(size_t(Pc) * stride));
+    HIPCHK(launch_replicate(d.coef.p, h->coef_batch.p, uint32_t(d.plan.coef_init.size()), stride, Pc, s));
+    h->coef_batch_programs = Pc;
+  }
+  for (uint32_t qa = 0; qa < n_prog; qa += R) {
+    const uint32_t qb = std::min<uint32_t>(n_prog, qa + R);
+    for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += Uc) {
+      const uint32_t c = std::min<uint32_t>(Uc, uint32_t(U) - s0);
+      HIPCHK(launch_replicate_rows(d_bits, h->pv_bits.p, n, c, s0, Pc * c, s));
+      HIPCHK(launch_replicate_rows(d_upstream, h->pv_upstream.p, T * uint32_t(sizeof(float)), c, s0, Pc * c, s));
+      // k: the pass the programs of this group start at; pv_base holds the base program's states after passes < k
+      for (int k = 0; k < (share ? n_pass : 1); ++k) {
+        const uint32_t gb = share ? (k ? group_end[size_t(k) - 1] : 0u) : 0u, ge = share ? group_end[size_t(k)] : n_prog;
+        const uint32_t lo = std::max(gb, qa), hi = std::min(ge, qb);
+        for (uint32_t q0 = lo; q0 < hi; q0 += Pc) {
+          const uint32_t nq = std::min<uint32_t>(Pc, hi - q0), ne = nq * c;
+          HIPCHK(launch_prep_coefs_batch(d.jobs.p, int(d.plan.jobs.size()), d_params, h->coef_batch.p, h->pv_gates.p + q0,
+                                         h->pv_shifts.p + q0, nq, stride, s));
+          HIPCHK(launch_combine_diag(h->coef_batch.p, d.rec_offsets.p, int(d.plan.record_offsets.size()), nq, stride, s));
+          HIPCHK(launch_zero_fill(h->vals64.p, size_t(ne) * T * sizeof(unsigned long long), s));
+          bool first_pass = true;
+          for (int i = k; i < n_pass; ++i) {
+            const Pass& p = d.plan.passes[size_t(i)];
+            if (skip && p.is_measure_only) continue;
+            PassArgs a = d.args[size_t(i)];
+            a.flags = p.flags & (PASS_INIT_BASIS | PASS_GENERAL | PASS_NO_ZERO_FILL);
+            if (h->opt_force_general) a.flags |= PASS_GENERAL;
+            if (skip) a.flags |= PASS_SKIP_MEASURE;
+            if (!p.is_measure_only || (first_pass && k > 0)) a.flags |= PASS_STORE;  // the final states feed lambda
+            a.prog_states = c;
+            a.coef_stride = stride;
+            hipEvent_t* ev = timer_begin(h, 0, s);
+            HIPCHK(launch_pass_fwd(p.K, d.plan.R, a, ne, h->psi.p, d_bits, int(n), d.prog.p, d.tables.p, h->coef_batch.p,
+                                   h->op_scale.p, h->vals64.p, s0, s, (first_pass && k > 0) ? h->pv_base.p : nullptr));
+            timer_end(ev, s);
+            first_pass = false;
+          }
+          if (!skip && !d.plan.global_terms.empty())
+            HIPCHK(launch_measure_global(h->psi.p, n_eff, ne, h->global_terms.p, uint32_t(d.plan.global_terms.size()),
+                                         h->op_scale.p, h->vals64.p, T, 0u, s));
+          if (mv && !gm)
+            if (int rc = run_values_chunk(h, 0u, ne, s)) return rc;
+          HIPCHK(launch_zero_fill(h->state_grad.p, size_t(ne) * ns1 * sizeof(float), s));
+          if (int rc = run_observable_chunk(h, 0u, ne, h->pv_upstream.p, vm, s, true, gm)) return rc;
+          // backward sweeps: runs of programs on the shared coefficients, a program behind the first live gate on its own
+          for (uint32_t j = 0; j < nq;) {
+            uint32_t j1 = j + 1;
+            if (swept[q0 + j]) {
+              HIPCHK(prep_adjoint(sg[q0 + j], double(sv[q0 + j])));
+              adjoint_shifted = true;
+            } else {
+              while (j1 < nq && !swept[q0 + j1]) ++j1;
+              if (adjoint_shifted) HIPCHK(prep_adjoint(-1, 0.0));
+              adjoint_shifted = false;
+            }
+            if (int rc = run_adjoint_chunk(h, h->pv_bits.p, j * c, (j1 - j) * c, s, j * c)) return rc;
+            j = j1;
+          }
+          // value mode: the sweep ran on the unweighted lambda, the upstream weight goes onto the rows (as adjoint_sweep)
+          if (vm) HIPCHK(launch_scale_rows(h->state_grad.p, ne, ns1, h->pv_upstream.p, s));
+          HIPCHK(launch_scatter_program_rows(h->state_grad.p, h->pv_rows.p, n_slots, c, s0, uint32_t(U), q0 - qa, ne, s));
+          HIPCHK(launch_values_from_fixed(h->vals64.p, h->op_inv_scale.p, h->vals_batch.p, ne * T, T, s));
+          HIPCHK(launch_accumulate_program_values(h->vals_batch.p, d_row_weights, nq, c, T, s0, h->pv_dst.p + q0,
+                                                  h->pv_vals.p, s));
+        }
+        // the base program advances by pass k (its own coefficients) while a later program of this range needs it
+        if (share && ge < qb && !d.plan.passes[size_t(k)].is_measure_only) {
+          const Pass& p = d.plan.passes[size_t(k)];
+          PassArgs a = d.args[size_t(k)];
+          a.flags = (p.flags & (PASS_INIT_BASIS | PASS_GENERAL | PASS_NO_ZERO_FILL)) | PASS_STORE | PASS_SKIP_MEASURE;
+          if (h->opt_force_general) a.flags |= PASS_GENERAL;
+          hipEvent_t* ev = timer_begin(h, 0, s);
+          HIPCHK(launch_pass_fwd(p.K, d.plan.R, a, c, h->pv_base.p, d_bits, int(n), d.prog.p, d.tables.p, d.coef.p,
+                                 h->op_scale.p, h->vals64.p, s0, s));
+          timer_end(ev, s);
+        }
+      }
+    }
+    HIPCHK(launch_reduce_program_grad(h->pv_rows.p, uint32_t(U), n_slots, h->param_slot_begin.p, h->param_slots.p,
+                                      h->slot_factor.p, h->pv_dst.p + qa, qb - qa, d_prog_grad, P, s));
+  }
+  if (adjoint_shifted) HIPCHK(prep_adjoint(-1, 0.0));
+  if (d_prog_vals) HIPCHK(launch_doubles_to_floats(h->pv_vals.p, d_prog_vals, size_t(n_prog) * T, s));
   return 0;
 }
 

@@ -193,5 +193,21 @@ hipError_t launch_scatter_jac(const float* state_grad, uint32_t U, uint32_t n_sl
                               const float* slot_factor, float* jac, uint32_t n_ops, uint32_t op,
                               uint32_t n_params, hipStream_t stream);
 
+// ---- qhbm_program_vjps (kernels.hip, after the reductions of the adjoint VJP) ----
+// dst[e, :] = src[state0 + e % c, :] for e < n_elements (rows of row_bytes bytes): per-element copies of per-state rows
+hipError_t launch_replicate_rows(const void* src, void* dst, uint32_t row_bytes, uint32_t c, uint32_t state0,
+                                 uint32_t n_elements, hipStream_t stream);
+// rows[(prog0 + e / c) * U + state0 + e % c, :] = elem_rows[e, :]  (n_slots floats per row)
+hipError_t launch_scatter_program_rows(const float* elem_rows, float* rows, uint32_t n_slots, uint32_t c, uint32_t state0,
+                                       uint32_t U, uint32_t prog0, uint32_t n_elements, hipStream_t stream);
+// grad[dst[q], p] = reduce_grad of program q's [U, n_slots] rows (the order of launch_reduce_grad)
+hipError_t launch_reduce_program_grad(const float* rows, uint32_t U, uint32_t n_slots, const int* param_slot_begin,
+                                      const int* param_slots, const float* slot_factor, const int* dst, uint32_t n_programs,
+                                      float* grad, int n_params, hipStream_t stream);
+// acc[dst[q], k] += sum_u w[state0 + u] * vals[q * c + u, k], u in order, fp64 (w NULL: 1)
+hipError_t launch_accumulate_program_values(const float* vals, const float* w, uint32_t n_programs, uint32_t c,
+                                            uint32_t n_ops, uint32_t state0, const int* dst, double* acc,
+                                            hipStream_t stream);
+hipError_t launch_doubles_to_floats(const double* src, float* dst, size_t count, hipStream_t stream);
 
 }  // namespace qhbm

@@ -3321,4 +3321,136 @@ hipError_t launch_scatter_jac(const float* state_grad, uint32_t U, uint32_t n_sl
   return hipGetLastError();
 }
 
+// ---- The bookkeeping kernels of qhbm_program_vjps (engine.cpp): one adjoint VJP per parameter-shifted
+// program, the (program, state) pairs batched as the elements of one launch set.
+//
+// The pass, observable and adjoint kernels index their per-state inputs (bitstrings, upstream rows) by
+// state0 + element.  Rather than teach every one of them the element -> state map of a batch of programs, the batch
+// gets per-ELEMENT copies of those rows (replicate_rows_kernel): the default path's kernels are untouched.  The
+// reductions below turn per-element rows into per-program outputs in a fixed order -- states in state order, fp64,
+// no atomics -- so the results do not depend on how the engine cuts the work into launch sets.
+
+// dst[e, :] = src[state0 + e % c, :] for e < n_elements: rows of `row_words` 32-bit words (upstream) ...
+__global__ void replicate_rows_kernel(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, uint32_t row_words,
+                                      uint32_t c, uint32_t state0, uint32_t n_elements) {
+  const size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= size_t(n_elements) * row_words) return;
+  const size_t e = i / row_words, w = i % row_words;
+  dst[i] = src[(size_t(state0) + e % c) * row_words + w];
+}
+// ... and of `row_bytes` bytes (int8 bitstrings)
+__global__ void replicate_bytes_kernel(const int8_t* __restrict__ src, int8_t* __restrict__ dst, uint32_t row_bytes,
+                                       uint32_t c, uint32_t state0, uint32_t n_elements) {
+  const size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= size_t(n_elements) * row_bytes) return;
+  const size_t e = i / row_bytes, b = i % row_bytes;
+  dst[i] = src[(size_t(state0) + e % c) * row_bytes + b];
+}
+
+hipError_t launch_replicate_rows(const void* src, void* dst, uint32_t row_bytes, uint32_t c, uint32_t state0,
+                                 uint32_t n_elements, hipStream_t stream) {
+  const size_t total_bytes = size_t(n_elements) * row_bytes;
+  if (!total_bytes) return hipSuccess;
+  if (row_bytes % 4 == 0) {
+    const size_t total = total_bytes / 4;
+    hipLaunchKernelGGL(replicate_rows_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, stream,
+                       static_cast<const uint32_t*>(src), static_cast<uint32_t*>(dst), row_bytes / 4, c, state0, n_elements);
+  } else {
+    hipLaunchKernelGGL(replicate_bytes_kernel, dim3(unsigned((total_bytes + 255) / 256)), dim3(256), 0, stream,
+                       static_cast<const int8_t*>(src), static_cast<int8_t*>(dst), row_bytes, c, state0, n_elements);
+  }
+  return hipGetLastError();
+}
+
+// rows[(prog0 + e / c) * U + state0 + e % c, :] = elem_rows[e, :]: the gradient rows of a launch set's elements into
+// the [programs, U, n_slots] rows of the programs in flight.
+__global__ void scatter_program_rows_kernel(const float* __restrict__ elem_rows, float* __restrict__ rows, uint32_t n_slots,
+                                            uint32_t c, uint32_t state0, uint32_t U, uint32_t prog0, uint32_t n_elements) {
+  const size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= size_t(n_elements) * n_slots) return;
+  const size_t e = i / n_slots, slot = i % n_slots;
+  const size_t q = prog0 + e / c, s = state0 + e % c;
+  rows[(q * U + s) * n_slots + slot] = elem_rows[i];
+}
+hipError_t launch_scatter_program_rows(const float* elem_rows, float* rows, uint32_t n_slots, uint32_t c, uint32_t state0,
+                                       uint32_t U, uint32_t prog0, uint32_t n_elements, hipStream_t stream) {
+  const size_t total = size_t(n_elements) * n_slots;
+  if (!total) return hipSuccess;
+  hipLaunchKernelGGL(scatter_program_rows_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, stream, elem_rows,
+                     rows, n_slots, c, state0, U, prog0, n_elements);
+  return hipGetLastError();
+}
+
+// grad[dst[q], p] = sum_s sum_slot(p) factor * rows[q, s, slot] -- block (p, q).  The loop and the tree are those of
+// reduce_grad_kernel (kernels.hip) on program q's [U, n_slots] rows, so the row of an unshifted program is
+// qhbm_expectation_vjp's d_grad bit for bit.
+__global__ __launch_bounds__(256) void reduce_program_grad_kernel(
+    const float* __restrict__ rows, uint32_t U, uint32_t n_slots, const int* __restrict__ param_slot_begin,
+    const int* __restrict__ param_slots, const float* __restrict__ slot_factor, const int* __restrict__ dst,
+    float* __restrict__ grad, int n_params) {
+  __shared__ double part[256];
+  const int p = blockIdx.x;
+  const uint32_t q = blockIdx.y;
+  const float* state_grad = rows + size_t(q) * U * n_slots;
+  const int b = param_slot_begin[p], e = param_slot_begin[p + 1];
+  double acc = 0.0;
+  for (uint32_t s = threadIdx.x; s < U; s += 256) {
+    for (int k = b; k < e; ++k) {
+      const int slot = param_slots[k];
+      acc += double(slot_factor[slot]) * double(state_grad[size_t(s) * n_slots + slot]);
+    }
+  }
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if (int(threadIdx.x) < o) part[threadIdx.x] += part[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) grad[size_t(dst[q]) * size_t(n_params) + size_t(p)] = float(part[0]);
+}
+hipError_t launch_reduce_program_grad(const float* rows, uint32_t U, uint32_t n_slots, const int* param_slot_begin,
+                                      const int* param_slots, const float* slot_factor, const int* dst, uint32_t n_programs,
+                                      float* grad, int n_params, hipStream_t stream) {
+  if (n_params == 0 || n_programs == 0) return hipSuccess;
+  hipLaunchKernelGGL(reduce_program_grad_kernel, dim3(unsigned(n_params), n_programs), dim3(256), 0, stream, rows, U,
+                     n_slots, param_slot_begin, param_slots, slot_factor, dst, grad, n_params);
+  return hipGetLastError();
+}
+
+// acc[dst[q], k] += w[state0 + u] * vals[q * c + u, k] for u = 0, 1, ..., c - 1 IN THAT ORDER, one thread per (q, k):
+// over the launch sets, which visit the states of a program in state order, every accumulator sees the same sequence of
+// fp64 additions however the states were cut.  w == NULL: weights 1.
+__global__ void accumulate_program_values_kernel(const float* __restrict__ vals, const float* __restrict__ w,
+                                                 uint32_t n_programs, uint32_t c, uint32_t n_ops, uint32_t state0,
+                                                 const int* __restrict__ dst, double* __restrict__ acc) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_programs * n_ops) return;
+  const uint32_t q = i / n_ops, k = i % n_ops;
+  double a = acc[size_t(dst[q]) * n_ops + k];
+  for (uint32_t u = 0; u < c; ++u) {
+    const double v = double(vals[(size_t(q) * c + u) * n_ops + k]);
+    a += w ? double(w[state0 + u]) * v : v;
+  }
+  acc[size_t(dst[q]) * n_ops + k] = a;
+}
+hipError_t launch_accumulate_program_values(const float* vals, const float* w, uint32_t n_programs, uint32_t c,
+                                            uint32_t n_ops, uint32_t state0, const int* dst, double* acc,
+                                            hipStream_t stream) {
+  const uint32_t total = n_programs * n_ops;
+  if (!total || !c) return hipSuccess;
+  hipLaunchKernelGGL(accumulate_program_values_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, vals, w,
+                     n_programs, c, n_ops, state0, dst, acc);
+  return hipGetLastError();
+}
+
+__global__ void doubles_to_floats_kernel(const double* __restrict__ src, float* __restrict__ dst, size_t count) {
+  const size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i < count) dst[i] = float(src[i]);
+}
+hipError_t launch_doubles_to_floats(const double* src, float* dst, size_t count, hipStream_t stream) {
+  if (!count) return hipSuccess;
+  hipLaunchKernelGGL(doubles_to_floats_kernel, dim3(unsigned((count + 255) / 256)), dim3(256), 0, stream, src, dst, count);
+  return hipGetLastError();
+}
+
 }  // namespace qhbm

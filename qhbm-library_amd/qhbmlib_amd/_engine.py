@@ -38,7 +38,7 @@ ABI_SYMBOLS = (
     "qhbm_set_circuit", "qhbm_set_gradient_mask", "qhbm_set_observables", "qhbm_set_option",
     "qhbm_workspace_bytes", "qhbm_allocated_bytes", "qhbm_expectation", "qhbm_expectation_vjp",
     "qhbm_expectation_retain", "qhbm_expectation_vjp_retained", "qhbm_retained_states", "qhbm_state_gradients",
-    "qhbm_expectation_jacobian", "qhbm_statevector", "qhbm_sample", "qhbm_sample_counts", "qhbm_parity_energy", "qhbm_parity_energy_vjp",
+    "qhbm_expectation_jacobian", "qhbm_statevector", "qhbm_sample", "qhbm_sample_counts", "qhbm_program_vjps", "qhbm_parity_energy", "qhbm_parity_energy_vjp",
     "qhbm_num_passes", "qhbm_describe_schedule",
     "qhbm_kernel_time_ms", "qhbm_traffic_model", "qhbm_flop_model", "qhbm_op_census", "qhbm_clock_probe", "qhbm_plan_builds",
 )
@@ -117,6 +117,7 @@ def load_library():
     lib.qhbm_op_census.argtypes = [vp, i32, i32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i32)]
     lib.qhbm_plan_builds.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)]
     lib.qhbm_clock_probe.argtypes = [vp] + [ctypes.POINTER(ctypes.c_double)] * 3 + [vp]
+    lib.qhbm_program_vjps.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
   except AttributeError:  # an older library given through QHBM_ENGINE_LIB (A/B runs): the probe is optional there
     pass
   _lib = lib
@@ -159,6 +160,20 @@ class _ParityEnergyFunction(torch.autograd.Function):
           w.data_ptr(), grad.data_ptr(),
           ctypes.c_void_p(torch.cuda.current_stream(bits.device).cuda_stream)))
     return grad.to(ctx.theta_device), None, None
+
+
+def parity_sums(bits, masks, weights):
+  """[M] float32: sum_i weights[i] * parity_m(bits[i]) over CUDA `bits` [N, n] for int64 CUDA column `masks` [M]
+  (qhbm_parity_energy_vjp, no autograd)."""
+  lib = load_library()
+  bits = bits.to(torch.int8).contiguous()
+  w = weights.to(device=bits.device, dtype=torch.float32).contiguous()
+  out = torch.empty((masks.numel(),), dtype=torch.float32, device=bits.device)
+  with torch.cuda.device(bits.device):
+    _check_global(lib.qhbm_parity_energy_vjp(
+        bits.data_ptr(), bits.shape[0], bits.shape[1], masks.data_ptr(), masks.numel(), w.data_ptr(), out.data_ptr(),
+        ctypes.c_void_p(torch.cuda.current_stream(bits.device).cuda_stream)))
+  return out
 
 
 def parity_energy(thetas, bits, masks):
@@ -465,6 +480,35 @@ class Engine:
                                        sg.ctypes.data, sv.ctypes.data, int(n_shots), int(seed) & (2**64 - 1),
                                        out.data_ptr(), self._stream()))
     return out
+
+  def program_vjps(self, bits, params, shift_gates, shifts, upstream, row_weights=None):
+    """(prog_vals [n_programs, n_ops], prog_grad [n_programs, n_params]): one adjoint VJP of `upstream` per
+    parameter-shifted program -- `shifts[q]` added to the exponent of gate `shift_gates[q]`, a negative gate = the
+    unshifted circuit -- and the row-weighted sums of its values, all programs in one launch set
+    (include/qhbm_engine.h qhbm_program_vjps)."""
+    self.retained = None
+    bits, params = self._prep(bits, params)
+    sg = np.ascontiguousarray(shift_gates, dtype=np.int32)
+    sv = np.ascontiguousarray(shifts, dtype=np.float32)
+    if sg.shape != sv.shape or sg.ndim != 1:
+      raise ValueError("shift_gates and shifts must be 1-D and of equal length")
+    upstream = torch.as_tensor(upstream).to(device=self.device, dtype=torch.float32).contiguous()
+    if tuple(upstream.shape) != (bits.shape[0], self.n_ops):
+      raise ValueError("upstream must have shape [batch, n_ops]")
+    w_ptr = None
+    if row_weights is not None:
+      row_weights = torch.as_tensor(row_weights).to(device=self.device, dtype=torch.float32).contiguous()
+      if tuple(row_weights.shape) != (bits.shape[0],):
+        raise ValueError("row_weights must have shape [batch]")
+      w_ptr = row_weights.data_ptr()
+    vals = torch.empty((len(sg), self.n_ops), dtype=torch.float32, device=self.device)
+    grad = torch.empty((len(sg), self.n_params), dtype=torch.float32, device=self.device)
+    with torch.cuda.device(self.device):
+      self._check(
+          self._lib.qhbm_program_vjps(self._h, bits.data_ptr(), bits.shape[0], params.data_ptr(), len(sg),
+                                      sg.ctypes.data, sv.ctypes.data, upstream.data_ptr(), w_ptr, vals.data_ptr(),
+                                      grad.data_ptr(), self._stream()))
+    return vals, grad
 
   def expectation_jacobian(self, bits, params):
     self.retained = None
