@@ -131,6 +131,11 @@ int qhbm_set_observables(qhbm_engine* h, int n_ops, const int32_t* term_offsets,
  *   "chunk_states"         states simulated per launch group, 0 = auto
  *   "workspace_budget_mb"  cap on the statevector workspace; 0 = a third of the device's memory
  *   "profile_events"       record HIP events around the pass kernels (qhbm_kernel_time_ms)
+ *   "shift_prefix_sharing" parameter-shift VJP and qhbm_program_vjps: 1 (default) = a shifted program starts at the
+ *                          first forward pass that reads its gate, from the base program's state -- on plans whose
+ *                          first pass writes one tile per state (every index bit meets a non-diagonal gate); a plan
+ *                          with an idle or diagonal-only qubit zero-fills in its first pass and runs every program
+ *                          from the basis state; 0 = always from the basis state.  The outputs are the same bits.
  * Developer knobs for A/B measurements (defaults are the measured best): "measure_tile_qubits"
  * (tile of measurement-only passes, 0 = largest), "adjoint_exchange" (1 = register-resident tile
  * pair with one LDS exchange buffer, 0 = both tiles in LDS), "full_diag_threshold" /

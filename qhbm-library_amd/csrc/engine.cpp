@@ -1112,7 +1112,9 @@ int check_call(qhbm_engine* h, int U) {
 // first_dependent_pass()[g] = that pass for gate g (the pass count for a gate no record depends on); `first_measuring` =
 // the first pass with a measurement op (a program must not start behind it: a pass measures into the program's own
 // accumulators).  Record ranges come from the pass programs (OP_ROUND: n_instances records from its first record;
-// OP_GATE2: a 4 x 4 matrix), jobs from the plan (CoefJob::gate writes at CoefJob::out_off).
+// OP_GATE2: a 4 x 4 matrix), jobs from the plan (CoefJob::gate writes at CoefJob::out_off).  Sound only on plans whose
+// first pass has PASS_NO_ZERO_FILL: a program that starts at pass k > 0 loads only the tiles pass k launches, and on a
+// zero-filling plan the others must already hold zeros of its own state (both callers check the flag).
 std::vector<int> first_dependent_pass(const Plan& plan, size_t n_gates, int* first_measuring) {
   const RecordLayout L(plan.R, false);
   struct Range { uint32_t lo, hi; int pass; };
@@ -1627,6 +1629,11 @@ int qhbm_expectation_vjp(qhbm_engine* h, const int8_t* d_bits, int U, const floa
   if (int rc = forward(h, d_bits, U, d_params, d_out_vals, -1, 0.0, s)) return rc;
   DevicePlan& d = h->fwd;
   const bool from_obs = forward_values_from_observable(h);
+  // Prefix sharing only when the first forward pass has PASS_NO_ZERO_FILL, as in qhbm_program_vjps: without it (an index
+  // bit no non-diagonal gate acts on) later passes, the observable kernel and the global-term measurement rely on pass 0
+  // having zero-filled every tile of a program's OWN state, which a program that starts behind it from the base state
+  // never did -- they would read what an earlier call or launch set left there.
+  const bool can_share = h->opt_shift_prefix != 0 && (d.plan.passes.front().flags & PASS_NO_ZERO_FILL);
   if (!h->shift_ready || h->shift_tables_from_obs != from_obs) {  // shift tables: once per model
     h->shift_tables_from_obs = from_obs;
     std::vector<int> sg, sp;
@@ -1647,7 +1654,7 @@ int qhbm_expectation_vjp(qhbm_engine* h, const int8_t* d_bits, int U, const floa
     const int n_pass = int(d.plan.passes.size());
     int first_measuring = n_pass;
     std::vector<int> first(h->model.gates.size(), 0);
-    if (h->opt_shift_prefix) first = first_dependent_pass(d.plan, h->model.gates.size(), &first_measuring);
+    if (can_share) first = first_dependent_pass(d.plan, h->model.gates.size(), &first_measuring);
     auto start_of = [&](int gate) {
       int k = std::min(first[size_t(gate)], n_pass - 1);
       if (!from_obs) k = std::min(k, first_measuring);   // measuring passes write the program's own accumulators
@@ -1691,7 +1698,7 @@ int qhbm_expectation_vjp(qhbm_engine* h, const int8_t* d_bits, int U, const floa
   cap = std::min<size_t>(cap, (size_t(2) << 30) / (size_t(stride) * sizeof(float)));  // <= 2 GiB of coefficient copies
   if (h->opt_chunk > 0) cap = std::min<size_t>(cap, size_t(h->opt_chunk));
   // sharing needs a second buffer of Uc base states and at least one pass to skip
-  const bool share = h->opt_shift_prefix != 0 && h->shift_group_end.size() > 1 && h->shift_group_end[0] < n_prog && cap >= 2;
+  const bool share = can_share && h->shift_group_end.size() > 1 && h->shift_group_end[0] < n_prog && cap >= 2;
   const uint32_t Uc = uint32_t(std::min<size_t>(size_t(U), share ? cap / 2 : cap));
   const uint32_t Pc = uint32_t(std::max<size_t>(1, std::min<size_t>(n_prog, (cap - (share ? Uc : 0)) / Uc)));
   if (int rc = ensure_state_buffers(h, Uc * Pc, false)) return rc;
@@ -1822,9 +1829,9 @@ int qhbm_program_vjps(qhbm_engine* h, const int8_t* d_bits, int U, const float* 
   const uint32_t n_slots = uint32_t(b.plan.slot_gate.size()), ns1 = std::max<uint32_t>(n_slots, 1);
   // values and lambda exactly as the adjoint VJP (adjoint_sweep) takes them: an unshifted program is its d_grad bit for bit
   const bool vm = value_mode(h), mv = multi_value_mode(h), gm = mv && gather_multi_mode(h), skip = vm || mv;
-  // Prefix sharing.  Only when the first forward pass has PASS_NO_ZERO_FILL: without it (an index bit no non-diagonal
-  // gate acts on) later passes rely on pass 0 having zero-filled every tile of an element's OWN state, which a program
-  // that starts behind it from the base state never did.
+  // Prefix sharing.  Only when the first forward pass has PASS_NO_ZERO_FILL, as in qhbm_expectation_vjp(method 1):
+  // without it (an index bit no non-diagonal gate acts on) later passes rely on pass 0 having zero-filled every tile of
+  // an element's OWN state, which a program that starts behind it from the base state never did.
   const bool can_share = h->opt_shift_prefix != 0 && n_pass > 1 && (d.plan.passes[0].flags & PASS_NO_ZERO_FILL);
   int first_measuring = n_pass;
   std::vector<int> first;

@@ -1536,7 +1536,10 @@ std::string describe_plan(const Plan& p) {
     os << "] mat_ops=" << q.n_mat_ops << " diag_terms=" << q.n_diag_terms << " rounds=" << q.n_rounds
        << " instances=" << q.n_instances << " meas_groups=" << q.n_meas_groups
        << " meas_terms=" << q.n_meas_terms << " slots=" << q.n_slots
-       << (q.is_measure_only ? " [measure-only]" : "") << " words=" << q.prog.size() << " regs=";
+       << (q.is_measure_only ? " [measure-only]" : "");
+    // the first forward pass writes one tile per state, or zero-fills every tile (an index bit no non-diagonal op acts on)
+    if (!p.adjoint && (q.flags & PASS_INIT_BASIS)) os << ((q.flags & PASS_NO_ZERO_FILL) ? " [basis tile only]" : " [zero-fill]");
+    os << " words=" << q.prog.size() << " regs=";
     for (size_t r = 0; r < q.round_regmasks.size(); ++r) os << (r ? "," : "") << std::hex << q.round_regmasks[r] << std::dec;
     if (p.relabel) {
       os << " at=";
