@@ -302,7 +302,8 @@ int qhbm_program_vjps(qhbm_engine* h, const int8_t* d_bits, int U, const float* 
 int qhbm_parity_energy(const int8_t* d_bits, int64_t n_rows, int n_bits,
                        const uint64_t* d_masks, const float* d_thetas, int n_terms,
                        float* d_energy, void* stream);
-/* Its VJP with respect to thetas: d_grad[k] = sum_i d_weights[i] * parity_k(x_i) (overwritten). */
+/* Its VJP with respect to thetas: d_grad[k] = sum_i d_weights[i] * parity_k(x_i) (overwritten), summed in fp64
+ * in a fixed order: bit-identical from call to call. */
 int qhbm_parity_energy_vjp(const int8_t* d_bits, int64_t n_rows, int n_bits,
                            const uint64_t* d_masks, int n_terms, const float* d_weights,
                            float* d_grad, void* stream);

@@ -1485,9 +1485,8 @@ int qhbm_parity_energy_vjp(const int8_t* d_bits, int64_t n_rows, int n_bits, con
                            int n_terms, const float* d_weights, float* d_grad, void* stream) {
   if (n_rows < 0 || n_terms < 0) return fail(nullptr, "negative size");
   if (n_bits < 1 || n_bits > 64) return fail(nullptr, "n_bits must be in [1, 64]");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  hipError_t e = n_terms ? launch_zero_fill(d_grad, size_t(n_terms) * sizeof(float), s) : hipSuccess;
-  if (e == hipSuccess) e = launch_parity_energy_vjp(d_bits, n_rows, n_bits, d_masks, n_terms, d_weights, d_grad, s);
+  hipError_t e = launch_parity_energy_vjp(d_bits, n_rows, n_bits, d_masks, n_terms, d_weights, d_grad,
+                                          static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return fail(nullptr, std::string("qhbm_parity_energy_vjp: ") + hipGetErrorString(e));
   return 0;
 }

@@ -2787,6 +2787,7 @@ hipError_t launch_scale_states(float2* st, size_t count, const float* cs, hipStr
 //      the block prefix sums -> wave prefix scan inside the block -> amplitude index -> bits.
 // ================================================================================
 constexpr uint32_t kSampleBlock = 1024;
+constexpr uint32_t kShotSlice = 65535;  // shots per draw launch (grid.x)
 
 __global__ __launch_bounds__(256) void block_prob_kernel(const float2* __restrict__ psi, uint32_t n,
                                                          double* __restrict__ block_mass) {
@@ -2847,8 +2848,9 @@ __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uin
 
 __global__ __launch_bounds__(64) void draw_kernel(const float2* __restrict__ psi, uint32_t n, int n_user,
                                                   const double* __restrict__ block_cum, uint32_t n_shots,
-                                                  uint64_t seed, uint32_t state0, int8_t* __restrict__ out) {
-  const uint32_t shot = blockIdx.x, s = blockIdx.y, lane = threadIdx.x;
+                                                  uint32_t shot0, uint64_t seed, uint32_t state0,
+                                                  int8_t* __restrict__ out) {
+  const uint32_t shot = shot0 + blockIdx.x, s = blockIdx.y, lane = threadIdx.x;
   const uint32_t nb = (1u << n) / kSampleBlock;
   const double* cum = block_cum + size_t(s) * nb;
   uint32_t c[4] = {shot, state0 + s, 0x51b0c6a1u, 0u};
@@ -2877,7 +2879,10 @@ __global__ __launch_bounds__(64) void draw_kernel(const float2* __restrict__ psi
     const float t = __shfl_up(incl, k);
     if (int(lane) >= k) incl += t;
   }
-  const float excl = incl - mine;
+  // lane l's interval is [incl of lane l - 1, incl of lane l): the intervals tile [0, block mass) with no gap or
+  // overlap (incl - mine would not: its rounding left r in no lane or in two, and the shot went astray)
+  float excl = __shfl_up(incl, 1);
+  if (lane == 0) excl = 0.f;
   // the lane whose interval [excl, incl) holds r; rounding may push r past the block mass:
   // then the last lane with any mass takes it
   const bool hit = (r >= excl && r < incl) || (lane == 63 && r >= incl);
@@ -2887,14 +2892,18 @@ __global__ __launch_bounds__(64) void draw_kernel(const float2* __restrict__ psi
   const int owner = (r >= __shfl(incl, 63)) ? 63 - __builtin_clzll(ballot) : __builtin_ctzll(ballot);
   if (int(lane) == owner) {
     float acc = excl;
-    int pick = -1, last_nz = 0;
+    // r past this lane's sequential sum (it rounds apart from the scan's incl): the last outcome whose mass exceeds
+    // the scans' rounding, never one whose mass is rounding noise of an exact zero
+    const float tol = incl * 0x1p-19f;
+    int pick = -1, last_nz = 0, last_big = -1;
 #pragma unroll
     for (int i = 0; i < kPer; ++i) {
       if (w[i] > 0.f) last_nz = i;
+      if (w[i] > tol) last_big = i;
       acc += w[i];
       if (pick < 0 && r < acc && w[i] > 0.f) pick = i;
     }
-    if (pick < 0) pick = last_nz;
+    if (pick < 0) pick = last_big >= 0 ? last_big : last_nz;
     const uint32_t idx = lo * kSampleBlock + lane * kPer + uint32_t(pick);
     int8_t* o = out + (size_t(state0 + s) * n_shots + shot) * size_t(n_user);
     for (int q = 0; q < n_user; ++q) o[q] = int8_t((idx >> (n_user - 1 - q)) & 1u);
@@ -2906,8 +2915,10 @@ hipError_t launch_sample(const float2* psi, uint32_t n, int n_user, uint32_t n_s
   const uint32_t nb = (1u << n) / kSampleBlock;
   hipLaunchKernelGGL(block_prob_kernel, dim3(nb, n_states), dim3(256), 0, stream, psi, n, block_cum);
   hipLaunchKernelGGL(block_scan_kernel, dim3(n_states), dim3(256), 0, stream, block_cum, nb);
-  if (n_shots) hipLaunchKernelGGL(draw_kernel, dim3(n_shots, n_states), dim3(64), 0, stream, psi, n, n_user, block_cum,
-                                  n_shots, seed, state0, out);
+  // shots in slices of <= kShotSlice workgroups (grid.x); the global shot index feeds the counter, so the cut changes no bit
+  for (uint32_t shot0 = 0; shot0 < n_shots; shot0 += kShotSlice)
+    hipLaunchKernelGGL(draw_kernel, dim3(std::min(kShotSlice, n_shots - shot0), n_states), dim3(64), 0, stream, psi, n,
+                       n_user, block_cum, n_shots, shot0, seed, state0, out);
   return hipGetLastError();
 }
 
@@ -2976,9 +2987,9 @@ __global__ __launch_bounds__(256) void sample_counts_small_kernel(const float2* 
 
 __global__ __launch_bounds__(64) void draw_counts_kernel(const float2* __restrict__ psi, uint32_t n, int n_user,
                                                          const double* __restrict__ block_cum, uint32_t prog_states,
-                                                         uint32_t prog0, uint64_t seed, uint32_t state0,
+                                                         uint32_t prog0, uint32_t shot0, uint64_t seed, uint32_t state0,
                                                          uint32_t n_states_total, int* __restrict__ out) {
-  const uint32_t shot = blockIdx.x, e = blockIdx.y, lane = threadIdx.x;
+  const uint32_t shot = shot0 + blockIdx.x, e = blockIdx.y, lane = threadIdx.x;
   const uint32_t q = prog0 + e / prog_states, srow = state0 + e % prog_states;
   const uint32_t nb = (1u << n) / kSampleBlock;
   const double* cum = block_cum + size_t(e) * nb;
@@ -3008,7 +3019,8 @@ __global__ __launch_bounds__(64) void draw_counts_kernel(const float2* __restric
     const float t = __shfl_up(incl, k);
     if (int(lane) >= k) incl += t;
   }
-  const float excl = incl - mine;
+  float excl = __shfl_up(incl, 1);  // gapless lane intervals, as in draw_kernel
+  if (lane == 0) excl = 0.f;
   const bool hit = (r >= excl && r < incl) || (lane == 63 && r >= incl);
   uint64_t ballot = __ballot(hit && mine > 0.f);
   if (ballot == 0) ballot = __ballot(mine > 0.f);
@@ -3016,14 +3028,18 @@ __global__ __launch_bounds__(64) void draw_counts_kernel(const float2* __restric
   const int owner = (r >= __shfl(incl, 63)) ? 63 - __builtin_clzll(ballot) : __builtin_ctzll(ballot);
   if (int(lane) == owner) {
     float acc = excl;
-    int pick = -1, last_nz = 0;
+    // r past this lane's sequential sum (it rounds apart from the scan's incl): the last outcome whose mass exceeds
+    // the scans' rounding, never one whose mass is rounding noise of an exact zero
+    const float tol = incl * 0x1p-19f;
+    int pick = -1, last_nz = 0, last_big = -1;
 #pragma unroll
     for (int i = 0; i < kPer; ++i) {
       if (w[i] > 0.f) last_nz = i;
+      if (w[i] > tol) last_big = i;
       acc += w[i];
       if (pick < 0 && r < acc && w[i] > 0.f) pick = i;
     }
-    if (pick < 0) pick = last_nz;
+    if (pick < 0) pick = last_big >= 0 ? last_big : last_nz;
     const uint32_t idx = lo * kSampleBlock + lane * kPer + uint32_t(pick);
     atomicAdd(&out[((size_t(q) * n_states_total + srow) << n_user) + (idx & ((1u << n_user) - 1u))], 1);
   }
@@ -3042,9 +3058,9 @@ hipError_t launch_sample_counts(const float2* psi, uint32_t n, int n_user, uint3
   const uint32_t nb = (1u << n) / kSampleBlock;  // (the caller zeroed `out`: this path adds to global counters)
   hipLaunchKernelGGL(block_prob_kernel, dim3(nb, n_elements), dim3(256), 0, stream, psi, n, block_cum);
   hipLaunchKernelGGL(block_scan_kernel, dim3(n_elements), dim3(256), 0, stream, block_cum, nb);
-  if (n_shots)
-    hipLaunchKernelGGL(draw_counts_kernel, dim3(n_shots, n_elements), dim3(64), 0, stream, psi, n, n_user, block_cum,
-                       prog_states, prog0, seed, state0, n_states_total, out);
+  for (uint32_t shot0 = 0; shot0 < n_shots; shot0 += kShotSlice)  // grid.x slices, as in launch_sample
+    hipLaunchKernelGGL(draw_counts_kernel, dim3(std::min(kShotSlice, n_shots - shot0), n_elements), dim3(64), 0, stream,
+                       psi, n, n_user, block_cum, prog_states, prog0, shot0, seed, state0, n_states_total, out);
   return hipGetLastError();
 }
 
@@ -3083,34 +3099,50 @@ __global__ __launch_bounds__(256) void parity_energy_kernel(const int8_t* __rest
 }
 
 // grad[k] = sum_i w[i] * parity_k(x_i): the VJP of the energies with respect to theta.
-// A workgroup keeps 256 x 8 bitstrings (and their weights) in registers and walks the terms.
-constexpr int kParityRows = 8;
-__global__ __launch_bounds__(256) void parity_energy_vjp_kernel(const int8_t* __restrict__ bits, int64_t n_rows, int n,
-                                                                const uint64_t* __restrict__ masks, int n_terms,
-                                                                const float* __restrict__ w,
-                                                                float* __restrict__ grad) {
-  uint64_t x[kParityRows];
-  float wt[kParityRows];
+// One workgroup per group of T terms sweeps every row and accumulates in fp64; the workgroup then reduces its threads
+// in a fixed order.  No atomics: the sums do not depend on the order the workgroups run in, and the call needs no
+// scratch (CapturedLoss captures it in a graph).  Rows are visited kVjpUnroll at a time to keep loads in flight.
+constexpr int kVjpThreads = 1024, kVjpUnroll = 4;
+template <int T>
+__global__ __launch_bounds__(kVjpThreads) void parity_energy_vjp_kernel(const int8_t* __restrict__ bits, int64_t n_rows,
+                                                                        int n, const uint64_t* __restrict__ masks,
+                                                                        int n_terms, const float* __restrict__ w,
+                                                                        float* __restrict__ grad) {
+  __shared__ double part[T][kVjpThreads / 64];
+  const int k0 = int(blockIdx.x) * T, tid = int(threadIdx.x);
+  uint64_t m[T];
+  double acc[T];
 #pragma unroll
-  for (int j = 0; j < kParityRows; ++j) {
-    const int64_t i = (int64_t(blockIdx.x) * kParityRows + j) * 256 + threadIdx.x;
-    x[j] = i < n_rows ? pack_bits(bits + i * n, n) : 0ull;
-    wt[j] = i < n_rows ? w[i] : 0.f;
+  for (int t = 0; t < T; ++t) {
+    m[t] = k0 + t < n_terms ? masks[k0 + t] : 0ull;
+    acc[t] = 0.0;
   }
-  __shared__ float part[4];
-  for (int k = 0; k < n_terms; ++k) {
-    const uint64_t m = masks[k];
-    float acc = 0.f;
+  for (int64_t i0 = tid; i0 < n_rows; i0 += int64_t(kVjpThreads) * kVjpUnroll) {
+    uint64_t x[kVjpUnroll];
+    double wi[kVjpUnroll];
 #pragma unroll
-    for (int j = 0; j < kParityRows; ++j) acc += (__popcll(x[j] & m) & 1) ? -wt[j] : wt[j];
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const float v = part[0] + part[1] + part[2] + part[3];
-      if (v != 0.f) atomicAdd(&grad[k], v);
+    for (int u = 0; u < kVjpUnroll; ++u) {
+      const int64_t i = i0 + int64_t(u) * kVjpThreads;
+      x[u] = i < n_rows ? pack_bits(bits + i * n, n) : 0ull;
+      wi[u] = i < n_rows ? double(w[i]) : 0.0;
     }
-    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < kVjpUnroll; ++u)
+#pragma unroll
+      for (int t = 0; t < T; ++t) acc[t] += (__popcll(x[u] & m[t]) & 1) ? -wi[u] : wi[u];
+  }
+#pragma unroll
+  for (int t = 0; t < T; ++t) {
+    double v = acc[t];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    if ((tid & 63) == 0) part[t][tid >> 6] = v;
+  }
+  __syncthreads();
+  if (tid < T && k0 + tid < n_terms) {
+    double v = 0.0;
+    for (int j = 0; j < kVjpThreads / 64; ++j) v += part[tid][j];
+    grad[k0 + tid] = float(v);
   }
 }
 
@@ -3124,10 +3156,14 @@ hipError_t launch_parity_energy(const int8_t* bits, int64_t n_rows, int n, const
 
 hipError_t launch_parity_energy_vjp(const int8_t* bits, int64_t n_rows, int n, const uint64_t* masks, int n_terms,
                                     const float* w, float* grad, hipStream_t stream) {
-  if (n_rows == 0 || n_terms == 0) return hipSuccess;
-  const int64_t per_block = 256 * kParityRows;
-  hipLaunchKernelGGL(parity_energy_vjp_kernel, dim3(unsigned((n_rows + per_block - 1) / per_block)), dim3(256), 0,
-                     stream, bits, n_rows, n, masks, n_terms, w, grad);
+  if (n_terms == 0) return hipSuccess;  // (every term is written, zero rows included)
+  // one term per workgroup while that fills the machine; beyond, eight terms share each sweep of the rows
+  if (n_terms <= 1024)
+    hipLaunchKernelGGL(parity_energy_vjp_kernel<1>, dim3(unsigned(n_terms)), dim3(kVjpThreads), 0, stream, bits, n_rows,
+                       n, masks, n_terms, w, grad);
+  else
+    hipLaunchKernelGGL(parity_energy_vjp_kernel<8>, dim3(unsigned((n_terms + 7) / 8)), dim3(kVjpThreads), 0, stream,
+                       bits, n_rows, n, masks, n_terms, w, grad);
   return hipGetLastError();
 }
 

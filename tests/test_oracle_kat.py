@@ -409,3 +409,36 @@ def test_fidelity_self_is_one():
   np.testing.assert_allclose(O.fidelity_direct(dm, dm), 1.0, rtol=1e-6)
   u = O.unitary(n, gates, params)
   np.testing.assert_allclose(u.conj().T @ u, np.eye(2**n), atol=1e-12)
+
+
+# ---- the sampler's generator: Philox4x32-10 (Random123 known-answer vectors) --
+@pytest.mark.parametrize("counter,key,want", [
+    ([0, 0, 0, 0], [0, 0], [0x6627e8d5, 0xe169c58d, 0xbc57ac4c, 0x9b00dbd8]),
+    ([0xffffffff] * 4, [0xffffffff] * 2, [0x408f276d, 0x41c83b0e, 0xa20bc7c6, 0x6d5451fd]),
+    ([0x243f6a88, 0x85a308d3, 0x13198a2e, 0x03707344], [0xa4093822, 0x299f31d0],
+     [0xd16cfe09, 0x94fdcceb, 0x5001e420, 0x24126ea1]),
+])
+def test_philox4x32_10_known_answers(counter, key, want):
+  from oracle import sampling as S
+  assert [int(v) for v in S.philox4x32_10(counter, key)] == want
+  # vectorised: the same answer in every row of a batch
+  batch = S.philox4x32_10(np.tile(np.asarray(counter, np.uint64), (3, 1)), key)
+  assert (batch == np.asarray(want, np.uint32)).all()
+
+
+def test_engine_uniforms_and_inverse_cdf():
+  from oracle import sampling as S
+  seed = (0x0123456789 << 24) | 0xabcdef
+  u = S.engine_uniforms(4096, 5, seed, program=2)
+  assert u.dtype == np.float64 and (u >= 0).all() and (u < 1).all()
+  assert abs(u.mean() - 0.5) < 5 * np.sqrt(1 / 12 / 4096)
+  # counter = {shot, row, tag, program}, key = (seed lo, seed hi)
+  words = S.philox4x32_10([7, 5, S.COUNTER_TAG, 2], [seed & 0xffffffff, seed >> 32])
+  assert u[7] == float(words[0]) * 2.0**-32 + float(words[1]) * 2.0**-64
+  assert (S.engine_uniforms(10, 5, seed, 2, shot0=7)[:3] == u[7:10]).all()
+  assert (S.engine_uniforms(16, 6, seed, 2) != u[:16]).all()
+  assert (S.engine_uniforms(16, 5, seed, 3) != u[:16]).all()
+  # inverse CDF: the first outcome whose inclusive prefix exceeds u; zero-mass outcomes are never drawn
+  cum = S.cdf([0.25, 0.0, 0.5, 0.0, 0.25])
+  got = S.inverse_cdf(cum, np.array([0.0, 0.2499, 0.25, 0.7499, 0.75, 0.999999]))
+  assert got.tolist() == [0, 0, 2, 2, 4, 4]

@@ -72,3 +72,45 @@ def test_no_register_spills_in_the_kernels_the_default_planner_selects():
   spec.loader.exec_module(mod)
   assert mod.default_selectable("pass_adjx_kernel<12, 0>") and not mod.default_selectable("pass_adj_kernel<12, true>")
   assert mod.check() == []
+
+
+def test_no_floating_point_atomics_in_the_device_code():
+  """README.md and DESIGN.md promise no floating-point atomics anywhere: every cross-workgroup sum is a fixed-order
+  reduction or an integer (fixed-point) atomic, so a result does not depend on the order the workgroups run in.
+  The gfx950 assembly of both kernel sources, built with the Makefile's flags, must hold no floating-point atomic add
+  of the vector-memory or LDS instruction sets."""
+  import re
+  import shutil
+  import subprocess
+  import tempfile
+  import pytest
+  hipcc = "/opt/rocm/bin/hipcc"
+  if not shutil.which(hipcc):
+    pytest.skip("no hipcc")
+  csrc = os.path.join(ROOT, "qhbm-library_amd", "csrc")
+  float_atomic = re.compile(r"\b(?:global|buffer|flat)_atomic_(?:pk_)?add_(?:f16|bf16|f32|f64)\b"
+                            r"|\bds_(?:pk_)?add(?:_rtn)?_(?:f16|bf16|f32|f64)\b")
+  with tempfile.TemporaryDirectory() as tmp:
+    procs = {}
+    for src in ("kernels.hip", "observable.hip"):
+      asm = os.path.join(tmp, src + ".s")
+      procs[src] = (asm, subprocess.Popen(
+          [hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-mllvm", "-disable-promote-alloca-to-vector=1",
+           "-mllvm", "-amdgpu-sched-strategy=max-ilp", "--cuda-device-only", "-S", src, "-o", asm],
+          cwd=csrc, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
+    for src, (asm, proc) in procs.items():
+      log = proc.communicate(timeout=900)[0]
+      assert proc.returncode == 0, log[-2000:]
+      with open(asm) as f:
+        text = f.read()
+      assert "global_load" in text  # the guard reads real gfx950 device code
+      found, fn = [], "?"
+      for line in text.splitlines():
+        head = re.match(r"^([A-Za-z_.$][\w.$]*):", line)
+        if head and not head.group(1).startswith("."):
+          fn = head.group(1)
+        code = line.split(";")[0]
+        m = float_atomic.search(code)
+        if m:
+          found.append((fn, m.group(0)))
+      assert not found, f"{src}: floating-point atomics in {sorted(set(found))}"
