@@ -292,6 +292,34 @@ int qhbm_program_vjps(qhbm_engine* h, const int8_t* d_bits, int U, const float* 
                       const float* d_upstream, const float* d_row_weights,
                       float* d_prog_vals, float* d_prog_grad, void* stream);
 
+/* A diagonal observable given as a TABLE of energies, E = sum_y d_table[y] |y><y| -- the modular Hamiltonian of a general
+ * BitstringEnergy (an MLP on the bits; qhbmlib/models/energy.py), which is no Pauli sum:
+ *   d_table [2^n_qubits] float (device), indexed like qhbm_statevector (the bitstring read big-endian, qubit 0 most
+ *   significant); d_out[u] = <x_u| C^dagger E C |x_u> = sum_y d_table[y] |<y|C|x_u>|^2      [U] float (device)
+ * No observables need be installed (as for qhbm_statevector): the forward runs the lean, measurement-free passes and
+ * one streaming pass of the table kernel over the final states.  The _retain form leaves the final states in the
+ * workspace, as qhbm_expectation_retain does, for one qhbm_table_expectation_vjp_retained. */
+int qhbm_table_expectation(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params,
+                           const float* d_table, float* d_out, void* stream);
+int qhbm_table_expectation_retain(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params,
+                                  const float* d_table, float* d_out, void* stream);
+/* Values plus one vector-Jacobian product of the table expectation:
+ *   d_grad[p] = sum_u d_upstream[u] * d out[u] / d params[p]            [n_params] float (overwritten; the gradient mask
+ *                                                                       of qhbm_set_gradient_mask applies as in qhbm_expectation_vjp)
+ *   d_table_grad[y] = sum_u d_upstream[u] |<y|C|x_u>|^2                  [2^n_qubits] float (overwritten), NULL = not wanted
+ *   d_out_vals [U] float, may be NULL.
+ * lambda = upstream E psi, then the adjoint sweep.  Values, d_grad and d_table_grad are summed in fp64 in an order fixed by
+ * the state index, with no atomics: bit-identical for any chunk_states.  The _retained form runs on the states a
+ * qhbm_table_expectation_retain kept (same bits, params and table) and consumes them; it fails if nothing suitable is
+ * retained -- any other compute call drops the states -- and the caller falls back to qhbm_table_expectation_vjp.
+ * Errors: d_table NULL, U < 0. */
+int qhbm_table_expectation_vjp(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params,
+                               const float* d_table, const float* d_upstream, float* d_out_vals,
+                               float* d_grad, float* d_table_grad, void* stream);
+int qhbm_table_expectation_vjp_retained(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params,
+                                        const float* d_table, const float* d_upstream, float* d_grad,
+                                        float* d_table_grad, void* stream);
+
 /* ---- EBM side -------------------------------------------- */
 /* Spin-parity energies of bitstrings on the current HIP device (no engine handle):
  *   d_energy[i] = sum_k d_thetas[k] * prod_{q in S_k} (1 - 2 x_i[q]),  S_k = set bits of d_masks[k]

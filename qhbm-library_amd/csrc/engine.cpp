@@ -99,6 +99,7 @@ struct qhbm_engine {
   int opt_obs_xcd_states = -1; // lambda = O psi: one state per XCD at a time (1), every XCD an eighth of each state (0); -1: by state size
   int opt_adj_exchange = 1;  // lean adjoint passes: register-resident tile pair + one LDS exchange buffer
   int retained_U = 0;  // final states of the last qhbm_expectation_retain still sit in psi
+  bool retained_table = false;  // ... of a qhbm_table_expectation_retain (no lambda = O psi; only the table VJP takes them)
   int state_grad_U = 0;  // rows of state_grad the last adjoint VJP filled (qhbm_state_gradients)
   int64_t opt_chunk = 0;
   int64_t opt_budget_mb = 0;  // 0: a third of the device's memory, resolved at first use (budget_bytes)
@@ -180,6 +181,9 @@ struct qhbm_engine {
   DevBuf<float2> pv_base;
   DevBuf<double> pv_vals;
   DevBuf<int> pv_gates, pv_dst;
+  // energy tables (energy_table.hip): per (state, y-block) value partials, per-group folds of the table gradient, the
+  // fold a chunk boundary cut, the running fp64 table gradient
+  DevBuf<double> tab_vpart, tab_gpart, tab_carry, tab_gsum;
   std::vector<TimedEvent> events;
   std::vector<TimedEvent> free_events;
 };
@@ -214,7 +218,8 @@ size_t own_bytes(const qhbm_engine* h) {
          buf_bytes(h->far[1].terms) + buf_bytes(h->far[1].groups) + buf_bytes(h->far[2].terms) + buf_bytes(h->far[2].groups) + buf_bytes(h->obs_bterms) + buf_bytes(h->obs_bgroups) + buf_bytes(h->op_scale) + buf_bytes(h->op_inv_scale) +
          buf_bytes(h->param_slot_begin) + buf_bytes(h->param_slots) + buf_bytes(h->pv_bits) + buf_bytes(h->pv_upstream) +
          buf_bytes(h->pv_rows) + buf_bytes(h->pv_shifts) + buf_bytes(h->pv_base) + buf_bytes(h->pv_vals) +
-         buf_bytes(h->pv_gates) + buf_bytes(h->pv_dst) + plan_bytes(h->fwd) + plan_bytes(h->adj) + [&] {
+         buf_bytes(h->pv_gates) + buf_bytes(h->pv_dst) + buf_bytes(h->tab_vpart) + buf_bytes(h->tab_gpart) +
+         buf_bytes(h->tab_carry) + buf_bytes(h->tab_gsum) + plan_bytes(h->fwd) + plan_bytes(h->adj) + [&] {
            size_t cached = 0;  // backward plans of other gradient masks, kept with their device copies (adj_cache)
            for (const auto& kv : h->adj_cache) cached += plan_bytes(*kv.second);
            return cached;
@@ -1158,6 +1163,100 @@ std::vector<int> first_dependent_pass(const Plan& plan, size_t n_gates, int* fir
   return first;
 }
 
+// ---- energy tables: E = sum_y table[y] |y><y| (a general BitstringEnergy's modular Hamiltonian) ----
+// No observables are needed: the forward runs the lean, measurement-free passes and keeps the state; the table kernel
+// (energy_table.hip) takes the values, lambda = upstream E psi and the table gradient from it.
+int check_table_call(qhbm_engine* h, int U, const float* d_table) {
+  if (!h) return 1;
+  if (int rc = need_device(h)) return rc;
+  if (U < 0) return fail(h, "negative batch size");
+  if (!d_table) return fail(h, "energy table is NULL");
+  return upload_model(h);
+}
+
+// Scratch of the table kernel for chunks of up to cs states (grown before the chunk loop, never inside it).
+int reserve_table_scratch(qhbm_engine* h, uint32_t cs, bool with_grad) {
+  const uint32_t n_eff = uint32_t(h->fwd.plan.n_eff), n = uint32_t(h->model.n);
+  HIPCHK(h->tab_vpart.reserve(size_t(cs) << (n_eff - 10)));
+  if (with_grad) {
+    HIPCHK(h->tab_gpart.reserve(size_t((cs >> table_group_bits(n_eff)) + 2) << n));
+    HIPCHK(h->tab_carry.reserve(size_t(1) << n));
+    HIPCHK(h->tab_gsum.reserve(size_t(1) << n));
+  }
+  return 0;
+}
+
+int run_table_chunk(qhbm_engine* h, int mode, const float* d_table, uint32_t s0, uint32_t c, int U,
+                    const float* d_upstream, float* d_out, hipStream_t s) {
+  hipEvent_t* ev = timer_begin(h, 2, s);
+  HIPCHK(launch_energy_table(mode, h->psi.p, h->lam.p, d_table, uint32_t(h->model.n), uint32_t(h->fwd.plan.n_eff), c, s0,
+                             uint32_t(U), d_upstream, h->tab_vpart.p, d_out, h->tab_gpart.p, h->tab_carry.p, h->tab_gsum.p, s));
+  timer_end(ev, s);
+  return 0;
+}
+
+// Values of the table; `retain`: the batch stays in psi (one chunk, lambda allocated beside it) for the retained VJP.
+int table_forward(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, const float* d_table, float* d_out,
+                  bool retain, hipStream_t s) {
+  DevicePlan& d = h->fwd;
+  h->retained_U = 0;
+  if (retain && adjoint_chunk_states(h, U) < uint32_t(U)) retain = false;  // the batch does not fit one backward chunk
+  HIPCHK(launch_prep_coefs(d.jobs.p, int(d.plan.jobs.size()), d_params, d.coef.p, -1, 0.0, s));
+  HIPCHK(launch_combine_diag(d.coef.p, d.rec_offsets.p, int(d.plan.record_offsets.size()), 1u, 0u, s));
+  const uint32_t cs = retain ? uint32_t(U) : chunk_states(h, U);
+  if (int rc = ensure_state_buffers(h, cs, retain)) return rc;
+  if (int rc = reserve_table_scratch(h, cs, false)) return rc;
+  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += cs) {
+    const uint32_t c = std::min<uint32_t>(cs, uint32_t(U) - s0);
+    if (int rc = run_forward_chunk(h, d_bits, s0, c, true, s, true)) return rc;
+    if (int rc = run_table_chunk(h, TABLE_VALUES, d_table, s0, c, U, nullptr, d_out, s)) return rc;
+  }
+  if (retain) {
+    h->retained_U = U;
+    h->retained_table = true;
+  }
+  return 0;
+}
+
+// lambda = upstream E psi, the backward sweep, d_grad; values if d_out_vals, the table gradient if d_table_grad.
+// `retained`: the final states of a table_forward(retain) are in psi -- no forward passes.
+int table_vjp(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, const float* d_table,
+              const float* d_upstream, float* d_out_vals, float* d_grad, float* d_table_grad, bool retained, hipStream_t s) {
+  DevicePlan& f = h->fwd;
+  DevicePlan& b = h->adj;
+  const int P = h->model.n_params;
+  const size_t dim = size_t(1) << h->model.n;
+  h->retained_U = 0;  // (the backward sweep un-applies psi in place: retained states are consumed)
+  h->state_grad_U = 0;
+  const uint32_t n_slots = uint32_t(b.plan.slot_gate.size());
+  if (!retained) {
+    HIPCHK(launch_prep_coefs(f.jobs.p, int(f.plan.jobs.size()), d_params, f.coef.p, -1, 0.0, s));
+    HIPCHK(launch_combine_diag(f.coef.p, f.rec_offsets.p, int(f.plan.record_offsets.size()), 1u, 0u, s));
+  }
+  HIPCHK(launch_prep_coefs(b.jobs.p, int(b.plan.jobs.size()), d_params, b.coef.p, -1, 0.0, s));
+  HIPCHK(launch_combine_diag(b.coef.p, b.rec_offsets.p, int(b.plan.record_offsets.size()), 1u, 0u, s));
+  HIPCHK(h->state_grad.reserve(size_t(U) * std::max<uint32_t>(n_slots, 1)));
+  HIPCHK(launch_zero_fill(h->state_grad.p, size_t(U) * std::max<uint32_t>(n_slots, 1) * sizeof(float), s));
+  const uint32_t cs = retained ? uint32_t(U) : adjoint_chunk_states(h, U);
+  if (!retained)
+    if (int rc = ensure_state_buffers(h, cs, true)) return rc;
+  if (int rc = reserve_table_scratch(h, cs, d_table_grad != nullptr)) return rc;
+  if (d_table_grad) HIPCHK(launch_zero_fill(h->tab_gsum.p, dim * sizeof(double), s));
+  const int mode = d_table_grad ? TABLE_LAMBDA_GRAD : TABLE_LAMBDA;
+  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += cs) {
+    const uint32_t c = std::min<uint32_t>(cs, uint32_t(U) - s0);
+    if (!retained)
+      if (int rc = run_forward_chunk(h, d_bits, s0, c, true, s, true)) return rc;
+    if (int rc = run_table_chunk(h, mode, d_table, s0, c, U, d_upstream, d_out_vals, s)) return rc;
+    if (int rc = run_adjoint_chunk(h, d_bits, s0, c, s)) return rc;
+  }
+  HIPCHK(launch_reduce_grad(h->state_grad.p, uint32_t(U), n_slots, h->param_slot_begin.p, h->param_slots.p,
+                            h->slot_factor.p, d_grad, P, 0, s));
+  h->state_grad_U = U;
+  if (d_table_grad) HIPCHK(launch_doubles_to_floats(h->tab_gsum.p, d_table_grad, dim, s));
+  return 0;
+}
+
 }  // namespace
 
 // ================================================================================
@@ -1398,6 +1497,7 @@ int qhbm_expectation_retain(qhbm_engine* h, const int8_t* d_bits, int U, const f
   if (int rc = values_end(h, U, d_out, s)) return rc;
   h->retained_U = U;
   h->retained_mu = vm;
+  h->retained_table = false;
   return 0;
 }
 
@@ -1405,6 +1505,7 @@ int qhbm_expectation_vjp_retained(qhbm_engine* h, const int8_t* d_bits, int U, c
                                   const float* d_upstream, float* d_grad, void* stream) {
   if (int rc = check_call(h, U)) return rc;
   if (U <= 0 || h->retained_U != U) return fail(h, "no retained forward state for this batch");
+  if (h->retained_table) return fail(h, "the retained states are an energy-table call's: use qhbm_table_expectation_vjp_retained");
   hipStream_t s = static_cast<hipStream_t>(stream);
   DevicePlan& b = h->adj;
   h->retained_U = 0;  // the backward sweep un-applies psi in place: the state is consumed
@@ -1469,6 +1570,48 @@ int qhbm_statevector(qhbm_engine* h, const int8_t* d_bits, int U, const float* d
                              h->phase_cs.p, s));
   HIPCHK(launch_scale_states(static_cast<float2*>(d_out_states), size_t(U) << h->model.n, h->phase_cs.p, s));
   return 0;
+}
+
+int qhbm_table_expectation(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, const float* d_table,
+                           float* d_out, void* stream) {
+  if (int rc = check_table_call(h, U, d_table)) return rc;
+  if (U == 0) return 0;
+  if (!d_out) return fail(h, "d_out is NULL");
+  return table_forward(h, d_bits, U, d_params, d_table, d_out, false, static_cast<hipStream_t>(stream));
+}
+
+int qhbm_table_expectation_retain(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, const float* d_table,
+                                  float* d_out, void* stream) {
+  if (int rc = check_table_call(h, U, d_table)) return rc;
+  if (U == 0) return 0;
+  if (!d_out) return fail(h, "d_out is NULL");
+  return table_forward(h, d_bits, U, d_params, d_table, d_out, true, static_cast<hipStream_t>(stream));
+}
+
+int qhbm_table_expectation_vjp(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, const float* d_table,
+                               const float* d_upstream, float* d_out_vals, float* d_grad, float* d_table_grad,
+                               void* stream) {
+  if (int rc = check_table_call(h, U, d_table)) return rc;
+  if (!d_grad || (U > 0 && !d_upstream)) return fail(h, "d_grad / d_upstream is NULL");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (U == 0) {
+    h->retained_U = 0;
+    if (h->model.n_params) HIPCHK(launch_zero_fill(d_grad, size_t(h->model.n_params) * sizeof(float), s));
+    if (d_table_grad) HIPCHK(launch_zero_fill(d_table_grad, (size_t(1) << h->model.n) * sizeof(float), s));
+    return 0;
+  }
+  return table_vjp(h, d_bits, U, d_params, d_table, d_upstream, d_out_vals, d_grad, d_table_grad, false, s);
+}
+
+int qhbm_table_expectation_vjp_retained(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params,
+                                        const float* d_table, const float* d_upstream, float* d_grad,
+                                        float* d_table_grad, void* stream) {
+  if (int rc = check_table_call(h, U, d_table)) return rc;
+  if (U <= 0 || h->retained_U != U || !h->retained_table)
+    return fail(h, "no retained energy-table forward state for this batch");
+  if (!d_grad || !d_upstream) return fail(h, "d_grad / d_upstream is NULL");
+  return table_vjp(h, d_bits, U, d_params, d_table, d_upstream, nullptr, d_grad, d_table_grad, true,
+                   static_cast<hipStream_t>(stream));
 }
 
 int qhbm_parity_energy(const int8_t* d_bits, int64_t n_rows, int n_bits, const uint64_t* d_masks,

@@ -210,4 +210,20 @@ hipError_t launch_accumulate_program_values(const float* vals, const float* w, u
                                             hipStream_t stream);
 hipError_t launch_doubles_to_floats(const double* src, float* dst, size_t count, hipStream_t stream);
 
+// ---- energy tables (energy_table.hip): E = sum_y table[y] |y><y| over the c final states of a chunk ----
+enum TableMode : int {
+  TABLE_VALUES = 0,       // d_out[s0 + i] = <psi_i|E|psi_i>, nothing stored
+  TABLE_LAMBDA = 1,       // lambda_i = upstream[s0 + i] E psi_i (zeros at padded indices), values as above if d_out
+  TABLE_LAMBDA_GRAD = 2,  // ... and gsum[y] += sum_i upstream[s0 + i] |psi_i[y]|^2 (fp64, order fixed by global state index)
+};
+// States per group of the 2-D grid, log2 (a function of n_eff only: the fold order of the table gradient depends on it).
+uint32_t table_group_bits(uint32_t n_eff);
+// Groups (rows of gpart, each 2^n doubles) a chunk [s0, s0 + c) touches.
+uint32_t table_groups(uint32_t s0, uint32_t c, uint32_t n_eff);
+// vpart: c * 2^(n_eff - 10) doubles of scratch; gpart: table_groups() * 2^n; carry, gsum: 2^n (TABLE_LAMBDA_GRAD only,
+// gsum zeroed before the first chunk); d_out may be NULL (no values wanted).
+hipError_t launch_energy_table(int mode, const float2* psi, float2* lam, const float* table, uint32_t n, uint32_t n_eff,
+                               uint32_t c, uint32_t s0, uint32_t U, const float* upstream, double* vpart, float* d_out,
+                               double* gpart, double* carry, double* gsum, hipStream_t stream);
+
 }  // namespace qhbm

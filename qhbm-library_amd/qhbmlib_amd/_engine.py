@@ -41,6 +41,8 @@ ABI_SYMBOLS = (
     "qhbm_expectation_jacobian", "qhbm_statevector", "qhbm_sample", "qhbm_sample_counts", "qhbm_program_vjps", "qhbm_parity_energy", "qhbm_parity_energy_vjp",
     "qhbm_num_passes", "qhbm_describe_schedule",
     "qhbm_kernel_time_ms", "qhbm_traffic_model", "qhbm_flop_model", "qhbm_op_census", "qhbm_clock_probe", "qhbm_plan_builds",
+    "qhbm_table_expectation", "qhbm_table_expectation_retain", "qhbm_table_expectation_vjp",
+    "qhbm_table_expectation_vjp_retained",
 )
 
 
@@ -118,6 +120,10 @@ def load_library():
     lib.qhbm_plan_builds.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)]
     lib.qhbm_clock_probe.argtypes = [vp] + [ctypes.POINTER(ctypes.c_double)] * 3 + [vp]
     lib.qhbm_program_vjps.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.qhbm_table_expectation.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    lib.qhbm_table_expectation_retain.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    lib.qhbm_table_expectation_vjp.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.qhbm_table_expectation_vjp_retained.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp]
   except AttributeError:  # an older library given through QHBM_ENGINE_LIB (A/B runs): the probe is optional there
     pass
   _lib = lib
@@ -429,6 +435,65 @@ class Engine:
                                          grad.data_ptr(), int(method),
                                          self._stream()))
     return vals, grad
+
+  def _table(self, table):
+    table = torch.as_tensor(table).to(device=self.device, dtype=torch.float32).contiguous()
+    if table.numel() != (1 << self.n_qubits):
+      raise ValueError(f"an energy table has 2^{self.n_qubits} = {1 << self.n_qubits} entries, got {table.numel()}")
+    return table
+
+  def _table_upstream(self, upstream, batch):
+    upstream = torch.as_tensor(upstream).to(device=self.device, dtype=torch.float32).contiguous()
+    if upstream.numel() != batch:
+      raise ValueError(f"upstream must have {batch} entries (one per state), got {tuple(upstream.shape)}")
+    return upstream
+
+  def table_expectation(self, bits, params, table, retain=False):
+    """Values [batch] of the diagonal observable sum_y table[y] |y><y| (table [2^n], indexed like `statevector`).
+    Needs no installed observables.  With `retain` the final states stay for one `table_expectation_vjp_retained`
+    (`self.retained` is then a token, or None when the batch was too large to keep)."""
+    bits, params = self._prep(bits, params)
+    table = self._table(table)
+    out = torch.empty((bits.shape[0],), dtype=torch.float32, device=self.device)
+    fn = self._lib.qhbm_table_expectation_retain if retain else self._lib.qhbm_table_expectation
+    self.retained = None
+    with torch.cuda.device(self.device):
+      self._check(fn(self._h, bits.data_ptr(), bits.shape[0], params.data_ptr(), table.data_ptr(), out.data_ptr(),
+                     self._stream()))
+    if retain and bits.shape[0] > 0 and self.retained_states() == bits.shape[0]:
+      self._retain_count = getattr(self, "_retain_count", 0) + 1
+      self.retained = self._retain_count
+    return out
+
+  def table_expectation_vjp(self, bits, params, table, upstream, table_grad=True):
+    """(vals [batch], grad [n_params], table_grad [2^n] or None) for the upstream [batch] of `table_expectation`."""
+    self.retained = None
+    bits, params = self._prep(bits, params)
+    table = self._table(table)
+    upstream = self._table_upstream(upstream, bits.shape[0])
+    vals = torch.empty((bits.shape[0],), dtype=torch.float32, device=self.device)
+    grad = torch.zeros((self.n_params,), dtype=torch.float32, device=self.device)
+    tgrad = torch.empty((1 << self.n_qubits,), dtype=torch.float32, device=self.device) if table_grad else None
+    with torch.cuda.device(self.device):
+      self._check(self._lib.qhbm_table_expectation_vjp(
+          self._h, bits.data_ptr(), bits.shape[0], params.data_ptr(), table.data_ptr(), upstream.data_ptr(),
+          vals.data_ptr(), grad.data_ptr(), tgrad.data_ptr() if tgrad is not None else None, self._stream()))
+    return vals, grad, tgrad
+
+  def table_expectation_vjp_retained(self, bits, params, table, upstream, table_grad=True):
+    """(grad [n_params], table_grad [2^n] or None) from the states kept by `table_expectation(..., retain=True)`;
+    raises EngineError if they are gone (then call `table_expectation_vjp`)."""
+    bits, params = self._prep(bits, params)
+    table = self._table(table)
+    upstream = self._table_upstream(upstream, bits.shape[0])
+    grad = torch.zeros((self.n_params,), dtype=torch.float32, device=self.device)
+    tgrad = torch.empty((1 << self.n_qubits,), dtype=torch.float32, device=self.device) if table_grad else None
+    self.retained = None
+    with torch.cuda.device(self.device):
+      self._check(self._lib.qhbm_table_expectation_vjp_retained(
+          self._h, bits.data_ptr(), bits.shape[0], params.data_ptr(), table.data_ptr(), upstream.data_ptr(),
+          grad.data_ptr(), tgrad.data_ptr() if tgrad is not None else None, self._stream()))
+    return grad, tgrad
 
   def state_gradients(self, num_states):
     """[num_states, n_params] rows of the last adjoint VJP (their sum over states is its gradient)."""

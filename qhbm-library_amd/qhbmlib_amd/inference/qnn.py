@@ -20,6 +20,7 @@ from qhbmlib_amd import utils
 from qhbmlib_amd.inference import ebm
 from qhbmlib_amd.models import circuit  # noqa: F401
 from qhbmlib_amd.models import energy
+from qhbmlib_amd.models import energy_utils
 from qhbmlib_amd.models import hamiltonian
 
 Observables = Union[Sequence[ir.PauliSumLike], hamiltonian.Hamiltonian]
@@ -86,6 +87,47 @@ class _ExpectationFunction(torch.autograd.Function):
       else:
         parallel.all_reduce_sum(grad, ctx.group)
     return grad.to(symbol_values.device), None, None, None, None, None, None, None
+
+
+class _TableExpectationFunction(torch.autograd.Function):
+  """values[U, 1] = <x_u| C^dagger diag(table) C |x_u> (qhbm_table_expectation); backward = the table VJP: lambda =
+  upstream * table * psi, the adjoint sweep, and d/d table[y] = sum_u upstream_u |psi_u[y]|^2 -- autograd carries the
+  latter into the energy's variables."""
+
+  @staticmethod
+  def forward(ctx, symbol_values, table, engine, bits, grad_mask=None):
+    ctx.engine, ctx.bits = engine, bits
+    ctx.grad_mask = None if grad_mask is None or all(grad_mask) else tuple(bool(f) for f in grad_mask)
+    wants_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+    if wants_grad:
+      engine.set_gradient_mask(ctx.grad_mask)
+    ctx.save_for_backward(symbol_values, table)
+    out = engine.table_expectation(bits, symbol_values.detach(), table.detach(), retain=wants_grad)
+    ctx.token = engine.retained
+    return out.unsqueeze(1)
+
+  @staticmethod
+  def backward(ctx, upstream):
+    symbol_values, table = ctx.saved_tensors
+    eng = ctx.engine
+    eng.set_gradient_mask(ctx.grad_mask)
+    upstream = upstream.reshape(-1).contiguous()
+    want_table = ctx.needs_input_grad[1]
+    res = None
+    if ctx.token is not None and eng.retained == ctx.token:
+      try:
+        res = eng.table_expectation_vjp_retained(ctx.bits, symbol_values.detach(), table.detach(), upstream,
+                                                 table_grad=want_table)
+      except _engine.EngineError:
+        res = None  # the states are gone after all: simulate again
+    if res is None:
+      _, grad, table_grad = eng.table_expectation_vjp(ctx.bits, symbol_values.detach(), table.detach(), upstream,
+                                                      table_grad=want_table)
+    else:
+      grad, table_grad = res
+    if table_grad is not None:
+      table_grad = table_grad.to(table.device)
+    return grad.to(symbol_values.device), table_grad, None, None, None
 
 
 class ResolvedCircuits(tuple):
@@ -237,15 +279,28 @@ class AnalyticQuantumInference(QuantumInference):
   `ordered_reduction=True`.
   `check_consistency` (default True): before a sharded call the ranks compare a fingerprint of the
   unique bitstrings and the symbol values (8 bytes each) and raise `parallel.ShardMismatchError` if
-  they differ -- differently seeded samplers would otherwise shard different sets, silently."""
+  they differ -- differently seeded samplers would otherwise shard different sets, silently.
+  `energy_tables`: how a `Hamiltonian` is measured.  "off" (default): through the Pauli shards of a `PauliMixin`
+  energy; any other energy raises TypeError, as in the reference.  "general": an energy that is not a `PauliMixin` (an
+  MLP on the bits) is measured exactly through its TABLE E[y] = energy(bitstring y) over the 2^n bitstrings of the total
+  circuit's qubits -- one streaming pass over the final states (`qhbm_table_expectation`), gradients by the adjoint
+  sweep into the circuits and through the table into the energy's variables.  "all": every Hamiltonian goes through
+  its table (one engine call whatever the number of Pauli shards).  Tables need n <= `max_table_qubits` (default 24: a
+  64-MiB table, 16 M energy rows), the adjoint gradient method, and no process group."""
 
   MAX_OPS_PER_CALL = 1024  # kMaxOps of the engine (csrc/program.h)
+  ENERGY_TABLES = ("off", "general", "all")
 
   def __init__(self, input_circuit: circuit.QuantumCircuit, name: Union[None, str] = None,
                device: Union[None, int] = None, gradient_method: int = _engine.GRAD_ADJOINT,
                process_group=None, max_cached_engines: int = 4, ordered_reduction: bool = False,
-               check_consistency: bool = True, shard_weights=None):
+               check_consistency: bool = True, shard_weights=None, energy_tables: str = "off",
+               max_table_qubits: int = 24):
+    if energy_tables not in self.ENERGY_TABLES:
+      raise ValueError(f"energy_tables must be one of {self.ENERGY_TABLES}, got {energy_tables!r}")
     super().__init__(input_circuit, name)
+    self.energy_tables = energy_tables
+    self.max_table_qubits = int(max_table_qubits)
     if shard_weights is not None and ordered_reduction:
       raise ValueError("ordered_reduction=True (regression runs that compare rank counts) uses equal blocks only")
     self.shard_weights = None if shard_weights is None else [float(w) for w in shard_weights]
@@ -287,13 +342,46 @@ class AnalyticQuantumInference(QuantumInference):
       dev = torch.cuda.current_device() if self._device is None else self._device
       eng = _engine.Engine(dev)
       eng.set_circuit(n_qubits, flat_gates, n_symbols)
-      eng.set_observables([list(m) for m in op_masks])
+      if op_masks:  # (the table route installs no observables)
+        eng.set_observables([list(m) for m in op_masks])
       return eng
     return self._engines.get(key, make)
 
+  def _table_route(self, observables):
+    if not isinstance(observables, hamiltonian.Hamiltonian) or self.energy_tables == "off":
+      return False
+    return self.energy_tables == "all" or not isinstance(observables.energy, energy.PauliMixin)
+
+  def _table_expectation(self, circuits, symbol_names, symbol_values, observables):
+    """[U, 1] of the Hamiltonian measured through its energy table (`energy_tables`)."""
+    unique_states, total_circuit = circuits
+    qubits = total_circuit.qubits
+    n = len(qubits)
+    if n > self.max_table_qubits:
+      raise ValueError(f"energy_tables={self.energy_tables!r}: the total circuit has {n} qubits, above "
+                       f"max_table_qubits={self.max_table_qubits} (a table has 2^n entries)")
+    if self._group() is not None:
+      raise ValueError(f"energy_tables={self.energy_tables!r} does not shard over a process_group yet")
+    if self.gradient_method != _engine.GRAD_ADJOINT:
+      raise ValueError(f"energy_tables={self.energy_tables!r} takes the adjoint gradient only, not the "
+                       "parameter-shift rule")
+    # row y = the bitstring of amplitude index y (qubit 0 most significant), as the sampled path maps a shot outcome;
+    # under tfq_compat_bit_order only the injector columns are permuted (_engine_bits), never the table
+    table = energy_utils.energy_table(observables.energy, n, self.max_table_qubits)
+    bits = _engine_bits(total_circuit, unique_states)
+    values = _row_of_tiled(symbol_values, total_circuit).to(torch.float32)
+    flat_gates = total_circuit.pqc.flat_gates(qubits, list(symbol_names))
+    eng = self._engine_for(n, flat_gates, len(symbol_names), [])
+    grad_mask = getattr(circuits, "gradient_mask", None)
+    if grad_mask is not None and len(grad_mask) != len(symbol_names):
+      grad_mask = None
+    return _TableExpectationFunction.apply(values, table.to(eng.device), eng, bits, grad_mask)
+
   def _expectation(self, circuits, symbol_names, symbol_values, observables):
     """See qnn.py:114-139.  A Hamiltonian is only accepted if its energy inherits from
-    PauliMixin."""
+    PauliMixin, unless `energy_tables` routes it through its table."""
+    if self._table_route(observables):
+      return self._table_expectation(circuits, symbol_names, symbol_values, observables)
     if isinstance(observables, hamiltonian.Hamiltonian):
       if not isinstance(observables.energy, energy.PauliMixin):
         raise TypeError("General Hamiltonians not accepted.  "

@@ -71,3 +71,35 @@ class Parity(torch.nn.Module):
   def forward(self, inputs):
     cols = [torch.prod(inputs[..., list(ix)], dim=-1) for ix in self.indices]
     return torch.stack(cols, dim=-1)
+
+
+_ALL_BITSTRINGS = {}
+
+
+def all_bitstrings(n: int, device=None) -> torch.Tensor:
+  """int8 [2^n, n]: row y holds the bits of y read big-endian (column j = bit n-1-j of y), the order of
+  `itertools.product([0, 1], repeat=n)` (ebm.py:445-447) and of a state vector's amplitudes.  Cached per (n, device)."""
+  device = torch.device("cpu") if device is None else torch.device(device)
+  key = (int(n), device)
+  rows = _ALL_BITSTRINGS.get(key)
+  if rows is None:
+    index = torch.arange(1 << n, dtype=torch.int64, device=device).unsqueeze(1)
+    shifts = torch.arange(n - 1, -1, -1, dtype=torch.int64, device=device).unsqueeze(0)
+    rows = ((index >> shifts) & 1).to(torch.int8)
+    if len(_ALL_BITSTRINGS) >= 8:
+      _ALL_BITSTRINGS.clear()
+    _ALL_BITSTRINGS[key] = rows
+  return rows
+
+
+def energy_table(input_energy, n: int, max_qubits: int = 24) -> torch.Tensor:
+  """float32 [2^n]: E[y] = input_energy(row y of `all_bitstrings(n)`), the diagonal of the energy's operator in the
+  computational basis, evaluated on the device of the energy's variables and differentiable with respect to them."""
+  if n > max_qubits:
+    raise ValueError(f"an energy table over {n} qubits has 2^{n} entries: above max_table_qubits = {max_qubits}")
+  device = next(iter(input_energy.parameters()), torch.zeros(())).device
+  e = input_energy(all_bitstrings(n, device))
+  if e.numel() != 1 << n or not (e.dim() == 1 or (e.dim() == 2 and e.shape[1] == 1)):
+    raise ValueError(f"the energy of {1 << n} bitstrings must have shape [{1 << n}] or [{1 << n}, 1], "
+                     f"got {tuple(e.shape)}")
+  return e.reshape(-1).to(torch.float32)
