@@ -15,6 +15,7 @@
 
 #include "../../include/qhbm_engine.h"
 #include "kernels.h"
+#include "plan_args.h"
 #include "program.h"
 #include "schedule.h"
 
@@ -233,8 +234,11 @@ int need_device(qhbm_engine* h) {
   return 0;
 }
 
-void fill_args(const Plan& plan, const Model& m, std::vector<PassArgs>* args, std::vector<uint32_t>* prog,
-               std::vector<uint32_t>* tables) {
+}  // namespace
+
+// (declared in plan_args.h: the host-only plan emulator of tests/sanitize/ executes plans with these arguments)
+void qhbm::fill_args(const Plan& plan, const Model& m, std::vector<PassArgs>* args, std::vector<uint32_t>* prog,
+                     std::vector<uint32_t>* tables) {
   args->clear();
   prog->clear();
   tables->clear();
@@ -346,6 +350,8 @@ void fill_args(const Plan& plan, const Model& m, std::vector<PassArgs>* args, st
     a.n_free = a.n_nonlocal - uint32_t(__builtin_popcount(a.zero_mask));
   }
 }
+
+namespace {
 
 double pass_flops_per_amplitude(const Plan& plan, const Pass& p);
 
@@ -738,7 +744,7 @@ int upload_model(qhbm_engine* h) {
   {
     std::vector<ShiftPhase> sp;
     for (const Gate& G : h->model.gates)
-      if (G.global_shift != 0.f && G.kind != QHBM_GATE_I)
+      if (G.global_shift != 0.f)  // (an identity too: the gate is exp(i pi t global_shift) I**t, include/qhbm_engine.h)
         sp.push_back(ShiftPhase{G.param_idx, G.param_idx >= 0 ? G.scalar : 0.f, G.offset, G.global_shift});
     for (const auto& gp : h->fwd.plan.gate_phases) {  // lowered SWAP / ISWAP powers (schedule.cpp lower())
       const Gate& G = h->model.gates[size_t(gp.first)];

@@ -2260,14 +2260,17 @@ __global__ __launch_bounds__(256) void measure_global_kernel(
   for (int a = 0; a < 4; ++a) own[a] = ps[j0 + 256u * a];
   for (uint32_t k = 0; k < n_terms; ++k) {
     const DevTerm tm = terms[k];  // wave-uniform
+    // i^ny has period 4, and DevTerm::ny is the NUMBER of Y factors (engine.cpp): a term with five or six of them
+    // was measured with the wrong sign before the count was reduced here
+    const uint32_t ny = tm.ny & 3u;
     float acc = 0.f;
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       const uint32_t j = j0 + 256u * a;
       const float2 q = ps[j ^ tm.x];
       const float wr = q.x * own[a].x + q.y * own[a].y, wi = q.x * own[a].y - q.y * own[a].x;  // conj(q) * own
-      float v = (tm.ny & 1u) ? wi : wr;
-      if (tm.ny == 1u || tm.ny == 2u) v = -v;
+      float v = (ny & 1u) ? wi : wr;
+      if (ny == 1u || ny == 2u) v = -v;
       acc += (__popc(j & tm.z) & 1) ? -v : v;
     }
     acc = wave_sum(acc * tm.coeff);
@@ -2323,7 +2326,7 @@ __global__ void prep_coefs_kernel(const CoefJob* __restrict__ jobs, int n_jobs,
     coef += size_t(blockIdx.y) * coef_stride;
   }
   const CoefJob jb = jobs[j];
-  double t = double(jb.offset);
+  double t = double(jb.offset) + double(jb.add_offset);  // (summed in double: schedule.h CoefJob::add_offset)
   if (jb.param_idx >= 0) t += double(jb.scalar) * double(params[jb.param_idx]);
   if (shift_gate >= 0 && jb.gate == shift_gate) t += shift;  // (negative = unshifted, whatever the value: fixed ops carry gate -2)
   float* o = coef + jb.out_off;
@@ -2728,7 +2731,7 @@ __global__ void global_phase_kernel(const CoefJob* __restrict__ jobs, int n_jobs
   for (int j = threadIdx.x; j < n_jobs; j += 256) {
     const CoefJob jb = jobs[j];
     if (jb.mop != MOP_X && jb.mop != MOP_Y) continue;
-    double t = double(jb.offset);
+    double t = double(jb.offset) + double(jb.add_offset);
     if (jb.param_idx >= 0) t += double(jb.scalar) * double(params[jb.param_idx]);
     if (jb.mop == MOP_X) {
       t *= double(jb.mult);

@@ -537,12 +537,14 @@ class Builder {
     job.gate = op.gate;
     job.param_idx = G.param_idx;
     job.scalar = G.scalar;
-    job.offset = G.offset + op.add_offset;
+    job.offset = G.offset;
+    job.add_offset = op.add_offset;
     if (op.fixed) {  // a constant of the decomposition: not the gate's exponent, never shifted with it
       job.gate = -2;
       job.param_idx = -1;
       job.scalar = 0.f;
       job.offset = op.fixed_t;
+      job.add_offset = 0.f;
     }
     job.out_off = 0;
     job.dagger = adjoint_ ? 1 : 0;

@@ -52,6 +52,10 @@ struct CoefJob {
   int32_t swap;       // MAT2: matrix index bits swapped
   int32_t dagger;     // write U^dagger (adjoint plan), followed by the generator
   float mult;         // MOP_PHASE: multiplier of the exponent
+  // a constant of the lowering folded into this gate's exponent (schedule.cpp lower(): Z^(1/2) Z**t = Z**(t + 1/2)); kept
+  // apart from `offset` and added in double -- offset + 1/2 is not a float in general, and the sum rounded to one moved
+  // the phase by up to 1e-7 (found by the plan emulator of tests/sanitize/)
+  float add_offset;
 };
 
 struct Pass {

@@ -17,10 +17,13 @@
 //   * through the C ABI: pass counts > 0, flop / traffic models and the micro-op census finite and >= 0, and a
 //     plan rebuilt after gradient-mask changes equals the plan of a fresh engine given the final mask.
 #include <algorithm>
+#include <array>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <random>
 #include <set>
@@ -30,10 +33,14 @@
 
 #include "../../include/qhbm_engine.h"
 #include "../../qhbm-library_amd/csrc/schedule.h"
+#include "plan_emulate.h"
 
 using namespace qhbm;
 
 static int g_failures = 0;
+static double g_oracle_seconds = 0.0, g_forward_seconds = 0.0, g_adjoint_seconds = 0.0;  // where an emulation run spends its time
+static const int kEmulateCases = 360;  // default of --emulate: the floors of kFeatureFloors are set for it
+static const int kForcedGreedyFloor = 50;  // of the forced orders (floor 100), how many must be a last entry: the greedy order
 static std::string g_context;
 #define CHECK(cond, ...)                                                        \
   do {                                                                          \
@@ -289,21 +296,25 @@ static void check_trainable_covered(const Model& m, const Plan& adj, const std::
   }
 }
 
+static void fill_terms(Case* c) {
+  for (int op = 0; op < c->m.n_ops; ++op)
+    for (int j = c->term_offsets[size_t(op)]; j < c->term_offsets[size_t(op) + 1]; ++j) {
+      PauliTerm t;
+      t.coeff = c->coeffs[size_t(j)];
+      t.x = uint32_t(c->xs[size_t(j)]);
+      t.z = uint32_t(c->zs[size_t(j)]);
+      t.ny = __builtin_popcount(t.x & t.z);
+      t.op = op;
+      c->m.terms.push_back(t);
+    }
+}
+
 static int fuzz_one(std::mt19937_64& rng, int n, int index) {
   auto U = [&](int lo, int hi) { return int(std::uniform_int_distribution<int>(lo, hi)(rng)); };
   Case c = random_case(rng, n);
   // observables in the scheduler's form (engine.cpp set_observables: qubit q <-> index bit n - 1 - q is done there; the
   // masks here are already in index space)
-  for (int op = 0; op < c.m.n_ops; ++op)
-    for (int j = c.term_offsets[size_t(op)]; j < c.term_offsets[size_t(op) + 1]; ++j) {
-      PauliTerm t;
-      t.coeff = c.coeffs[size_t(j)];
-      t.x = uint32_t(c.xs[size_t(j)]);
-      t.z = uint32_t(c.zs[size_t(j)]);
-      t.ny = __builtin_popcount(t.x & t.z);
-      t.op = op;
-      c.m.terms.push_back(t);
-    }
+  fill_terms(&c);
   char ctx[128];
   std::map<JobKey, int> ref_jobs;
   bool have_ref = false;
@@ -392,6 +403,909 @@ static int fuzz_one(std::mt19937_64& rng, int n, int index) {
   return 0;
 }
 
+
+// =====================================================================================================================
+// Emulation mode: the plans are EXECUTED on the CPU in complex128 (plan_emulate.h) and compared with a dense oracle.
+// =====================================================================================================================
+using emu::cd;
+
+enum Feature {
+  F_FWD_MULTI, F_ADJ_MULTI, F_RELABEL, F_NO_ZERO_FILL, F_DENSE_TAIL, F_EARLY_MEASURE, F_MEASURE_ONLY, F_WHT, F_GLOBAL_TERMS,
+  F_WIDE_PASS, F_GENERAL, F_GATE2, F_FULL, F_CPH_TILE, F_CPH_THREAD, F_DEAD_MASK, F_FORCED_ORDER, F_GRAD_MASK, F_PADDED, F_COUNT
+};
+static const char* const kFeatureNames[F_COUNT] = {
+    "fwd_multi_pass", "adj_multi_pass", "relabel", "no_zero_fill", "dense_tail", "early_measure", "measure_only_pass", "wht",
+    "global_terms", "wide_pass", "general", "gate2", "full", "cph_tile", "cph_thread", "dead_mask", "forced_order", "grad_mask", "padded"};
+// floors of the default run (tests/test_sanitize_cpu.py asserts them on the summary line)
+static const int kFeatureFloors[F_COUNT] = {400, 400, 100, 100, 50, 100, 50, 50, 30, 20, 200, 100, 200, 200, 200, 50, 100, 200, 150};
+
+// Which features an emulated plan contains (forced order / gradient mask are the caller's to add).
+static uint32_t plan_features(const Model& m, const Plan& plan) {
+  uint32_t f = 0;
+  const RecordLayout L(plan.R, plan.adjoint);
+  if (plan.passes.size() >= 2) f |= 1u << (plan.adjoint ? F_ADJ_MULTI : F_FWD_MULTI);
+  if (plan.dense_tail) f |= 1u << F_DENSE_TAIL;
+  if (!plan.global_terms.empty()) f |= 1u << F_GLOBAL_TERMS;
+  if (m.n < kMinTileBits) f |= 1u << F_PADDED;
+  size_t last_circuit = plan.passes.size();
+  for (size_t pi = 0; pi < plan.passes.size(); ++pi)
+    if (plan.passes[pi].completes_circuit) last_circuit = pi;
+  for (size_t pi = 0; pi < plan.passes.size(); ++pi) {
+    const Pass& p = plan.passes[pi];
+    if (p.flags & PASS_RELABEL) f |= 1u << F_RELABEL;
+    if (p.flags & PASS_NO_ZERO_FILL) f |= 1u << F_NO_ZERO_FILL;
+    if (p.flags & PASS_GENERAL) f |= 1u << F_GENERAL;
+    if (p.is_measure_only) f |= 1u << F_MEASURE_ONLY;
+    if (p.K > plan.K) f |= 1u << F_WIDE_PASS;
+    size_t pc = 0;
+    while (pc < p.prog.size()) {
+      const uint32_t w0 = p.prog[pc], opc = w0 & 0xffu;
+      if (opc == OP_ROUND) {
+        const uint32_t n_inst = (w0 & ~kRoundNoBarrier) >> 8, first = p.prog[pc + 2];
+        if (p.prog[pc + 4]) f |= 1u << F_DEAD_MASK;
+        for (uint32_t i = 0; i < n_inst; ++i) {
+          const uint32_t* rec = &plan.coef_init[first + size_t(i) * size_t(L.words())];
+          if (rec[1] & kFullDiagFlag) f |= 1u << F_FULL;
+          for (int k = 0; k < 8; ++k)
+            if (rec[1] >> k & 1u) f |= 1u << ((rec[L.pred(k)] >> 8) ? F_CPH_TILE : F_CPH_THREAD);
+        }
+        pc += kRoundWords;
+      } else if (opc == OP_GATE2) {
+        f |= 1u << F_GATE2;
+        pc += kGate2Words;
+      } else if (opc == OP_MEASURE_WHT) {
+        f |= 1u << F_WHT;
+        if (pi < last_circuit) f |= 1u << F_EARLY_MEASURE;
+        pc += size_t(kWhtHeaderWords) + size_t(w0 >> 8) * kMeasTermWords;
+      } else if (opc == OP_MEASURE) {
+        if ((w0 >> 8) && pi < last_circuit) f |= 1u << F_EARLY_MEASURE;
+        ++pc;
+        for (uint32_t g = 0; g < (w0 >> 8); ++g) pc += 2 + size_t(p.prog[pc + 1]) * kMeasTermWords;
+      } else {
+        break;
+      }
+    }
+  }
+  return f;
+}
+
+struct EmuStats {
+  long plans = 0, runs = 0, skip_runs = 0;
+  long forced_rank[8] = {0}, forced_greedy = 0, forced_unplanned = 0;  // forced pass orders by their entry in candidate_orders; the last entry is the greedy order
+  long feat[F_COUNT] = {0};
+  double max_state = 0.0, max_value = 0.0, max_grad = 0.0;  // largest error seen, as a share of its bar
+  double max_state_abs = 0.0, max_value_abs = 0.0, max_grad_abs = 0.0;
+};
+
+// The oracle's side of one case: random parameters (float-representable, as the engine receives them), two random
+// input bitstrings, a random upstream per observable.
+struct CaseRun {
+  std::vector<double> params, up, op_norm;
+  uint32_t basis[2];
+  std::vector<cd> psi[2], lam[2];      // n_eff qubits, logical order (padding qubits are the high index bits, |0>)
+  std::vector<double> values[2], grad[2];
+};
+static CaseRun make_run(std::mt19937_64& rng, const Model& m) {
+  CaseRun r;
+  std::uniform_real_distribution<float> P(-2.f, 2.f), Un(-1.f, 1.f);
+  for (int i = 0; i < m.n_params; ++i) r.params.push_back(double(P(rng)));
+  for (int i = 0; i < m.n_ops; ++i) r.up.push_back(double(Un(rng)));
+  r.op_norm.assign(size_t(m.n_ops), 0.0);
+  for (const PauliTerm& t : m.terms) r.op_norm[size_t(t.op)] += std::fabs(double(t.coeff));
+  const size_t n_eff = size_t(std::max(m.n, int(kMinTileBits)));
+  for (int b = 0; b < 2; ++b) {
+    r.basis[b] = uint32_t(rng() & ((1ull << m.n) - 1ull));
+    std::vector<cd> psi = emu::oracle_state(m, r.params, r.basis[b]);
+    r.values[b] = emu::oracle_values(m, psi);
+    std::vector<cd> lam = emu::oracle_apply_observables(m, psi, r.up);
+    r.grad[b] = emu::oracle_gradient(m, r.params, r.basis[b], r.up);
+    psi.resize(size_t(1) << n_eff, cd(0.0, 0.0));
+    lam.resize(size_t(1) << n_eff, cd(0.0, 0.0));
+    r.psi[b] = std::move(psi);
+    r.lam[b] = std::move(lam);
+  }
+  return r;
+}
+
+enum Compare : unsigned { CMP_STATE = 1, CMP_VALUES = 2, CMP_GRAD = 4, CMP_ALL = 7 };
+static unsigned g_compare = CMP_ALL;  // (--self-test-without: one comparison off, to show what only it catches)
+typedef std::function<void(std::vector<PassArgs>*)> ArgsTweak;
+
+// Emulates a forward plan on both bitstrings and compares final state and values with the oracle.  Returns an empty
+// string when everything agrees, else the first disagreement.
+struct Stopwatch {
+  double* acc;
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  explicit Stopwatch(double* a) : acc(a) {}
+  ~Stopwatch() { *acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+};
+static std::string forward_disagreement(const Model& m, const Plan& plan, const CaseRun& run, bool skip_measure, unsigned what,
+                                        EmuStats* st, ArgsTweak tweak = nullptr) {
+  Stopwatch sw(&g_forward_seconds);
+  emu::Emulation e;
+  emu::emu_prepare(m, plan, run.params, &e);
+  if (!e.err.empty()) return "prepare: " + e.err;
+  if (tweak) tweak(&e.args);
+  char msg[256];
+  for (int b = 0; b < 2; ++b) {
+    emu::ForwardResult fr;
+    if (!emu::emu_forward(&e, run.basis[b], skip_measure, &fr)) return "forward: " + e.err;
+    if (st) { ++st->runs; st->skip_runs += skip_measure; }
+    if (what & g_compare & CMP_STATE) {
+      if (!fr.have_final) return "no pass completes the circuit";
+      const std::vector<cd>& ref = run.psi[b];
+      if (fr.final_state.size() != ref.size()) return "state size";
+      cd ip(0.0, 0.0);
+      for (size_t i = 0; i < ref.size(); ++i) ip += std::conj(ref[i]) * fr.final_state[i];
+      if (!(std::abs(ip) > 0.5)) { std::snprintf(msg, sizeof msg, "bitstring %d: overlap with the oracle's state %g", b, std::abs(ip)); return msg; }
+      const cd ph = ip / std::abs(ip);
+      double worst = 0.0;
+      for (size_t i = 0; i < ref.size(); ++i) {
+        const double d = std::abs(fr.final_state[i] - ph * ref[i]);
+        if (!(d <= 1e-10)) { std::snprintf(msg, sizeof msg, "bitstring %d: amplitude %zu off by %g (bar 1e-10)", b, i, d); return msg; }
+        worst = std::max(worst, d);
+      }
+      if (st) { st->max_state_abs = std::max(st->max_state_abs, worst); st->max_state = std::max(st->max_state, worst / 1e-10); }
+    }
+    if ((what & g_compare & CMP_VALUES) && !skip_measure)
+      for (int k = 0; k < m.n_ops; ++k) {
+        const double bar = 1e-10 * std::max(1.0, run.op_norm[size_t(k)]), d = std::fabs(fr.values[size_t(k)] - run.values[b][size_t(k)]);
+        if (!(d <= bar)) { std::snprintf(msg, sizeof msg, "bitstring %d: value of observable %d = %.15g, oracle %.15g (bar %g)", b, k, fr.values[size_t(k)], run.values[b][size_t(k)], bar); return msg; }
+        if (st) { st->max_value_abs = std::max(st->max_value_abs, d); st->max_value = std::max(st->max_value, d / bar); }
+      }
+  }
+  return "";
+}
+
+static std::string adjoint_disagreement(const Model& m, const Plan& plan, const CaseRun& run, EmuStats* st, ArgsTweak tweak = nullptr) {
+  Stopwatch sw(&g_adjoint_seconds);
+  emu::Emulation e;
+  emu::emu_prepare(m, plan, run.params, &e);
+  if (!e.err.empty()) return "prepare: " + e.err;
+  if (tweak) tweak(&e.args);
+  char msg[256];
+  for (size_t s = 0; s < plan.slot_gate.size(); ++s) {
+    const int g = plan.slot_gate[s];
+    if (g < 0 || size_t(g) >= m.gates.size() || m.gates[size_t(g)].param_idx < 0 || m.frozen(m.gates[size_t(g)].param_idx)) return "a slot of a frozen or constant gate";
+  }
+  for (int b = 0; b < 2; ++b) {
+    emu::AdjointResult ar;
+    if (!emu::emu_adjoint(&e, run.basis[b], run.psi[b], run.lam[b], &ar)) return "adjoint: " + e.err;
+    if (st) ++st->runs;
+    for (int p = 0; p < m.n_params && (g_compare & CMP_GRAD); ++p) {
+      if (m.frozen(p)) {
+        if (ar.grad[size_t(p)] != 0.0) { std::snprintf(msg, sizeof msg, "bitstring %d: frozen parameter %d has gradient %g", b, p, ar.grad[size_t(p)]); return msg; }
+        continue;
+      }
+      const double d = std::fabs(ar.grad[size_t(p)] - run.grad[b][size_t(p)]), bar = ar.bar[size_t(p)];
+      if (!(d <= bar)) { std::snprintf(msg, sizeof msg, "bitstring %d: d/d param %d = %.15g, oracle %.15g (off %g, bar %g)", b, p, ar.grad[size_t(p)], run.grad[b][size_t(p)], d, bar); return msg; }
+      if (st) { st->max_grad_abs = std::max(st->max_grad_abs, d); st->max_grad = std::max(st->max_grad, d / bar); }
+    }
+  }
+  return "";
+}
+
+static void count_features(EmuStats* st, uint32_t f) {
+  ++st->plans;
+  for (int i = 0; i < F_COUNT; ++i) st->feat[i] += (f >> i) & 1u;
+}
+
+struct OptionSet {
+  int tile = 0, full_threshold = 60, wide = -1, meas_tile = 0;
+  bool relabel = false, wave_bits = true;
+};
+static OptionSet draw_options(std::mt19937_64& rng, int os, int n_eff) {
+  auto U = [&](int lo, int hi) { return int(std::uniform_int_distribution<int>(lo, hi)(rng)); };
+  OptionSet o;  // (the draws of fuzz_one, in its order)
+  o.tile = os == 0 ? 0 : std::min(n_eff, U(kMinTileBits, kMaxTileBits - 1));
+  o.relabel = U(0, 1);
+  o.wave_bits = U(0, 3) != 0;
+  o.full_threshold = (const int[]){0, 60, 60, 100000}[U(0, 3)];
+  o.wide = U(-1, 1);
+  o.meas_tile = U(0, 3) == 0 ? std::min(n_eff, U(kMinTileBits, kMaxTileBits)) : 0;
+  return o;
+}
+
+static bool plan_forward(const Model& m, const OptionSet& o, Plan* plan) {
+  std::string err;
+  const bool ok = build_plan(m, o.tile, kRoundBits, false, plan, &err, o.full_threshold, o.meas_tile, o.wave_bits, false, o.wide, nullptr);
+  CHECK(ok, "build_plan: %s", err.c_str());
+  return ok;
+}
+static bool plan_adjoint(const Model& m, const OptionSet& o, Plan* plan, const std::vector<uint32_t>* forced = nullptr) {
+  std::string err;
+  const bool ok = build_plan(m, std::min(o.tile, 13), kRoundBits, true, plan, &err, o.full_threshold, 0, o.wave_bits, o.relabel, forced ? -1 : o.wide, forced);
+  if (!forced) CHECK(ok, "build_plan: %s", err.c_str());  // (engine.cpp build_plans skips a candidate order that does not plan)
+  return ok;
+}
+
+// qubit count of an emulated case: multi-pass plans (n above the tile size) dominate, a state is at most 2^n_cap
+static int draw_n(std::mt19937_64& rng, int n_cap) {
+  const int r = int(rng() % 100);
+  int n;
+  if (r < 10) n = 3 + int(rng() % 7);       // padded
+  else if (r < 12) n = 10;
+  else if (r < 18) n = 11;
+  else if (r < 43) n = 12;
+  else if (r < 77) n = 13;
+  else if (r < 95) n = 14;
+  else if (r < 98) n = 15;                  // (the states of 2^15 and 2^16 amplitudes take most of the time per case)
+  else n = 16;
+  return std::min(n, std::max(n_cap, 3));
+}
+
+struct EmuCase {
+  Case c;
+  CaseRun run;
+  int n = 0;
+  bool no_lean = false;
+  bool wide_term = false;
+  // what was emulated, per option set (for --dump-cases)
+  OptionSet o[3];
+  uint32_t feat[3] = {0, 0, 0};
+  int mask_os = -1, forced_os = -1;
+  std::vector<char> frozen;
+};
+static EmuCase draw_emu_case(std::mt19937_64& rng, int n_cap, int index) {
+  EmuCase ec;
+  ec.n = draw_n(rng, n_cap);
+  ec.c = random_case(rng, ec.n);
+  // Steering: random X-masks flip about half the qubits, and a term reaches Plan::global_terms only if its mask does not
+  // fit the measurement tile.  Every sixth case gets one term that flips every qubit (and small measurement tiles below).
+  ec.wide_term = index % 6 == 1 && ec.n > kMinTileBits;
+  if (ec.wide_term) {
+    ec.c.coeffs.push_back(0.5f);
+    ec.c.xs.push_back((1ull << ec.n) - 1ull);
+    ec.c.zs.push_back(rng() & ((1ull << ec.n) - 1ull));
+    ++ec.c.term_offsets.back();
+  }
+  fill_terms(&ec.c);
+  const auto t0 = std::chrono::steady_clock::now();
+  ec.run = make_run(rng, ec.c.m);
+  g_oracle_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return ec;
+}
+
+// Everything that is emulated for one case; `feat_seen`: union of the features of its plans (for --dump-cases).
+static void emulate_case(std::mt19937_64& rng, EmuCase& ec, int index, EmuStats* st) {
+  const Model& m = ec.c.m;
+  const int n_eff = std::max(ec.n, int(kMinTileBits));
+  // A third of the cases with the lean lowering off (schedule.cpp lower(): QHBM_NO_LEAN_CLIFFORD, the switch the GPU tests
+  // use): Y / dense 2x2 micro-ops, OP_GATE2, PASS_GENERAL and the general kernel variants exist only there.
+  ec.no_lean = index % 3 == 2;
+  struct LeanOff {
+    explicit LeanOff(bool off) { if (off) setenv("QHBM_NO_LEAN_CLIFFORD", "1", 1); else unsetenv("QHBM_NO_LEAN_CLIFFORD"); }
+    ~LeanOff() { unsetenv("QHBM_NO_LEAN_CLIFFORD"); }
+  } lean_off(ec.no_lean);
+  char ctx[192];
+  auto context = [&](const OptionSet& o, const char* kind) {
+    std::snprintf(ctx, sizeof ctx, "case %d n=%d gates=%zu lean=%d tile=%d relabel=%d wave=%d full=%d wide=%d meas=%d %s", index, ec.n, m.gates.size(), int(!ec.no_lean), o.tile,
+                  int(o.relabel), int(o.wave_bits), o.full_threshold, o.wide, o.meas_tile, kind);
+    g_context = ctx;
+  };
+  for (int os = 0; os < 3; ++os) {
+    OptionSet o = draw_options(rng, os, n_eff);
+    if (ec.wide_term && os > 0) o.meas_tile = std::min(n_eff, kMinTileBits + int(rng() % 3));
+    ec.o[os] = o;
+    uint32_t* feat_seen = &ec.feat[os];
+    {
+      context(o, "forward");
+      Plan plan;
+      if (plan_forward(m, o, &plan)) {
+        check_plan(m, plan);
+        const uint32_t f = plan_features(m, plan);
+        count_features(st, f);
+        *feat_seen |= f;
+        const std::string d = forward_disagreement(m, plan, ec.run, false, CMP_ALL, st);
+        CHECK(d.empty(), "%s", d.c_str());
+        if (d.empty() && (os == 0 || (rng() & 3) == 0)) {  // ... and as the engine runs it when the values come from lambda = O psi
+          const std::string d2 = forward_disagreement(m, plan, ec.run, true, CMP_STATE, st);
+          CHECK(d2.empty(), "measurements skipped: %s", d2.c_str());
+        }
+      }
+    }
+    {
+      context(o, "adjoint");
+      Plan plan;
+      if (plan_adjoint(m, o, &plan)) {
+        check_plan(m, plan);
+        const uint32_t f = plan_features(m, plan);
+        count_features(st, f);
+        *feat_seen |= f;
+        const std::string d = adjoint_disagreement(m, plan, ec.run, st);
+        CHECK(d.empty(), "%s", d.c_str());
+        // The plan rebuilt from EVERY entry of its candidate pass orders, as engine.cpp build_plans does: the searched
+        // orders by rank, the greedy order last -- the engine may keep any of them.  On three cases in four: each entry is a
+        // whole sweep more on both bitstrings.
+        const bool forced = os == index % 3 && index % 4 != 3;
+        if (forced) ec.forced_os = os;
+        if (forced) {
+          const std::vector<std::vector<uint32_t>> orders = plan.candidate_orders;
+          for (size_t rank = 0; rank < orders.size(); ++rank) {
+            Plan alt;
+            context(o, "adjoint, forced order");
+            if (!plan_adjoint(m, o, &alt, &orders[rank])) { ++st->forced_unplanned; continue; }  // (build_plans skips it too)
+            ++st->forced_rank[std::min<size_t>(rank, 7)];
+            st->forced_greedy += rank + 1 == orders.size();
+            check_plan(m, alt);
+            const uint32_t fa = plan_features(m, alt) | (1u << F_FORCED_ORDER);
+            count_features(st, fa);
+            *feat_seen |= fa;
+            const std::string da = adjoint_disagreement(m, alt, ec.run, st);
+            CHECK(da.empty(), "entry %zu of %zu: %s", rank, orders.size(), da.c_str());
+          }
+        }
+      }
+    }
+    if (os == (index + 1) % 3 && index % 4 != 1 && m.n_params > 0) {  // (three cases in four) a gradient mask, the sweep stopping at the first live gate or not
+      Model mm = m;
+      mm.param_frozen.assign(size_t(m.n_params), 0);
+      const int lead = int(rng() % 3);  // 0: random mask; 1, 2: the parameters of the leading gates frozen (dense_tail plans)
+      for (int p = 0; p < m.n_params; ++p) mm.param_frozen[size_t(p)] = char((rng() & 3) == 0);
+      if (lead) {
+        const size_t upto = m.gates.size() * size_t(lead) / 3;
+        for (size_t g = 0; g < upto; ++g)
+          if (m.gates[g].param_idx >= 0) mm.param_frozen[size_t(m.gates[g].param_idx)] = 1;
+      }
+      ec.mask_os = os;
+      ec.frozen = mm.param_frozen;
+      for (int stop = 0; stop < 2; ++stop) {
+        mm.stop_at_first_live_gate = stop != 0;
+        context(o, stop ? "adjoint, gradient mask, stops early" : "adjoint, gradient mask, whole sweep");
+        Plan plan;
+        if (!plan_adjoint(mm, o, &plan)) continue;
+        check_plan(mm, plan);
+        const uint32_t f = plan_features(mm, plan) | (1u << F_GRAD_MASK);
+        count_features(st, f);
+        *feat_seen |= f;
+        const std::string d = adjoint_disagreement(mm, plan, ec.run, st);
+        CHECK(d.empty(), "%s", d.c_str());
+      }
+    }
+  }
+}
+
+static void print_emu_summary(const EmuStats& st, bool with_floors) {
+  std::printf("plan_emulate: %ld plans, %ld runs (%ld with measurements skipped)\n", st.plans, st.runs, st.skip_runs);
+  std::printf("plan_emulate: features");
+  for (int i = 0; i < F_COUNT; ++i) std::printf(" %s=%ld/%d", kFeatureNames[i], st.feat[i], with_floors ? kFeatureFloors[i] : 0);
+  std::printf("\nplan_emulate: forced orders by entry of candidate_orders");
+  for (int i = 0; i < 8; ++i) std::printf(" %d:%ld", i, st.forced_rank[i]);
+  std::printf(" last(greedy)=%ld/%d not-plannable=%ld", st.forced_greedy, with_floors ? kForcedGreedyFloor : 0, st.forced_unplanned);
+  std::printf("\nplan_emulate: largest error state %.3g (bar 1e-10) value %.3g (%.3g of its bar) gradient %.3g (%.3g of its bar)\n",
+              st.max_state_abs, st.max_value_abs, st.max_value, st.max_grad_abs, st.max_grad);
+}
+
+static int emulate_main(int cases, uint64_t seed, int n_cap) {
+  std::mt19937_64 rng(seed);
+  EmuStats st;
+  int by_n[40] = {0};
+  for (int i = 0; i < cases; ++i) {
+    EmuCase ec = draw_emu_case(rng, n_cap, i);
+    ++by_n[ec.n];
+    emulate_case(rng, ec, i, &st);
+    if (g_failures > 50) break;
+  }
+  std::printf("plan_emulate: %d cases (seed %llu), qubit counts", cases, (unsigned long long)seed);
+  for (int n = 3; n <= 16; ++n) std::printf(" %d:%d", n, by_n[n]);
+  std::printf("\n");
+  print_emu_summary(st, true);
+  std::printf("plan_emulate: seconds in the oracle %.1f, emulating forward plans %.1f, adjoint plans %.1f\n", g_oracle_seconds, g_forward_seconds, g_adjoint_seconds);
+  std::printf("plan_emulate: %d failures\n", g_failures);
+  return g_failures ? 1 : 0;
+}
+
+
+// ---- the emulation is checked: corruptions that the structural check_plan ACCEPTS (the gap this mode closes) and the
+// emulation must reject --------------------------------------------------------------------------------------------------
+struct InstanceRef { size_t pass; uint32_t regmask, rec; int K; };
+static std::vector<std::vector<InstanceRef>> rounds_of(const Plan& plan) {  // every round's instances, in order
+  std::vector<std::vector<InstanceRef>> out;
+  const RecordLayout L(plan.R, plan.adjoint);
+  for (size_t pi = 0; pi < plan.passes.size(); ++pi) {
+    const Pass& p = plan.passes[pi];
+    for (uint32_t w : p.round_words) {
+      const uint32_t n_inst = (p.prog[w] & ~kRoundNoBarrier) >> 8;
+      out.emplace_back();
+      for (uint32_t i = 0; i < n_inst; ++i) out.back().push_back(InstanceRef{pi, p.prog[w + 1], p.prog[w + 2] + i * uint32_t(L.words()), p.K});
+    }
+  }
+  return out;
+}
+
+// index of the first measurement op of a pass's program and of its OP_END (prog.size() if none)
+static size_t find_op(const Pass& p, uint32_t want) {
+  size_t pc = 0;
+  while (pc < p.prog.size()) {
+    const uint32_t w0 = p.prog[pc], opc = w0 & 0xffu;
+    if (opc == want) return pc;
+    if (opc == OP_END) break;
+    if (opc == OP_ROUND) pc += kRoundWords;
+    else if (opc == OP_GATE2) pc += kGate2Words;
+    else if (opc == OP_MEASURE_WHT) pc += size_t(kWhtHeaderWords) + size_t(w0 >> 8) * kMeasTermWords;
+    else if (opc == OP_MEASURE) { ++pc; for (uint32_t g = 0; g < (w0 >> 8); ++g) pc += 2 + size_t(p.prog[pc + 1]) * kMeasTermWords; }
+    else break;
+  }
+  return p.prog.size();
+}
+
+static int self_test_emulation() {
+  // 14 qubits, tiles of 2^10: three layers of X**a Z**b and a CZ chain, every gate a parameter of its own class; a few
+  // flipping terms, and 40 diagonal strings (the Walsh-Hadamard measurement)
+  std::mt19937_64 rng(11);
+  const int n = 14;
+  Model m;
+  m.n = n;
+  m.n_params = 23;
+  int gi = 0;
+  for (int l = 0; l < 3; ++l) {
+    for (int q = 0; q < n; ++q) {
+      m.gates.push_back(Gate{QHBM_GATE_XPOW, q, -1, (gi++) % 23, 1.f, 0.125f, 0.f});
+      m.gates.push_back(Gate{QHBM_GATE_ZPOW, q, -1, (gi++) % 23, 0.75f, 0.f, 0.f});
+    }
+    for (int q = 0; q + 1 < n; ++q) m.gates.push_back(Gate{QHBM_GATE_CZPOW, q, q + 1, (gi++) % 23, 1.f, 0.f, 0.f});
+  }
+  m.n_ops = 2;
+  m.terms.push_back(PauliTerm{0.7f, 1u, 2u, 0, 0});
+  m.terms.push_back(PauliTerm{-0.4f, 0u, 3u, 0, 0});
+  m.terms.push_back(PauliTerm{0.3f, 3u << 5, 1u << 7, 0, 0});
+  m.terms.push_back(PauliTerm{0.9f, 1u << 13, (1u << 13) | (1u << 12), 1, 0});
+  m.terms.push_back(PauliTerm{0.6f, 1u << 2, 1u << 9, 0, 0});  // (flips a bit every tile holds, Z on a bit the last pass acts on)
+  for (int t = 0; t < 40; ++t) m.terms.push_back(PauliTerm{0.1f + 0.01f * float(t), 0u, uint32_t(rng() & ((1u << n) - 1u)) | 1u, 0, 1});
+  const CaseRun run = make_run(rng, m);
+  std::string err;
+  Plan fwd, adj, rel;
+  if (!build_plan(m, 10, kRoundBits, false, &fwd, &err) || !build_plan(m, 10, kRoundBits, true, &adj, &err) ||
+      !build_plan(m, 10, kRoundBits, true, &rel, &err, 60, 0, true, true)) {
+    std::fprintf(stderr, "self test: %s\n", err.c_str());
+    return 1;
+  }
+  int missed = 0, listed = 0;
+  g_context = "self test (emulation)";
+  auto accepted = [&](const Model& mm, const Plan& q) {
+    const int before = g_failures;
+    g_failures = 1000;  // (silences the messages)
+    check_plan(mm, q);
+    const bool ok = g_failures == 1000;
+    g_failures = before;
+    return ok;
+  };
+  auto verdict = [&](const char* what, const Model& mm, const CaseRun& r, const Plan& q, ArgsTweak tweak = nullptr) {
+    const bool ok_struct = accepted(mm, q);
+    const std::string d = q.adjoint ? adjoint_disagreement(mm, q, r, nullptr, tweak) : forward_disagreement(mm, q, r, false, CMP_ALL, nullptr, tweak);
+    ++listed;
+    std::printf("self test: %-58s %s by check_plan, %s by emulation%s%s\n", what, ok_struct ? "accepted" : "REJECTED", d.empty() ? "ACCEPTED" : "rejected",
+                d.empty() ? "" : ": ", d.substr(0, 90).c_str());
+    if (!ok_struct || d.empty()) ++missed;
+  };
+  auto not_found = [&](const char* what) { std::printf("self test: %-58s NO SITE for this corruption in the self-test plans\n", what); ++missed; };
+  // the valid plans agree with the oracle
+  for (const Plan* q : {&fwd, &adj, &rel}) {
+    const std::string d = q->adjoint ? adjoint_disagreement(m, *q, run, nullptr) : forward_disagreement(m, *q, run, false, CMP_ALL, nullptr);
+    if (!accepted(m, *q) || !d.empty()) { std::printf("self test: a valid plan fails: %s\n", d.c_str()); return 1; }
+  }
+  if (std::getenv("PLAN_FUZZ_DESCRIBE")) std::printf("%s\n%s\n", describe_plan(fwd).c_str(), describe_plan(rel).c_str());
+  if (fwd.passes.size() < 2 || adj.passes.size() < 2 || rel.passes.size() < 2) { std::printf("self test: single-pass plans\n"); return 1; }
+
+  // 1. two non-commuting instances of one round exchanged: a phase on a register bit, then an X on the same bit
+  {
+    const RecordLayout L(4, false);
+    bool done = false;
+    for (const auto& round : rounds_of(fwd)) {
+      for (size_t i = 0; i + 1 < round.size() && !done; ++i) {
+        const uint32_t a = round[i].rec, b = round[i + 1].rec;
+        const uint32_t ha = fwd.coef_init[a], hb = fwd.coef_init[b];
+        if (!((((ha >> 8) | (ha >> 4)) & 0xfu) & (hb & 0xfu))) continue;
+        Plan q = fwd;
+        for (int w = 0; w < L.words(); ++w) std::swap(q.coef_init[a + size_t(w)], q.coef_init[b + size_t(w)]);
+        for (CoefJob& j : q.jobs) {  // the coefficients travel with their records
+          if (uint32_t(j.out_off) >= a && uint32_t(j.out_off) < a + uint32_t(L.words())) j.out_off += int32_t(b - a);
+          else if (uint32_t(j.out_off) >= b && uint32_t(j.out_off) < b + uint32_t(L.words())) j.out_off -= int32_t(b - a);
+        }
+        verdict("1. two non-commuting instances of a round exchanged", m, run, q);
+        done = true;
+      }
+      if (done) break;
+    }
+    if (!done) not_found("1. two non-commuting instances of a round exchanged");
+  }
+  // 2. a CPH predicate on another free thread bit / another tile bit
+  for (int kind = 0; kind < 2; ++kind) {
+    const char* what = kind ? "2b. a tile-bit CPH predicate moved to another tile bit" : "2a. a CPH predicate moved to another free thread bit";
+    const RecordLayout L(4, false);
+    bool done = false;
+    for (const auto& round : rounds_of(fwd)) {
+      for (const InstanceRef& ir : round) {
+        for (int k = 0; k < 8 && !done; ++k) {
+          if (!(fwd.coef_init[ir.rec + 1] >> k & 1u)) continue;
+          const uint32_t pred = fwd.coef_init[ir.rec + size_t(L.pred(k))], pos = pred & 0xffu;
+          if (int(pred >> 8 != 0) != kind) continue;
+          Plan q = fwd;
+          uint32_t np = pos;
+          if (kind) np = pos + 1 < uint32_t(fwd.n_eff) ? pos + 1 : pos - 1;
+          else for (uint32_t c = 0; c < uint32_t(ir.K); ++c) if (c != pos && !(ir.regmask >> c & 1u)) { np = c; break; }
+          q.coef_init[ir.rec + size_t(L.pred(k))] = np | (pred & ~0xffu);
+          verdict(what, m, run, q);
+          done = true;
+        }
+        if (done) break;
+      }
+      if (done) break;
+    }
+    if (!done) not_found(what);
+  }
+  // 3a. one zl bit of a measurement term flipped
+  {
+    bool done = false;
+    for (size_t pi = 0; pi < fwd.passes.size() && !done; ++pi) {
+      const size_t pc = find_op(fwd.passes[pi], OP_MEASURE);
+      if (pc >= fwd.passes[pi].prog.size() || (fwd.passes[pi].prog[pc] >> 8) == 0 || fwd.passes[pi].prog[pc + 2] == 0) continue;
+      Plan q = fwd;
+      q.passes[pi].prog[pc + 3] ^= 1u << 2;
+      verdict("3a. one zl bit of a measurement term flipped", m, run, q);
+      done = true;
+    }
+    if (!done) not_found("3a. one zl bit of a measurement term flipped");
+  }
+  // 3b. a WHT term in another class, the class table kept consistent
+  {
+    bool done = false;
+    for (size_t pi = 0; pi < fwd.passes.size() && !done; ++pi) {
+      const Pass& p = fwd.passes[pi];
+      const size_t pc = find_op(p, OP_MEASURE_WHT);
+      if (pc >= p.prog.size()) continue;
+      const size_t nt = p.prog[pc] >> 8;
+      Plan q = fwd;
+      std::vector<std::array<uint32_t, 4>> terms(nt);
+      for (size_t t = 0; t < nt; ++t) for (int w = 0; w < 4; ++w) terms[t][size_t(w)] = p.prog[pc + kWhtHeaderWords + t * 4 + size_t(w)];
+      terms[0][0] ^= 1u << (p.K - 1);  // the top register bit of the first term's mask
+      std::stable_sort(terms.begin(), terms.end(), [&](const std::array<uint32_t, 4>& a, const std::array<uint32_t, 4>& b) { return (a[0] >> (p.K - 4)) < (b[0] >> (p.K - 4)); });
+      for (uint32_t c = 0; c < 16; ++c) {
+        uint32_t end = 0;
+        for (size_t t = 0; t < nt; ++t) end += (terms[t][0] >> (p.K - 4)) <= c;
+        q.passes[pi].prog[pc + 1 + c] = end;
+      }
+      for (size_t t = 0; t < nt; ++t) for (int w = 0; w < 4; ++w) q.passes[pi].prog[pc + kWhtHeaderWords + t * 4 + size_t(w)] = terms[t][size_t(w)];
+      verdict("3b. a WHT term moved to another class, table consistent", m, run, q);
+      done = true;
+    }
+    if (!done) not_found("3b. a WHT term moved to another class, table consistent");
+  }
+  // 3c. an X-mask group measured one pass earlier, across a gate on its bits
+  {
+    bool done = false;
+    for (size_t pi = 1; pi < fwd.passes.size() && !done; ++pi) {
+      const Pass& p = fwd.passes[pi];
+      const Pass& e = fwd.passes[pi - 1];
+      const size_t pc = find_op(p, OP_MEASURE);
+      if (pc >= p.prog.size() || e.is_measure_only) continue;
+      const uint32_t n_groups = p.prog[pc] >> 8;
+      size_t g_pc = pc + 1;
+      for (uint32_t g = 0; g < n_groups && !done; ++g) {
+        const uint32_t xl = p.prog[g_pc], nt = p.prog[g_pc + 1];
+        const size_t g_words = 2 + size_t(nt) * kMeasTermWords;
+        // the group's masks in index space, then in the earlier pass's split (forward plans: logical = physical bits)
+        auto to_index = [&](const Pass& ps, uint32_t local) { uint32_t v = 0; for (int i = 0; i < ps.K; ++i) if (local >> i & 1u) v |= 1u << ps.local_pos[size_t(i)]; return v; };
+        auto to_local = [&](const Pass& ps, uint32_t index) { uint32_t v = 0; for (int i = 0; i < ps.K; ++i) if (index >> ps.local_pos[size_t(i)] & 1u) v |= 1u << i; return v; };
+        uint32_t e_set = 0;
+        for (int b : e.local_pos) e_set |= 1u << b;
+        const uint32_t x = to_index(p, xl);
+        uint32_t z_all = 0;
+        for (uint32_t t = 0; t < nt; ++t) z_all |= to_index(p, p.prog[g_pc + 2 + t * 4]) | p.prog[g_pc + 2 + t * 4 + 1];
+        if ((x & ~e_set) == 0 && ((x | z_all) & p.mat_bits)) {
+          Plan q = fwd;
+          std::vector<uint32_t> grp;
+          grp.push_back(OP_MEASURE | (1u << 8));
+          grp.push_back(to_local(e, x));
+          grp.push_back(nt);
+          for (uint32_t t = 0; t < nt; ++t) {
+            const uint32_t z = to_index(p, p.prog[g_pc + 2 + t * 4]) | p.prog[g_pc + 2 + t * 4 + 1];
+            grp.push_back(to_local(e, z));
+            grp.push_back(z & ~e_set);
+            grp.push_back(p.prog[g_pc + 2 + t * 4 + 2]);
+            grp.push_back(p.prog[g_pc + 2 + t * 4 + 3]);
+          }
+          std::vector<uint32_t>& pp = q.passes[pi].prog;
+          pp.erase(pp.begin() + long(g_pc), pp.begin() + long(g_pc + g_words));
+          pp[pc] = OP_MEASURE | ((n_groups - 1) << 8);
+          std::vector<uint32_t>& ep = q.passes[pi - 1].prog;
+          ep.insert(ep.begin() + long(find_op(e, OP_END)), grp.begin(), grp.end());
+          verdict("3c. an X-mask group measured one pass earlier, across a gate", m, run, q);
+          done = true;
+        }
+        g_pc += g_words;
+      }
+    }
+    if (!done) not_found("3c. an X-mask group measured one pass earlier, across a gate");
+  }
+  // 4a. two gradient slots of one pass exchanged between two gates
+  {
+    const RecordLayout L(4, true);
+    bool done = false;
+    for (const auto& round : rounds_of(adj)) {
+      for (const InstanceRef& ir : round) {
+        std::vector<size_t> at;
+        for (int w = 0; w < 32; ++w) if (adj.coef_init[ir.rec + size_t(L.slot0()) + size_t(w)] != 0xffffffffu) at.push_back(ir.rec + size_t(L.slot0()) + size_t(w));
+        for (size_t i = 0; i < at.size() && !done; ++i)
+          for (size_t j = i + 1; j < at.size() && !done; ++j) {
+            const int base = adj.passes[ir.pass].slot_base;
+            const int ga = adj.slot_gate[size_t(base) + adj.coef_init[at[i]]], gb = adj.slot_gate[size_t(base) + adj.coef_init[at[j]]];
+            if (m.gates[size_t(ga)].param_idx == m.gates[size_t(gb)].param_idx) continue;
+            Plan q = adj;
+            std::swap(q.coef_init[at[i]], q.coef_init[at[j]]);
+            verdict("4a. two gradient slots exchanged between two gates", m, run, q);
+            done = true;
+          }
+        if (done) break;
+      }
+      if (done) break;
+    }
+    if (!done) not_found("4a. two gradient slots exchanged between two gates");
+  }
+  { Plan q = adj; q.slot_factor[q.slot_factor.size() / 2] = -q.slot_factor[q.slot_factor.size() / 2]; verdict("4b. one slot_factor negated", m, run, q); }
+  // 5. relabeling plans
+  {
+    bool done_tab = false, done_fz = false;
+    for (size_t pi = 0; pi < rel.passes.size(); ++pi) {
+      if (!done_tab && (rel.passes[pi].flags & PASS_RELABEL) && rel.passes[pi].relabel_tab.size() >= 12) {
+        Plan q = rel;
+        std::swap(q.passes[pi].relabel_tab[2 * 2 + 1], q.passes[pi].relabel_tab[2 * 4 + 1]);  // the addresses of out-indices 2 and 4
+        verdict("5a. two entries of a relabel_tab exchanged", m, run, q);
+        done_tab = true;
+      }
+      if (!done_fz && rel.passes[pi].frozen_old_local) {
+        Plan q = rel;
+        q.passes[pi].frozen_old_local &= q.passes[pi].frozen_old_local - 1;
+        verdict("5b. one bit cleared in a frozen_old_local", m, run, q);
+        done_fz = true;
+      }
+    }
+    for (size_t pi = 0; pi < fwd.passes.size() && !done_fz; ++pi)  // (forward: the bits no earlier pass has written, PASS_NO_ZERO_FILL)
+      if (fwd.passes[pi].frozen_old_local) {
+        Plan q = fwd;
+        q.passes[pi].frozen_old_local &= q.passes[pi].frozen_old_local - 1;
+        verdict("5b. one bit cleared in a frozen_old_local", m, run, q);
+        done_fz = true;
+      }
+    if (!done_tab) not_found("5a. two entries of a relabel_tab exchanged");
+    if (!done_fz) not_found("5b. one bit cleared in a frozen_old_local");
+  }
+  // 6. one bit set in a pass's zero_mask that is not prunable (the masks are fill_args' output: corrupted after it)
+  {
+    size_t pass = fwd.passes.size();
+    for (size_t pi = 0; pi < fwd.passes.size(); ++pi) if (fwd.passes[pi].completes_circuit) pass = pi;
+    verdict("6. one bit set in a zero_mask that is not prunable", m, run, fwd, [pass](std::vector<PassArgs>* args) {
+      PassArgs& a = (*args)[pass];
+      for (uint32_t k = 0; k < a.n_nonlocal; ++k)
+        if (!(a.zero_mask >> a.nonlocal_pos[k] & 1u)) { a.zero_mask |= 1u << a.nonlocal_pos[k]; --a.n_free; break; }
+    });
+  }
+  // 7a. one CoefJob::dagger flipped
+  {
+    Plan q = adj;
+    for (CoefJob& j : q.jobs) if (j.mop == MOP_X && j.param_idx >= 0) { j.dagger ^= 1; break; }
+    verdict("7a. one CoefJob::dagger flipped", m, run, q);
+  }
+  // 7b. CoefJob::swap flipped on a CNOT (a dense 4 x 4: the lean lowering off)
+  {
+    Model m2;
+    m2.n = 12;
+    m2.n_params = 6;
+    for (int q = 0; q < 12; ++q) m2.gates.push_back(Gate{QHBM_GATE_XPOW, q, -1, q % 6, 1.f, 0.25f, 0.f});
+    for (int q = 0; q + 1 < 12; q += 2) m2.gates.push_back(Gate{QHBM_GATE_CNOTPOW, q, q + 1, q % 6, 0.5f, 0.5f, 0.f});
+    for (int q = 0; q < 12; ++q) m2.gates.push_back(Gate{QHBM_GATE_YPOW, q, -1, (q + 1) % 6, 1.f, 0.f, 0.f});
+    m2.n_ops = 1;
+    m2.terms.push_back(PauliTerm{1.f, 1u, 6u, 0, 0});
+    m2.terms.push_back(PauliTerm{0.5f, 0u, 5u << 8, 0, 0});
+    const CaseRun run2 = make_run(rng, m2);
+    setenv("QHBM_NO_LEAN_CLIFFORD", "1", 1);
+    Plan g;
+    const bool ok = build_plan(m2, 10, kRoundBits, false, &g, &err);
+    unsetenv("QHBM_NO_LEAN_CLIFFORD");
+    bool done = false;
+    if (ok && forward_disagreement(m2, g, run2, false, CMP_ALL, nullptr).empty())
+      for (CoefJob& j : g.jobs)
+        if (j.mop == MOP_MAT2 && j.op_kind == QHBM_GATE_CNOTPOW) {
+          j.swap ^= 1;
+          verdict("7b. CoefJob::swap flipped on a CNOT", m2, run2, g);
+          done = true;
+          break;
+        }
+    if (!done) not_found("7b. CoefJob::swap flipped on a CNOT");
+  }
+  // ---- what the emulation found in the product, pinned (each failed before its fix) ----
+  {
+    // (a) Y**t = S X**t S^dagger, the S folded into a neighbouring Z**t of the circuit: that gate's offset plus 1/2 is no
+    // float in general, and CoefJob::offset held the rounded sum (a phase off by up to 1e-7)
+    Model ma;
+    ma.n = 10;
+    ma.n_params = 2;
+    for (int q = 0; q < 10; ++q) {
+      ma.gates.push_back(Gate{QHBM_GATE_ZPOW, q, -1, 0, 1.f, -0.3f - 0.01f * float(q), 0.f});
+      ma.gates.push_back(Gate{QHBM_GATE_YPOW, q, -1, 1, 1.f, 0.1f, 0.f});
+      ma.gates.push_back(Gate{QHBM_GATE_ZPOW, q, -1, 0, 0.5f, 0.7f + 0.03f * float(q), 0.f});
+    }
+    ma.n_ops = 1;
+    ma.terms.push_back(PauliTerm{1.f, 1u, 2u, 0, 0});
+    const CaseRun ra = make_run(rng, ma);
+    // (b) a term that flips more qubits than a measurement tile holds, with five and six Y factors: the strided-gather
+    // kernel took the NUMBER of Y factors for its value modulo 4
+    Model mb;
+    mb.n = 11;
+    mb.n_params = 3;
+    for (int q = 0; q < 11; ++q) mb.gates.push_back(Gate{QHBM_GATE_XPOW, q, -1, q % 3, 1.f, 0.2f, 0.f});
+    for (int q = 0; q + 1 < 11; ++q) mb.gates.push_back(Gate{QHBM_GATE_CZPOW, q, q + 1, q % 3, 1.f, 0.f, 0.f});
+    for (int q = 0; q < 11; ++q) mb.gates.push_back(Gate{QHBM_GATE_YPOW, q, -1, (q + 1) % 3, 0.5f, 0.f, 0.f});
+    mb.n_ops = 2;
+    mb.terms.push_back(PauliTerm{1.f, 0x7ffu, 0x1fu, 5, 0});
+    mb.terms.push_back(PauliTerm{1.f, 0x7ffu, 0x3fu << 3, 6, 1});
+    const CaseRun rb = make_run(rng, mb);
+    Plan pa, pb;
+    if (!build_plan(ma, 10, kRoundBits, false, &pa, &err) || !build_plan(mb, 10, kRoundBits, false, &pb, &err, 60, 10)) { std::printf("self test: %s\n", err.c_str()); return 1; }
+    const std::string da = forward_disagreement(ma, pa, ra, false, CMP_ALL, nullptr), db = forward_disagreement(mb, pb, rb, false, CMP_ALL, nullptr);
+    std::printf("self test: folded lowering constant next to an offset that is no float plus 1/2: %s\n", da.empty() ? "agrees" : da.c_str());
+    std::printf("self test: strided-gather terms with five and six Y factors (%zu global terms): %s\n", pb.global_terms.size(), db.empty() ? "agrees" : db.c_str());
+    if (!da.empty() || !db.empty() || pb.global_terms.size() != 2) ++missed;
+  }
+  // ---- the oracle: its adjoint gradient against central differences of its own values, all twelve kinds ----
+  {
+    Model mo;
+    mo.n = 5;
+    mo.n_params = 12;
+    for (int k = 0; k < QHBM_GATE_KIND_COUNT; ++k)
+      mo.gates.push_back(Gate{k, k % 5, k >= QHBM_GATE_CZPOW ? (k + 2) % 5 : -1, k, 0.5f + 0.125f * float(k), 0.25f, k % 3 ? 0.f : -0.5f});
+    for (int k = 0; k < QHBM_GATE_KIND_COUNT; ++k) mo.gates.push_back(Gate{(k * 5 + 1) % 12, (k + 1) % 5, (k * 5 + 1) % 12 >= QHBM_GATE_CZPOW ? (k + 3) % 5 : -1, (k + 4) % 12, 1.f, 0.f, 0.f});
+    mo.n_ops = 2;
+    mo.terms.push_back(PauliTerm{0.8f, 5u, 6u, 1, 0});
+    mo.terms.push_back(PauliTerm{-0.6f, 0u, 9u, 0, 0});
+    mo.terms.push_back(PauliTerm{0.5f, 24u, 24u, 2, 1});
+    mo.terms.push_back(PauliTerm{0.3f, 2u, 1u, 0, 1});
+    std::vector<double> prm, up = {0.7, -1.3};
+    for (int p = 0; p < 12; ++p) prm.push_back(0.1 + 0.17 * p);
+    const std::vector<double> g = emu::oracle_gradient(mo, prm, 19u, up);
+    double worst = 0.0;
+    for (int p = 0; p < 12; ++p) {
+      const double hstep = 1e-5;
+      double f[2];
+      for (int s = 0; s < 2; ++s) {
+        std::vector<double> q = prm;
+        q[size_t(p)] += s ? hstep : -hstep;
+        const std::vector<double> v = emu::oracle_values(mo, emu::oracle_state(mo, q, 19u));
+        f[s] = up[0] * v[0] + up[1] * v[1];
+      }
+      const double fd = (f[1] - f[0]) / (2.0 * hstep), d = std::fabs(fd - g[size_t(p)]);
+      worst = std::max(worst, d / std::max(1.0, std::fabs(g[size_t(p)])));
+      if (!(d <= 1e-8 * std::max(1.0, std::fabs(g[size_t(p)])))) { std::printf("self test: oracle gradient of parameter %d: adjoint %.12g, central difference %.12g\n", p, g[size_t(p)], fd); ++missed; }
+    }
+    // closed form (tests/test_oracle_kat.py): <Z> of X**p on |0> is cos(pi p), on |1> -cos(pi p); d/dp = -+ pi sin(pi p)
+    Model mx;
+    mx.n = 1;
+    mx.n_params = 1;
+    mx.gates.push_back(Gate{QHBM_GATE_XPOW, 0, -1, 0, 1.f, 0.f, 0.f});
+    mx.n_ops = 1;
+    mx.terms.push_back(PauliTerm{1.f, 0u, 1u, 0, 0});
+    for (double pw : {0.0, 0.3, 1.0, -2.7}) {
+      for (uint32_t b = 0; b < 2; ++b) {
+        const double want = (b ? -1.0 : 1.0) * std::cos(3.14159265358979323846 * pw);
+        const double got = emu::oracle_values(mx, emu::oracle_state(mx, {pw}, b))[0];
+        const double gg = emu::oracle_gradient(mx, {pw}, b, {1.0})[0], gw = (b ? 1.0 : -1.0) * 3.14159265358979323846 * std::sin(3.14159265358979323846 * pw);
+        if (!(std::fabs(got - want) <= 1e-14) || !(std::fabs(gg - gw) <= 1e-13)) { std::printf("self test: oracle X**%g on |%u>: %.17g (want %.17g), gradient %.17g (want %.17g)\n", pw, b, got, want, gg, gw); ++missed; }
+      }
+    }
+    std::printf("self test: oracle gradient against central differences (step 1e-5, twelve kinds): largest error %.3g of its bar 1e-8\n", worst / 1e-8);
+  }
+  std::printf("self test: %d corruptions listed, %d problems\n", listed, missed);
+  return missed;
+}
+
+
+// ---- --dump-cases: a sample of the emulated cases as plain data, for the same checks on the real engine ------------------
+// (tests/test_plan_fuzz_cases_gpu.py; tests/test_sanitize_cpu.py regenerates the committed file and compares bytes)
+static uint64_t to_qubit_mask(uint64_t index_mask, int n) {  // index bit b <-> qubit n - 1 - b
+  uint64_t q = 0;
+  for (int b = 0; b < n; ++b) if (index_mask >> b & 1ull) q |= 1ull << (n - 1 - b);
+  return q;
+}
+struct DumpEntry { EmuCase ec; int os; int index; };
+static void write_entry(std::FILE* f, const DumpEntry& d, bool last) {
+  const EmuCase& ec = d.ec;
+  const Model& m = ec.c.m;
+  const OptionSet& o = ec.o[d.os];
+  const uint32_t feat = ec.feat[d.os];
+  const bool masked = ec.mask_os == d.os;
+  std::fprintf(f, "  {\"case\": %d, \"option_set\": %d, \"n\": %d, \"n_params\": %d, \"lean_lowering\": %d,\n   \"features\": [", d.index, d.os, m.n, m.n_params, int(!ec.no_lean));
+  bool first = true;
+  for (int i = 0; i < F_COUNT; ++i) if (feat >> i & 1u) { std::fprintf(f, "%s\"%s\"", first ? "" : ", ", kFeatureNames[i]); first = false; }
+  std::fprintf(f, "],\n   \"options\": {\"tile_qubits\": %d, \"adjoint_tile_qubits\": %d, \"adjoint_relabel\": %d, \"cph_wave_bits\": %d, \"full_diag_threshold\": %d, "
+               "\"adjoint_full_diag_threshold\": %d, \"wide_last_pass\": %d, \"measure_tile_qubits\": %d, \"adjoint_plan_search\": %d, \"adjoint_stop_early\": %d},\n",
+               o.tile, std::min(o.tile, 13), int(o.relabel), int(o.wave_bits), o.full_threshold, o.full_threshold, o.wide, o.meas_tile, int(ec.forced_os == d.os),
+               masked ? d.index & 1 : -1);
+  std::fprintf(f, "   \"gradient_mask\": ");
+  if (masked) { std::fprintf(f, "["); for (int p = 0; p < m.n_params; ++p) std::fprintf(f, "%s%d", p ? ", " : "", int(!ec.frozen[size_t(p)])); std::fprintf(f, "],\n"); }
+  else std::fprintf(f, "null,\n");
+  std::fprintf(f, "   \"gates\": [");
+  for (size_t g = 0; g < m.gates.size(); ++g) {
+    const Gate& G = m.gates[g];
+    std::fprintf(f, "%s[%d, %d, %d, %d, %.9g, %.9g, %.9g]", g ? ", " : "", G.kind, G.q0, G.q1, G.param_idx, double(G.scalar), double(G.offset), double(G.global_shift));
+  }
+  std::fprintf(f, "],\n   \"observables\": [");
+  for (int op = 0; op < m.n_ops; ++op) {
+    std::fprintf(f, "%s[", op ? ", " : "");
+    bool ft = true;
+    for (const PauliTerm& t : m.terms) {
+      if (t.op != op) continue;
+      std::fprintf(f, "%s[%.9g, %llu, %llu]", ft ? "" : ", ", double(t.coeff), (unsigned long long)to_qubit_mask(t.x, m.n), (unsigned long long)to_qubit_mask(t.z, m.n));
+      ft = false;
+    }
+    std::fprintf(f, "]");
+  }
+  std::fprintf(f, "],\n   \"params\": [");
+  for (size_t p = 0; p < ec.run.params.size(); ++p) std::fprintf(f, "%s%.9g", p ? ", " : "", ec.run.params[p]);
+  std::fprintf(f, "],\n   \"upstream\": [");
+  for (size_t k = 0; k < ec.run.up.size(); ++k) std::fprintf(f, "%s%.9g", k ? ", " : "", ec.run.up[k]);
+  std::fprintf(f, "],\n   \"bitstrings\": [");
+  for (int b = 0; b < 2; ++b) {
+    std::fprintf(f, "%s[", b ? ", " : "");
+    for (int q = 0; q < m.n; ++q) std::fprintf(f, "%s%u", q ? ", " : "", (ec.run.basis[b] >> (m.n - 1 - q)) & 1u);
+    std::fprintf(f, "]");
+  }
+  // the dense C++ oracle's results (tests/test_sanitize_cpu.py compares the numpy oracle with them)
+  std::fprintf(f, "],\n   \"oracle_values\": [");
+  for (int b = 0; b < 2; ++b) {
+    std::fprintf(f, "%s[", b ? ", " : "");
+    for (size_t k = 0; k < ec.run.values[b].size(); ++k) std::fprintf(f, "%s%.17g", k ? ", " : "", ec.run.values[b][k]);
+    std::fprintf(f, "]");
+  }
+  std::fprintf(f, "],\n   \"oracle_gradients\": [");
+  for (int b = 0; b < 2; ++b) {
+    std::fprintf(f, "%s[", b ? ", " : "");
+    for (size_t p = 0; p < ec.run.grad[b].size(); ++p) std::fprintf(f, "%s%.17g", p ? ", " : "", ec.run.grad[b][p]);
+    std::fprintf(f, "]");
+  }
+  std::fprintf(f, "]}%s\n", last ? "" : ",");
+}
+
+static int dump_main(int count, uint64_t seed, const char* path) {
+  std::mt19937_64 rng(seed);
+  EmuStats st;
+  int need[F_COUNT];
+  for (int i = 0; i < F_COUNT; ++i) need[i] = 2;  // every floor category at least twice
+  std::vector<DumpEntry> picked;
+  int small = 0;
+  for (int i = 0; i < 400 && int(picked.size()) < count; ++i) {
+    EmuCase ec = draw_emu_case(rng, 16, i);
+    emulate_case(rng, ec, i, &st);
+    if (g_failures) break;
+    if (ec.c.m.gates.size() > 90) continue;  // (keeps the file small; the layered cases above that are the least varied)
+    bool all_met = true;
+    for (int k = 0; k < F_COUNT; ++k) all_met &= need[k] <= 0;
+    for (int os = 0; os < 3; ++os) {
+      const uint32_t f = ec.feat[os];
+      bool wanted = false;
+      for (int k = 0; k < F_COUNT; ++k) wanted |= (f >> k & 1u) && need[k] > 0 && (k == F_PADDED || ec.n >= kMinTileBits);
+      if (all_met) wanted = os == i % 3 && ec.n >= kMinTileBits;  // then whatever comes, at 10 qubits and above
+      if (!wanted || (ec.n < kMinTileBits && small >= count / 4)) continue;
+      for (int k = 0; k < F_COUNT; ++k) need[k] -= int(f >> k & 1u);
+      small += ec.n < kMinTileBits;
+      DumpEntry d{ec, os, i};
+      d.ec.run.psi[0].clear(); d.ec.run.psi[1].clear(); d.ec.run.lam[0].clear(); d.ec.run.lam[1].clear();
+      picked.push_back(std::move(d));
+      break;  // one option set per case
+    }
+  }
+  for (int k = 0; k < F_COUNT; ++k) CHECK(need[k] <= 0, "--dump-cases: feature %s appears %d times in the sample, not twice", kFeatureNames[k], 2 - need[k]);
+  CHECK(small * 4 <= int(picked.size()), "--dump-cases: %d of %zu cases below 10 qubits", small, picked.size());
+  if (g_failures) { std::printf("plan_fuzz: %d failures\n", g_failures); return 1; }
+  std::FILE* f = std::fopen(path, "w");
+  if (!f) { std::fprintf(stderr, "cannot write %s\n", path); return 1; }
+  std::fprintf(f, "{\"generator\": \"plan_fuzz --dump-cases %d %llu\",\n \"cases\": [\n", count, (unsigned long long)seed);
+  for (size_t i = 0; i < picked.size(); ++i) write_entry(f, picked[i], i + 1 == picked.size());
+  std::fprintf(f, " ]}\n");
+  std::fclose(f);
+  std::printf("plan_fuzz: wrote %zu cases to %s (%d below 10 qubits)\n", picked.size(), path, small);
+  return 0;
+}
+
 // The checker checks: corrupted copies of a valid plan must each be reported.
 static int self_test() {
   std::mt19937_64 rng(7);
@@ -436,6 +1350,20 @@ static int self_test() {
 
 int main(int argc, char** argv) {
   if (self_test()) { std::printf("plan_fuzz: self test FAILED\n"); return 2; }
+  if (argc > 2 && std::string(argv[1]) == "--self-test-without") {  // what only one comparison catches (by hand)
+    const std::string w(argv[2]);
+    if (w != "state" && w != "values" && w != "gradient") { std::fprintf(stderr, "--self-test-without state|values|gradient\n"); return 2; }
+    g_compare = CMP_ALL & ~(w == "state" ? CMP_STATE : w == "values" ? CMP_VALUES : CMP_GRAD);
+    self_test_emulation();
+    return 0;
+  }
+  if (argc > 4 && std::string(argv[1]) == "--dump-cases") return dump_main(std::atoi(argv[2]), std::strtoull(argv[3], nullptr, 10), argv[4]);
+  if (argc > 1 && std::string(argv[1]) == "--emulate") {
+    if (self_test_emulation()) { std::printf("plan_fuzz: self test of the emulation FAILED\n"); return 2; }
+    const int cases = argc > 2 ? std::atoi(argv[2]) : kEmulateCases;
+    const uint64_t seed = argc > 3 ? std::strtoull(argv[3], nullptr, 10) : 20261016ull;
+    return emulate_main(cases, seed, argc > 4 ? std::atoi(argv[4]) : 16);
+  }
   const int cases = argc > 1 ? std::atoi(argv[1]) : 2000;
   const uint64_t seed = argc > 2 ? std::strtoull(argv[2], nullptr, 10) : 20261003ull;
   const int n_max = argc > 3 ? std::atoi(argv[3]) : 28;

@@ -1237,3 +1237,44 @@ def test_many_diagonal_terms_measured_in_the_wide_last_pass_at_19_qubits(case):
   assert measuring and all("K=13" in line for line in measuring), measuring   # (the case the test is for)
   got = eng.expectation(bits, params).cpu().numpy()
   np.testing.assert_allclose(got, want, atol=5e-5 * max(1.0, _op_norm(ops).max()), rtol=0)
+
+
+@pytest.mark.parametrize("values_from_observable", [0, -1])
+def test_wide_terms_with_five_and_six_y_factors(values_from_observable):
+  """Terms that flip more qubits than a measurement tile holds are measured on the final state by the strided-gather
+  kernel (Plan::global_terms).  It took the NUMBER of Y factors of a term for the exponent of i^ny modulo 4: with five
+  or six of them the term came out with the wrong sign (found by the plan emulator, tests/sanitize/plan_fuzz.cpp
+  --emulate; the in-tile measurement and the lambda = O psi kernels always reduced the count).  Eleven qubits, tiles and
+  measurement tiles of 2^10, one term with five and one with six Y factors that flip every qubit; with the values taken
+  in the passes (0) and wherever the engine takes them by default (-1)."""
+  n, P = 11, 3
+  gates = [(E.GATE_XPOW, q, -1, q % 3, 1.0, 0.2) for q in range(n)]
+  gates += [(E.GATE_CZPOW, q, q + 1, q % 3, 1.0, 0.0) for q in range(n - 1)]
+  gates += [(E.GATE_YPOW, q, -1, (q + 1) % 3, 0.5, 0.0) for q in range(n)]
+  every = (1 << n) - 1
+  ops = [[(1.0, every, 0b11111)], [(1.0, every, 0b111111 << 3)]]
+  rng = np.random.default_rng(71)   # (every value of these draws is at least 3e-3: 300 bars)
+  params = rng.uniform(-1, 1, P)
+  bits = _random_bits(rng, 4, n)
+  eng = _engine(n, gates, P, ops, tile_qubits=10, measure_tile_qubits=10, forward_values_from_observable=values_from_observable)
+  assert "global_terms=2" in eng.describe_schedule()   # (the case the test is for)
+  _, want = check_values(eng, n, gates, params, bits, ops, rel=1e-5)
+  assert np.abs(want).min() > 2e-3   # (a sign error is hundreds of bars wide)
+
+
+def test_statevector_carries_the_global_shift_of_an_identity_gate():
+  """Every gate is exp(i pi t global_shift) * G**t (include/qhbm_engine.h), the identity included: qhbm_statevector left
+  the phase of an I**t with a global_shift out of the exported state, which then differed from the oracle's by that
+  phase (found by tests/test_plan_fuzz_cases_gpu.py on a random case).  Values and gradients never see it."""
+  n, P = 4, 2
+  gates = [(E.GATE_XPOW, q, -1, q % P, 1.0, 0.3) for q in range(n)]
+  gates += [(E.GATE_I, 1, -1, 0, 0.75, 0.25, -0.5), (E.GATE_I, 2, -1, -1, 0.0, 0.6, -0.5), (E.GATE_ZPOW, 0, -1, 1, 1.0, 0.0, -0.5)]
+  ops = [O.xxz_chain_op(n)]
+  rng = np.random.default_rng(3)
+  params = rng.uniform(-1, 1, P)
+  bits = _random_bits(rng, 2, n)
+  eng = _engine(n, gates, P, ops)
+  sv = eng.statevector(bits, params).cpu().numpy()
+  for b in range(2):
+    np.testing.assert_allclose(sv[b], O.simulate(n, gates, params, list(bits[b])).ravel(), atol=3e-6)
+  check_values(eng, n, gates, params, bits, ops, rel=1e-5)
