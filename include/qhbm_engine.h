@@ -154,8 +154,9 @@ int qhbm_set_observables(qhbm_engine* h, int n_ops, const int32_t* term_offsets,
  * nothing, supplies the value when the plan has more than one pass and some term flips two or more qubits or
  * needs a measurement-only pass; 0 = measure in the passes; 1 = always),
  * "adjoint_relabel" (1 = adjoint plans move finished index bits out of the 128-byte lines when the finishing
- * pass stores its tiles), "forward_pairs" (1 = dense lean forward passes run on pairs of states with the
- * tiles in registers), "wide_last_pass" (-1 = the last forward gate pass may take a tile one or two bits
+ * pass stores its tiles), "x_two_shear" (1 = an X**t next to a full diagonal table whose angle is at most pi / 3
+ * runs as two shears, its scaling folded into the table; 0 = always three shears), "forward_pairs" (1 = dense
+ * lean forward passes run on pairs of states with the tiles in registers), "wide_last_pass" (-1 = the last forward gate pass may take a tile one or two bits
  * wider when that saves a pass, unless tile_qubits is set; 0 = never; 1 = always), "observable_xcd_states"
  * (lambda = O psi: 1 = one state per XCD at a time, 0 = every XCD an eighth of each state, -1 = by state size: states of
  * 64 MiB and more are shared), "observable_kernel" (lambda = O psi and <psi|O|psi>: 0 = one L2 gather per X-mask and

@@ -98,6 +98,7 @@ struct qhbm_engine {
   int opt_shift_prefix = 1;    // parameter shift: a shifted program starts at the pass that holds its gate, from the base program's state
   int opt_adj_relabel = 1;     // adjoint plans move finished index bits out of the 128-byte lines (schedule.h Pass)
   int opt_obs_xcd_states = -1; // lambda = O psi: one state per XCD at a time (1), every XCD an eighth of each state (0); -1: by state size
+  int opt_x_two_shear = 1;   // X**t in FULL instances as two shears, the scaling folded into the table (x_shear.h); 0: always three
   int opt_adj_exchange = 1;  // lean adjoint passes: register-resident tile pair + one LDS exchange buffer
   int retained_U = 0;  // final states of the last qhbm_expectation_retain still sit in psi
   bool retained_table = false;  // ... of a qhbm_table_expectation_retain (no lambda = O psi; only the table VJP takes them)
@@ -353,7 +354,7 @@ void qhbm::fill_args(const Plan& plan, const Model& m, std::vector<PassArgs>* ar
 
 namespace {
 
-double pass_flops_per_amplitude(const Plan& plan, const Pass& p);
+double pass_flops_per_amplitude(const Plan& plan, const Pass& p, const uint32_t* dyn = nullptr);
 
 // Modelled time of the adjoint sweep per state, in seconds: per pass the larger of its arithmetic at the rate the
 // pass kernel sustains (67 TFLOP/s of qhbm_flop_model's flops: 65-69 over 20...28 qubits, depths 16 and 32, tiles of
@@ -471,7 +472,13 @@ int upload_plan(qhbm_engine* h, DevicePlan* d) {
   fill_args(d->plan, h->model, &d->args, &prog, &tables);
   HIPCHK(d->prog.upload(prog));
   HIPCHK(d->tables.upload(tables));
-  HIPCHK(d->jobs.upload(d->plan.jobs));
+  if (h->opt_x_two_shear) {
+    HIPCHK(d->jobs.upload(d->plan.jobs));
+  } else {  // every X job keeps the three-shear form
+    std::vector<CoefJob> jobs = d->plan.jobs;
+    for (CoefJob& jb : jobs) jb.x_full = 0;
+    HIPCHK(d->jobs.upload(jobs));
+  }
   HIPCHK(d->rec_offsets.upload(d->plan.record_offsets));
   {
     std::vector<float> init(d->plan.coef_init.size() + 64, 0.f);
@@ -1416,6 +1423,7 @@ int qhbm_set_option(qhbm_engine* h, const char* name, int64_t value) {
   else if (k == "adjoint_full_diag_threshold") { h->opt_full_adj = int(value); h->plans_valid = false; }
   else if (k == "adjoint_tile_qubits") { h->opt_adj_tile = int(value); h->plans_valid = false; }
   else if (k == "adjoint_exchange") { h->opt_adj_exchange = int(value); h->plans_valid = false; }
+  else if (k == "x_two_shear") { h->opt_x_two_shear = value != 0; h->plans_valid = false; h->adj_cache.clear(); }
   else if (k == "adjoint_relabel") { h->opt_adj_relabel = int(value); h->plans_valid = false; }
   else if (k == "forward_pairs") h->opt_fwd_pair = int(value);
   else if (k == "shift_prefix_sharing") { h->opt_shift_prefix = int(value); h->shift_ready = false; }
@@ -2231,15 +2239,19 @@ namespace {
 // fp32 operations (FMA = 2) the gate arithmetic of one pass kernel executes per AMPLITUDE of a tile it
 // does not skip, from the plan's instance records -- the counts are those of the inline-asm sequences
 // in kernels.hip (v_pk_fma_f32 = 4, v_pk_mul_f32 / v_pk_add_f32 = 2 per amplitude pair of lanes):
-//   forward   X**t three shears 6 | PH1 3 (half the amplitudes x (mul + fma)) | PH2 1.5 | FULL table 5.625
+//   forward   X**t three shears 6, two shears 4 (x_shear.h; + 0.125 per instance that has one: entry 0 of its table)
+//             | PH1 3 (half the amplitudes x (mul + fma)) | PH2 1.5 | FULL table 5.625
 //             | boundary CPH 3 x (share of waves whose predicate is on) | Y 6 | dense 2x2 14 | dense 4x4 32
-//   adjoint   X 16 (psi 6 + lambda 6 + inner product 4) | PH1 8 | PH2 4 | FULL 15.75 (two tables 11.25 + the ten
+//   adjoint   X 16 (psi 6 + lambda 6 + inner product 4), two shears 12 (+ 0.25 per instance) | PH1 8 | PH2 4 | FULL 15.75 (two tables 11.25 + the ten
 //             partial sums as scalar differences, round 5: 15 x (mul + fma) + 27 adds = 4.5) | CPH 8 x share | Y 16 |
 //             dense 2x2 44 | dense 4x4 on (psi, lambda) + generator 96
 // Rounds whose waves are dead (OP_ROUND word 4) run on 2^-popc(dead mask) of the waves.  Wave
 // reductions, address arithmetic and record decoding are NOT counted: this is the arithmetic the gate
 // set requires of this kernel design, the numerator of a compute roofline against the fp32 vector peak.
-double pass_flops_per_amplitude(const Plan& plan, const Pass& p) {
+// Which X gates ran as two shears is decided per call on the device: `dyn` = the coefficient buffer as the last call
+// left it (qhbm_flop_model reads it back); without it every X counts as three shears, which is also what the plan
+// search compares (the choice depends on the parameters, a plan must not).
+double pass_flops_per_amplitude(const Plan& plan, const Pass& p, const uint32_t* dyn) {
   const RecordLayout L(plan.R, plan.adjoint);
   const bool adj = plan.adjoint;
   double total = 0.0;
@@ -2257,6 +2269,8 @@ double pass_flops_per_amplitude(const Plan& plan, const Pass& p) {
         const uint32_t h0 = rec[0], h1 = rec[1];
         const bool full = (h1 & kFullDiagFlag) != 0;
         f += (adj ? 16.0 : 6.0) * __builtin_popcount(h0 & 0xfu);
+        if (const uint32_t x2 = dyn && full ? dyn[first + size_t(i) * size_t(L.words()) + size_t(L.x2_mask())] & h0 & 0xfu : 0u)
+          f += (adj ? 0.25 : 0.125) - (adj ? 4.0 : 2.0) * __builtin_popcount(x2);
         if (full) f += adj ? 15.75 : 5.625;
         else f += (adj ? 8.0 : 3.0) * __builtin_popcount((h0 >> 8) & 0xfu) + (adj ? 4.0 : 1.5) * __builtin_popcount((h0 >> 16) & 0x3fu);
         for (int k = 0; k < 8; ++k) {
@@ -2431,6 +2445,18 @@ extern "C" int qhbm_flop_model(qhbm_engine* h, int U, int with_vjp, double* fwd_
   const double amps = double(size_t(1) << h->fwd.plan.n_eff) * double(U);
   double f = 0.0, o = 0.0, b = 0.0;
   const bool from_obs = with_vjp ? (value_mode(h) || multi_value_mode(h)) : forward_values_from_observable(h);  // no measurement in the sweep
+  // the coefficient buffers as the last call left them: which X gates ran as two shears (pass_flops_per_amplitude)
+  std::vector<uint32_t> dyn_f, dyn_b;
+  auto read_back = [&](const DevicePlan& d, std::vector<uint32_t>* out) -> hipError_t {
+    if (h->device < 0 || !d.uploaded || !h->opt_x_two_shear || d.coef.n < d.plan.coef_init.size()) return hipSuccess;
+    hipError_t e = hipSetDevice(h->device);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    out->resize(d.plan.coef_init.size());
+    if (e == hipSuccess && !out->empty()) e = hipMemcpy(out->data(), d.coef.p, out->size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    return e;
+  };
+  HIPCHK(read_back(h->fwd, &dyn_f));
+  if (with_vjp) HIPCHK(read_back(h->adj, &dyn_b));
   {
     std::vector<PassArgs> args;
     std::vector<uint32_t> prog, tables;
@@ -2450,7 +2476,7 @@ extern "C" int qhbm_flop_model(qhbm_engine* h, int U, int with_vjp, double* fwd_
           pc += opc == OP_ROUND ? size_t(kRoundWords) : size_t(kGate2Words);
         }
       }
-      f += share * amps * pass_flops_per_amplitude(h->fwd.plan, q);
+      f += share * amps * pass_flops_per_amplitude(h->fwd.plan, q, dyn_f.empty() ? nullptr : dyn_f.data());
     }
   }
   if (with_vjp || from_obs) {
@@ -2468,7 +2494,7 @@ extern "C" int qhbm_flop_model(qhbm_engine* h, int U, int with_vjp, double* fwd_
     fill_args(h->adj.plan, h->model, &args, &prog, &tables);
     for (size_t i = 0; i < args.size(); ++i) {
       const double live = 1.0 / double(1ull << __builtin_popcount(args[i].zero_mask));
-      b += live * amps * pass_flops_per_amplitude(h->adj.plan, h->adj.plan.passes[i]);
+      b += live * amps * pass_flops_per_amplitude(h->adj.plan, h->adj.plan.passes[i], dyn_b.empty() ? nullptr : dyn_b.data());
     }
   }
   if (fwd_flops) *fwd_flops = f;

@@ -27,6 +27,7 @@
 #include "device_common.h"
 #include "kernels.h"
 #include "program.h"
+#include "x_shear.h"
 
 namespace qhbm {
 
@@ -113,16 +114,19 @@ template <int N> using iseq = std::make_integer_sequence<int, N>;
 //   [[c, -is], [-is, c]] = [[1, u], [0, 1]] [[1, 0], [v, 1]] [[1, u], [0, 1]],  u = -i tan(theta/2), v = -i sin(theta),
 // each one in-place packed FMA per pair (-i w (x + i y) = (w y, -w x)): 1.5 packed ops per amplitude
 // instead of the 2 of the direct form, no temporaries, determinant exactly 1.  ts = (tan(theta/2),
-// sin(theta)) is a wave-uniform SGPR pair; U^dagger is the same with ts negated.  Four pairs per asm
-// statement: the compiler pads every inline-asm block with an s_nop (it cannot see the hazards
-// inside), so fewer, longer blocks issue fewer of them, and dependent FMAs sit four apart.
-__device__ __forceinline__ void x_pair4(v2f& a0, v2f& a1, v2f& b0, v2f& b1, v2f& c0, v2f& c1, v2f& d0, v2f& d1, v2f ts) {
+// sin(theta)) is a wave-uniform SGPR pair; U^dagger is the same with ts negated.
+// Or as TWO SHEARS (x_shear.h): the first two of the three with other coefficients -- forward
+// ts = (tan(theta), sin(theta) cos(theta)), adjoint (-sin cos, -tan) -- 1.0 packed op per amplitude; what is left,
+// diag(cos(theta), 1 / cos(theta)) on the register bit, is part of the instance's FULL table (combine_diag_kernel).
+// x2_pair4 = the two shears both forms begin with, x3_pair8 = the third shear of the three-shear form.
+// Four (eight) pairs per asm statement: the compiler pads every inline-asm block with an s_nop (it cannot see the
+// hazards inside), so fewer, longer blocks issue fewer of them, and dependent FMAs sit four apart.
+__device__ __forceinline__ void x2_pair4(v2f& a0, v2f& a1, v2f& b0, v2f& b1, v2f& c0, v2f& c1, v2f& d0, v2f& d1, v2f ts) {
 #define QHBM_SH_T(D_, S_) "v_pk_fma_f32 %[" #D_ "], %[" #S_ "], %[ts], %[" #D_ "] op_sel:[1,0,0] op_sel_hi:[0,0,1] neg_hi:[1,0,0]\n\t"
 #define QHBM_SH_S(D_, S_) "v_pk_fma_f32 %[" #D_ "], %[" #S_ "], %[ts], %[" #D_ "] op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_hi:[1,0,0]\n\t"
   asm(QHBM_SH_T(a0, a1) QHBM_SH_T(b0, b1) QHBM_SH_T(c0, c1) QHBM_SH_T(d0, d1)
-      QHBM_SH_S(a1, a0) QHBM_SH_S(b1, b0) QHBM_SH_S(c1, c0) QHBM_SH_S(d1, d0)
-      QHBM_SH_T(a0, a1) QHBM_SH_T(b0, b1) QHBM_SH_T(c0, c1)
-      "v_pk_fma_f32 %[d0], %[d1], %[ts], %[d0] op_sel:[1,0,0] op_sel_hi:[0,0,1] neg_hi:[1,0,0]"
+      QHBM_SH_S(a1, a0) QHBM_SH_S(b1, b0) QHBM_SH_S(c1, c0)
+      "v_pk_fma_f32 %[d1], %[d0], %[ts], %[d1] op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_hi:[1,0,0]"
       : [a0] "+v"(a0), [a1] "+v"(a1), [b0] "+v"(b0), [b1] "+v"(b1), [c0] "+v"(c0), [c1] "+v"(c1),
         [d0] "+v"(d0), [d1] "+v"(d1)
       : [ts] "s"(ts));
@@ -130,15 +134,41 @@ __device__ __forceinline__ void x_pair4(v2f& a0, v2f& a1, v2f& b0, v2f& b1, v2f&
 #undef QHBM_SH_S
 }
 template <int R, int RB, int... Q>
-__device__ __forceinline__ void apply_x_(v2f (&a)[1 << R], v2f cs, std::integer_sequence<int, Q...>) {
-  static_assert(R == 4, "x_pair4 covers the eight pairs of a 16-amplitude register file in two calls");
-  (x_pair4(a[ins0<RB>(4 * Q)], a[ins0<RB>(4 * Q) | (1 << RB)], a[ins0<RB>(4 * Q + 1)], a[ins0<RB>(4 * Q + 1) | (1 << RB)],
-           a[ins0<RB>(4 * Q + 2)], a[ins0<RB>(4 * Q + 2) | (1 << RB)], a[ins0<RB>(4 * Q + 3)],
-           a[ins0<RB>(4 * Q + 3) | (1 << RB)], cs), ...);
+__device__ __forceinline__ void apply_x2_(v2f (&a)[1 << R], v2f ts, std::integer_sequence<int, Q...>) {
+  static_assert(R == 4, "x2_pair4 covers the eight pairs of a 16-amplitude register file in two calls");
+  (x2_pair4(a[ins0<RB>(4 * Q)], a[ins0<RB>(4 * Q) | (1 << RB)], a[ins0<RB>(4 * Q + 1)], a[ins0<RB>(4 * Q + 1) | (1 << RB)],
+            a[ins0<RB>(4 * Q + 2)], a[ins0<RB>(4 * Q + 2) | (1 << RB)], a[ins0<RB>(4 * Q + 3)],
+            a[ins0<RB>(4 * Q + 3) | (1 << RB)], ts), ...);
 }
-// c*I - i*s*X  on register bit RB  (cs = (tan(theta/2), sin(theta)), see x_pair4)
 template <int R, int RB>
-__device__ __forceinline__ void apply_x(v2f (&a)[1 << R], v2f cs) { apply_x_<R, RB>(a, cs, iseq<(1 << (R - 3))>{}); }
+__device__ __forceinline__ void apply_x2(v2f (&a)[1 << R], v2f ts) { apply_x2_<R, RB>(a, ts, iseq<(1 << (R - 3))>{}); }
+// The third shear on all eight pairs: a0 += -i ts.x a1 (a0..h0 updated, a1..h1 read).
+__device__ __forceinline__ void x3_pair8(v2f& a0, v2f a1, v2f& b0, v2f b1, v2f& c0, v2f c1, v2f& d0, v2f d1, v2f& e0, v2f e1,
+                                         v2f& f0, v2f f1, v2f& g0, v2f g1, v2f& h0, v2f h1, v2f ts) {
+#define QHBM_SH_T(D_, S_) "v_pk_fma_f32 %[" #D_ "], %[" #S_ "], %[ts], %[" #D_ "] op_sel:[1,0,0] op_sel_hi:[0,0,1] neg_hi:[1,0,0]\n\t"
+  asm(QHBM_SH_T(a0, a1) QHBM_SH_T(b0, b1) QHBM_SH_T(c0, c1) QHBM_SH_T(d0, d1) QHBM_SH_T(e0, e1) QHBM_SH_T(f0, f1) QHBM_SH_T(g0, g1)
+      "v_pk_fma_f32 %[h0], %[h1], %[ts], %[h0] op_sel:[1,0,0] op_sel_hi:[0,0,1] neg_hi:[1,0,0]"
+      : [a0] "+v"(a0), [b0] "+v"(b0), [c0] "+v"(c0), [d0] "+v"(d0), [e0] "+v"(e0), [f0] "+v"(f0), [g0] "+v"(g0), [h0] "+v"(h0)
+      : [a1] "v"(a1), [b1] "v"(b1), [c1] "v"(c1), [d1] "v"(d1), [e1] "v"(e1), [f1] "v"(f1), [g1] "v"(g1), [h1] "v"(h1),
+        [ts] "s"(ts));
+#undef QHBM_SH_T
+}
+template <int R, int RB>
+__device__ __forceinline__ void apply_x3(v2f (&a)[1 << R], v2f ts) {
+  static_assert(R == 4, "the eight pairs of a 16-amplitude register file");
+  constexpr int B = 1 << RB;
+  x3_pair8(a[ins0<RB>(0)], a[ins0<RB>(0) | B], a[ins0<RB>(1)], a[ins0<RB>(1) | B], a[ins0<RB>(2)], a[ins0<RB>(2) | B],
+           a[ins0<RB>(3)], a[ins0<RB>(3) | B], a[ins0<RB>(4)], a[ins0<RB>(4) | B], a[ins0<RB>(5)], a[ins0<RB>(5) | B],
+           a[ins0<RB>(6)], a[ins0<RB>(6) | B], a[ins0<RB>(7)], a[ins0<RB>(7) | B], ts);
+}
+// X on register bit RB in the form its record says (x2: the record's two-shear mask).  Both forms start with the
+// same two shears on the slot's two floats, so the choice is ONE scalar branch around the third -- an if-then triangle
+// around in-place code like every other micro-op, not two code paths that meet (which costs merge copies of the file).
+template <int R, int RB>
+__device__ __forceinline__ void apply_x_form(v2f (&a)[1 << R], v2f ts, uint32_t x2) {
+  apply_x2<R, RB>(a, ts);
+  if (!((x2 >> RB) & 1u)) apply_x3<R, RB>(a, ts);
+}
 
 template <int R, int RB, int... P>
 __device__ __forceinline__ void apply_y_(v2f (&a)[1 << R], v2f cs, std::integer_sequence<int, P...>) {
@@ -184,7 +214,7 @@ __device__ __forceinline__ void apply_ph1_(v2f (&a)[1 << R], v2f cs, std::intege
 template <int R, int RB>
 __device__ __forceinline__ void apply_ph1(v2f (&a)[1 << R], v2f cs) { apply_ph1_<R, RB>(a, cs, iseq<(1 << (R - 1))>{}); }
 
-// a_k <- (c + i s) a_k for eight amplitudes in one asm statement (see x_pair4).
+// a_k <- (c + i s) a_k for eight amplitudes in one asm statement (see x2_pair4).
 __device__ __forceinline__ void phase_v8(v2f& a0, v2f& a1, v2f& a2, v2f& a3, v2f& a4, v2f& a5, v2f& a6, v2f& a7, v2f cs) {
   v2f t0, t1, t2, t3, t4, t5, t6, t7;
 #define QHBM_PH_MUL(K_) "v_pk_mul_f32 %[t" #K_ "], %[a" #K_ "], %[cs] op_sel_hi:[1,0]\n\t"
@@ -253,7 +283,7 @@ __device__ __forceinline__ void acc_re(v2f& acc, v2f l, v2f p) {
 }
 
 // sum over selected registers of Im(conj(lam) psi); two packed accumulators break the chain
-// Eight accumulations into two partial sums in one asm statement (see x_pair4).
+// Eight accumulations into two partial sums in one asm statement (see x2_pair4).
 // The same with the two partial sums STARTED here (products 0 and 1 are multiplies): no zeroed accumulators
 // (two v_mov_b64 per sum: 4.1 cycles each on gfx950, scripts/experiments/micro/valu_cycles.hip).
 __device__ __forceinline__ void acc_im8_first(v2f& a0, v2f& a1, v2f l0, v2f p0, v2f l1, v2f p1, v2f l2, v2f p2, v2f l3, v2f p3,
@@ -778,6 +808,12 @@ template <int NV>
 __device__ __forceinline__ void apply_full(v2f (&a)[16], const uint32_t (&rv)[NV], RecBase rb, bool conj) {
   apply_full_<NV>(a, rv, rb, conj, iseq<15>{});
 }
+// Table entry of register value 0: 1 unless the instance has two-shear X gates (x_shear.h), then the product of
+// their cosines -- one packed multiply per instance and register file, under the record's mask.
+__device__ __forceinline__ void scale_full0(v2f& a, float e0) {
+  const v2f e{e0, e0};
+  asm("v_pk_mul_f32 %[a], %[a], %[e]" : [a] "+v"(a) : [e] "s"(e));
+}
 // q[m] = (lam.re * psi.im, lam.im * psi.re): Im(conj(lam) psi) = q.x - q.y, subtracted once per SUM, not
 // per amplitude -- eight packed multiplies per asm statement (plain C++ here makes the SLP vectoriser
 // gather the scalars with 32 v_mov before it packs them).
@@ -889,7 +925,8 @@ __device__ __forceinline__ void instance_fwd(const uint32_t (&rv)[NV], const uin
   const uint32_t h0 = rec_word<0>(rv, rb), h1 = rec_word<1>(rv, rb);
   // One-qubit gates: a separate predicated slot class per kind (X, Y, dense), each a plain
   // if-then triangle around in-place code -- no merge copies.
-  QHBM_FOR_RB(R, if ((h0 >> J) & 1u) apply_x<R, J>(a, rec_cs<L.x(J)>(rv, rb));)
+  const uint32_t x2 = rb.p[L.x2_mask()];  // X gates in two-shear form (0 in instances without a FULL table)
+  QHBM_FOR_RB(R, if ((h0 >> J) & 1u) apply_x_form<R, J>(a, rec_cs<L.x(J)>(rv, rb), x2);)
   if constexpr (GEN) {
   if ((h1 >> 16) & 0xfu) {
     QHBM_FOR_RB(R, if ((h1 >> (16 + J)) & 1u) apply_y<R, J>(a, rec_cs<L.y(J)>(rv, rb));)
@@ -903,7 +940,10 @@ __device__ __forceinline__ void instance_fwd(const uint32_t (&rv)[NV], const uin
   }
   }
   // (a FULL instance has its PH1 / PH2 masks zeroed in word 0: independent triangles, no else)
-  if (h1 & kFullDiagFlag) apply_full<NV>(a, rv, rb, false);
+  if (h1 & kFullDiagFlag) {
+    if (x2) scale_full0(a[0], __uint_as_float(rb.p[L.full0()]));
+    apply_full<NV>(a, rv, rb, false);
+  }
   QHBM_FOR_RB(R, if ((h0 >> (8 + J)) & 1u) apply_ph1<R, J>(a, rec_cs<L.ph1(J)>(rv, rb));)
   if ((h0 >> 16) & 0x3fu) {
     QHBM_FOR_PAIR(R,
@@ -935,8 +975,23 @@ __device__ __forceinline__ void instance_fwd_pair(const uint32_t (&rv)[NV], cons
   constexpr RecordLayout L(R, false);
   const RecBase rb{recs + rec_off};
   const uint32_t h0 = rec_word<0>(rv, rb), h1 = rec_word<1>(rv, rb);
-  QHBM_FOR_RB(R, if ((h0 >> J) & 1u) { const v2f cs = rec_cs<L.x(J)>(rv, rb); apply_x<R, J>(a, cs); apply_x<R, J>(b, cs); })
-  if (h1 & kFullDiagFlag) { apply_full<NV>(a, rv, rb, false); apply_full<NV>(b, rv, rb, false); }
+  const uint32_t x2 = rb.p[L.x2_mask()];  // (see instance_fwd)
+  QHBM_FOR_RB(R,
+    if ((h0 >> J) & 1u) {
+      const v2f cs = rec_cs<L.x(J)>(rv, rb);
+      apply_x2<R, J>(a, cs);
+      apply_x2<R, J>(b, cs);
+      if (!((x2 >> J) & 1u)) { apply_x3<R, J>(a, cs); apply_x3<R, J>(b, cs); }
+    })
+  if (h1 & kFullDiagFlag) {
+    if (x2) {
+      const float e0 = __uint_as_float(rb.p[L.full0()]);
+      scale_full0(a[0], e0);
+      scale_full0(b[0], e0);
+    }
+    apply_full<NV>(a, rv, rb, false);
+    apply_full<NV>(b, rv, rb, false);
+  }
   QHBM_FOR_RB(R, if ((h0 >> (8 + J)) & 1u) { const v2f cs = rec_cs<L.ph1(J)>(rv, rb); apply_ph1<R, J>(a, cs); apply_ph1<R, J>(b, cs); })
   if ((h0 >> 16) & 0x3fu) {
     QHBM_FOR_PAIR(R,
@@ -1384,6 +1439,7 @@ __device__ __forceinline__ void instance_adj(const uint32_t (&cur)[1], const uin
   constexpr int S0 = L.slot0();
   const RecBase rb{recs + rec_off};
   const uint32_t h0 = rec_word<0>(cur, rb), h1 = rec_word<1>(cur, rb);
+  const uint32_t x2 = rb.p[L.x2_mask()];  // X gates in two-shear form (0 in instances without a FULL table)
   // ---- CPH (slot group 2) ----
   if (h1 & 0xffu) {
     float g[8] = {any_float(), any_float(), any_float(), any_float(), any_float(), any_float(), any_float(), any_float()};
@@ -1401,6 +1457,11 @@ __device__ __forceinline__ void instance_adj(const uint32_t (&cur)[1], const uin
     float g[6];
     full_partials(p, l, g1, g);
     if ((h0 >> 24) & 0x3fu) add_slots8<1, NW>(cells, lane, wave, sv[0], (h0 >> 24) & 0x3fu, g[0], g[1], g[2], g[3], g[4], g[5], any_float(), any_float());
+    if (x2) {  // (the partials above are taken on the exact pair: the scaling of the two-shear X gates comes after them)
+      const float e0 = __uint_as_float(rb.p[L.full0()]);
+      scale_full0(p[0], e0);
+      scale_full0(l[0], e0);
+    }
     apply_full<NB>(p, cur, rb, false);  // (adjoint records hold the CONJUGATE phases: prep_coefs_kernel, CoefJob::dagger)
     apply_full<NB>(l, cur, rb, false);
   }
@@ -1430,13 +1491,21 @@ __device__ __forceinline__ void instance_adj(const uint32_t (&cur)[1], const uin
   {
     float g[4] = {any_float(), any_float(), any_float(), any_float()};
     if (h0 & 0xfu) {
+      // While a two-shear gate of the instance is pending, the table has scaled the pair by the diagonal factors of ALL
+      // of them, and an inner product taken now would be wrong by those factors squared.  X_J commutes with every X
+      // gate of the instance (its own included), so Im<lam|X_J|psi> is the same after they are all un-applied, when
+      // the pair is exact again: first every shear, then every inner product.
       QHBM_FOR_RB(R,
         if ((h0 >> J) & 1u) {
           const v2f cs = rec_cs<L.x(J)>(cur, rb);  // (U^dagger's shear coefficients: negated at preparation)
-          if ((h0 >> (12 + J)) & 1u) g[J] = im_lam_x_psi<R, J>(p, l);  // (the X gates that own a gradient slot: a header bit, not a v_readlane of the slot vector)
-          apply_x<R, J>(p, cs);
-          apply_x<R, J>(l, cs);
+          if (!x2 && ((h0 >> (12 + J)) & 1u)) g[J] = im_lam_x_psi<R, J>(p, l);  // (the X gates that own a gradient slot: a header bit, not a v_readlane of the slot vector)
+          apply_x2<R, J>(p, cs);
+          apply_x2<R, J>(l, cs);
+          if (!((x2 >> J) & 1u)) { apply_x3<R, J>(p, cs); apply_x3<R, J>(l, cs); }
         })
+      if (x2 && ((h0 >> 12) & 0xfu)) {
+        QHBM_FOR_RB(R, if ((h0 >> (12 + J)) & 1u) g[J] = im_lam_x_psi<R, J>(p, l);)
+      }
     }
     // the values that exist: X gates that own a slot (word 0 bits 12..15), PH1 terms (per-term: bits 8..11, FULL: 4..7)
     const uint32_t present = ((h0 >> 12) & 0xfu) | ((((h0 >> 8) | (h0 >> 4)) & 0xfu) << 4);
@@ -2339,12 +2408,18 @@ __global__ void prep_coefs_kernel(const CoefJob* __restrict__ jobs, int n_jobs,
   }
   if (jb.mop == MOP_X) {  // X**t has period 2 in t: theta = pi t / 2 in [-pi/2, pi/2], |tan(theta/2)| <= 1
     t *= double(jb.mult);  // (1 except for the X**(1/2) of a lowered constant Hadamard)
-    const double tr = t - 2.0 * rint(0.5 * t);
-    double s2, c2;
-    sincospi(0.5 * tr, &s2, &c2);
-    const double sgn = jb.dagger ? -1.0 : 1.0;  // U^dagger = c*I + i*s*X: both shear coefficients negated
-    o[0] = float(sgn * s2 / (1.0 + c2));  // tan(theta / 2)
-    o[1] = float(sgn * s2);               // sin(theta)           (x_pair4's three shears)
+    // three shears (tan(theta / 2), sin(theta)), U^dagger = c*I + i*s*X: both negated; or, in a FULL instance and
+    // for |theta| <= pi / 3, two shears and a scaling that combine_diag_kernel folds into the table (x_shear.h)
+    const XShearCoefs k = x_shear_coefs(t, jb.x_full != 0, jb.dagger != 0);
+    o[0] = float(k.first);
+    o[1] = float(k.second);
+    if (jb.x_full) {  // the X slot j sits at word 2 + 2 j of its 64-word aligned record
+      constexpr RecordLayout L(4, false);
+      float* rec = coef + (jb.out_off & ~63);
+      const int xj = ((jb.out_off & 63) - L.x(0)) >> 1;
+      rec[L.x2_flag(xj)] = __uint_as_float(k.two_shear ? 1u : 0u);
+      *reinterpret_cast<double*>(rec + L.x2_exponent(xj)) = k.tr;
+    }
     return;
   }
   double sh, ch;  // sin, cos of pi*t/2
@@ -2418,23 +2493,35 @@ __global__ void combine_diag_kernel(float* __restrict__ coef, const uint32_t* __
   coef += size_t(blockIdx.y) * coef_stride;  // program of a batch
   const int r = blockIdx.x;
   const int m = threadIdx.x;
-  if (r >= n_records || m == 0 || m > 15) return;
+  if (r >= n_records || m > 15) return;
   constexpr RecordLayout L(4, false);
   float* rec = coef + rec_offsets[r];
   const uint32_t h0 = __float_as_uint(rec[0]), h1 = __float_as_uint(rec[1]);
   if (!(h1 & kFullDiagFlag)) return;
-  double cr = 1.0, ci = 0.0;
-  auto mul = [&](int w) {
-    const double a = rec[w], b = rec[w + 1];
-    const double nr = cr * a - ci * b, ni = cr * b + ci * a;
-    cr = nr;
-    ci = ni;
-  };
-  for (int j = 0; j < 4; ++j)
-    if (((m >> j) & 1) && ((h0 >> (4 + j)) & 1u)) mul(L.in_ph1(j));
-  for (int jb = 1; jb < 4; ++jb)
-    for (int ja = 0; ja < jb; ++ja)
-      if (((m >> ja) & 1) && ((m >> jb) & 1) && ((h0 >> (24 + pair_index(ja, jb))) & 1u)) mul(L.in_ph2(pair_index(ja, jb)));
+  // ... times the scaling D = diag(c, 1/c) of the instance's two-shear X gates (x_shear.h), in double from the reduced
+  // exponents their jobs left in the record: 1/c_J where bit J of m is set, c_J where it is clear -- entry 0 too (real,
+  // word full0), which the kernels apply only when the mask is not empty.
+  uint32_t two = 0;
+  double tr[4] = {0.0, 0.0, 0.0, 0.0}, ph1[4][2], ph2[6][2];
+  for (int j = 0; j < 4; ++j) {
+    if (((h0 >> j) & 1u) && __float_as_uint(rec[L.x2_flag(j)]) != 0u) {
+      two |= 1u << j;
+      tr[j] = *reinterpret_cast<const double*>(rec + L.x2_exponent(j));
+    }
+    ph1[j][0] = rec[L.in_ph1(j)];
+    ph1[j][1] = rec[L.in_ph1(j) + 1];
+  }
+  for (int pi = 0; pi < 6; ++pi) {
+    ph2[pi][0] = rec[L.in_ph2(pi)];
+    ph2[pi][1] = rec[L.in_ph2(pi) + 1];
+  }
+  double cr, ci;
+  x_full_entry(m, (h0 >> 4) & 0xfu, (h0 >> 24) & 0x3fu, ph1, ph2, two, tr, &cr, &ci);
+  if (m == 0) {
+    rec[L.full0()] = float(cr);
+    rec[L.x2_mask()] = __uint_as_float(two);
+    return;
+  }
   rec[L.full(m)] = float(cr);
   rec[L.full(m) + 1] = float(ci);
 }

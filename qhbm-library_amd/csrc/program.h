@@ -82,7 +82,7 @@ constexpr int kMeasTermWords = 4;
 
 // ---- one-qubit micro-ops / coefficient-job tags ------------------------------
 enum : uint32_t {
-  MOP_X = 1,      // c*I - i*s*X on a register bit     (coef: tan(theta/2), sin(theta): three shears)
+  MOP_X = 1,      // c*I - i*s*X on a register bit     (coef: tan(theta/2), sin(theta): three shears; or two: x_shear.h)
   MOP_Y = 2,      // c*I - i*s*Y                         (coef: c, s)
   MOP_MAT1 = 3,   // dense 2x2                           (coef: 8 floats, row-major re,im)
   MOP_MAT2 = 4,   // coefficient-job tag of a dense 4x4 (32 floats); executed by OP_GATE2
@@ -108,7 +108,9 @@ constexpr int pair_index(int lo, int hi) { return hi * (hi - 1) / 2 + lo; }  // 
 //           register value m: the whole diagonal on the register bits is then ONE complex
 //           multiply per amplitude.  A FULL instance keeps its term masks in fph1/fph2 and has
 //           ph1_mask = ph2_mask = 0, so table and per-term slots are independent triangles.
-//   vec 1:  (FULL only) the per-term phases PH1[4] PH2[6] that combine_diag_kernel multiplies
+//   vec 1:  (FULL only) the per-term phases PH1[4] PH2[6] that combine_diag_kernel multiplies; then the words of the
+//           two-shear X gates (x_shear.h): FULL0 = table entry of register value 0, the two-shear bit mask the
+//           kernels branch on, and per X bit the flag and reduced exponent prep_coefs_kernel leaves for the combine
 //   vec 2:  DENSE[4] 2x2 blocks (8 floats; adjoint: U^dagger then generator, 16 floats)
 //   vec 3:  (adjoint) SLOT[32] = gradient slot per entry, pass-local, laid out for the eight-wide wave
 //           reduction (slot_lane8): group 0 = X + PH1, 1 = PH2, 2 = CPH, 3 = Y + DENSE
@@ -127,6 +129,11 @@ struct RecordLayout {
   constexpr int y(int j) const { return 54 + 2 * j; }
   constexpr int in_ph1(int j) const { return 64 + 2 * j; }    // FULL: combine inputs
   constexpr int in_ph2(int pi) const { return 72 + 2 * pi; }
+  // FULL, two-shear X gates (x_shear.h), all DYNAMIC: rewritten on every call, per program of a batch
+  constexpr int full0() const { return 84; }                  // table entry of register value 0: the product of the c_J, real
+  constexpr int x2_mask() const { return 85; }                // register bits whose X runs as two shears (combine_diag_kernel)
+  constexpr int x2_flag(int j) const { return 86 + j; }       // the same per bit, as prep_coefs_kernel's X job decided it
+  constexpr int x2_exponent(int j) const { return 90 + 2 * j; }  // its reduced exponent, a double
   constexpr int dense_words() const { return adjoint ? 16 : 8; }
   constexpr int dense(int j) const { return 128 + dense_words() * j; }
   constexpr int slot0() const { return 192; }

@@ -670,7 +670,15 @@ class Builder {
       CoefJob job = base_job(op);
       int lane = 0, slot_lane = 0;
       switch (pl.kind) {
-        case 0: job.mop = MOP_X; lane = L.x(pl.j); slot_lane = L.slot_x(pl.j); break;
+        case 0:
+          job.mop = MOP_X;
+          lane = L.x(pl.j);
+          slot_lane = L.slot_x(pl.j);
+          // Inside an instance the X gates and the table are neighbours in both sweeps, with the table on the side
+          // of the gate's diagonal factor (x_shear.h) -- whatever the circuit order was: an X that follows a diagonal
+          // term on its bit went into a later instance (above).
+          job.x_full = (rec[1] & kFullDiagFlag) ? 1 : 0;
+          break;
         case 1: job.mop = MOP_Y; lane = L.y(pl.j); slot_lane = L.slot_y(pl.j); break;
         case 2: job.mop = MOP_MAT1; lane = L.dense(pl.j); slot_lane = L.slot_dense(pl.j); break;
         case 3:
@@ -1485,6 +1493,7 @@ std::string describe_plan(const Plan& p) {
     const RecordLayout L(p.R, p.adjoint);
     int n_inst = 0, n_full = 0, x = 0, ph1 = 0, ph2 = 0, fph1 = 0, fph2 = 0, cph = 0, cph_tile = 0, groups = 0;
     int x_hist[5] = {0, 0, 0, 0, 0};
+    int x_full = 0;  // X gates next to a FULL table: the ones that may run as two shears (x_shear.h)
     auto pc = [](uint32_t v) { return __builtin_popcount(v); };
     for (uint32_t off : p.record_offsets) {
       const uint32_t h0 = p.coef_init[off], h1 = p.coef_init[off + 1];
@@ -1497,6 +1506,7 @@ std::string describe_plan(const Plan& p) {
       groups += ((h0 & 0xf0fu) != 0 || ((h1 & kFullDiagFlag) && ((h0 >> 4) & 0xfu))) + ((h1 & 0xffu) != 0);
       if (h1 & kFullDiagFlag) {
         ++n_full;
+        x_full += pc(h0 & 0xfu);
         fph1 += pc((h0 >> 4) & 0xfu);
         fph2 += pc((h0 >> 24) & 0x3fu);
         groups += ((h0 >> 24) & 0x3fu) != 0;
@@ -1529,7 +1539,7 @@ std::string describe_plan(const Plan& p) {
     }
     os << "  census: instances=" << n_inst << " (FULL " << n_full << ") X=" << x << " PH1=" << ph1 << " PH2=" << ph2
        << " FULL-PH1=" << fph1 << " FULL-PH2=" << fph2 << " CPH=" << cph << " (tile predicate " << cph_tile << ") slot-groups=" << groups << " instances by X count 0..4: " << x_hist[0] << "/" << x_hist[1] << "/"
-       << x_hist[2] << "/" << x_hist[3] << "/" << x_hist[4] << "\n";
+       << x_hist[2] << "/" << x_hist[3] << "/" << x_hist[4] << " X-in-FULL=" << x_full << "\n";
   }
   for (size_t i = 0; i < p.passes.size(); ++i) {
     const Pass& q = p.passes[i];
@@ -1548,6 +1558,20 @@ std::string describe_plan(const Plan& p) {
       for (size_t k = 0; k < q.local_phys.size(); ++k) os << (k ? "," : "") << q.local_phys[k];
       if (q.flags & PASS_RELABEL) os << " moves-local-bits=" << std::hex << q.frozen_new_local << std::dec;
       if (q.frozen_old_local) os << " stale-local-bits=" << std::hex << q.frozen_old_local << std::dec;
+    }
+    {  // per round: X micro-ops next to a FULL table / all X micro-ops (which may run as two shears: x_shear.h)
+      const RecordLayout L(p.R, p.adjoint);
+      os << " x_full=";
+      for (size_t r = 0; r < q.round_words.size(); ++r) {
+        const uint32_t w0 = q.prog[q.round_words[r]], n_inst = (w0 & ~kRoundNoBarrier) >> 8, first = q.prog[q.round_words[r] + 2];
+        int x = 0, xf = 0;
+        for (uint32_t i = 0; i < n_inst; ++i) {
+          const uint32_t* rec = &p.coef_init[first + size_t(i) * size_t(L.words())];
+          x += __builtin_popcount(rec[0] & 0xfu);
+          if (rec[1] & kFullDiagFlag) xf += __builtin_popcount(rec[0] & 0xfu);
+        }
+        os << (r ? "," : "") << xf << "/" << x;
+      }
     }
     if (p.adjoint) {
       os << " dead=";

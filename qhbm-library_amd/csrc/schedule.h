@@ -56,6 +56,9 @@ struct CoefJob {
   // apart from `offset` and added in double -- offset + 1/2 is not a float in general, and the sum rounded to one moved
   // the phase by up to 1e-7 (found by the plan emulator of tests/sanitize/)
   float add_offset;
+  // MOP_X in an instance with a FULL diagonal table: the gate may run as two shears with its scaling folded into
+  // the table (x_shear.h; cleared at upload when the engine's x_two_shear option is off)
+  int32_t x_full;
 };
 
 struct Pass {

@@ -79,10 +79,15 @@ __global__ __launch_bounds__(1 << (K - 4), adjx_min_waves(K)) void pass_adjx_ker
         "  regs_from_tile(p, rp);\n  regs_from_tile(l, rl);\n  __syncthreads();\n"),
         "    const ThreadOff o = thread_offsets<ROWS>(t, tid);\n    round_store0<R>(T, DB, p);\n    __syncthreads();\n    __builtin_amdgcn_sched_barrier(0);\n    store_tile<K, NT, ROWS>(xt, sp, t, o, tid);\n    __builtin_amdgcn_sched_barrier(0);\n    __syncthreads();\n    round_store0<R>(T, DB, l);\n    __syncthreads();\n    __builtin_amdgcn_sched_barrier(0);\n    store_tile<K, NT, ROWS>(xt, sl, t, o, tid);\n",
         "    regs_to_global<K, NT>(p, sp, t, tid);\n    regs_to_global<K, NT>(l, sl, t, tid);\n    __syncthreads();\n"),
-    "no_x_inner": lambda t: in_instance(t, "g[J] = im_lam_x_psi<R, J>(p, l);", "g[J] = p[0].x;"),
-    "no_x_on_lambda": lambda t: in_instance(t, "          apply_x<R, J>(l, cs);\n", ""),
-    "no_x_at_all": lambda t: in_instance(in_instance(in_instance(t, "          apply_x<R, J>(l, cs);\n", ""), "          apply_x<R, J>(p, cs);\n", ""),
-                                         "g[J] = im_lam_x_psi<R, J>(p, l);", "g[J] = p[0].x + cs.x;"),
+    # (both places the inner product may stand: before the shears, or after them all when a two-shear gate is pending)
+    "no_x_inner": lambda t: in_instance(in_instance(t, "g[J] = im_lam_x_psi<R, J>(p, l);  //", "g[J] = p[0].x;  //"),
+                                        "g[J] = im_lam_x_psi<R, J>(p, l);)", "g[J] = p[0].x;)"),
+    "no_x_on_lambda": lambda t: in_instance(in_instance(t, "          apply_x2<R, J>(l, cs);\n", ""), " apply_x3<R, J>(l, cs); }", " }"),
+    "no_x_at_all": lambda t: in_instance(in_instance(in_instance(in_instance(in_instance(
+        t, "          apply_x2<R, J>(l, cs);\n", ""), "          apply_x2<R, J>(p, cs);\n", ""),
+        "          if (!((x2 >> J) & 1u)) { apply_x3<R, J>(p, cs); apply_x3<R, J>(l, cs); }\n", ""),
+        "g[J] = im_lam_x_psi<R, J>(p, l);  //", "g[J] = p[0].x + cs.x;  //"),
+        "g[J] = im_lam_x_psi<R, J>(p, l);)", "g[J] = p[0].x;)"),
     "no_full": lambda t: in_instance(t, "  if (h1 & kFullDiagFlag) {", "  if ((h1 & kFullDiagFlag) && lane == 77) {"),
     "no_cph": lambda t: in_instance(t, "  if (h1 & 0xffu) {", "  if ((h1 & 0xffu) && lane == 77) {", 1),
     "no_ph1_ph2": lambda t: in_instance(in_instance(t, "  if ((h0 >> 16) & 0x3fu) {", "  if (((h0 >> 16) & 0x3fu) && lane == 77) {"),
@@ -122,8 +127,8 @@ def in_fwd_instance(text, old, new, count=-1):
 VARIANTS.update({
     "fwd_no_instances": lambda t: once(t, "        instance_fwd<R, NV, GEN>(cur, recs, rec_off, lane, amp, TL | tile_hi);",
                                        "        if (lane == 77) instance_fwd<R, NV, GEN>(cur, recs, rec_off, lane, amp, TL | tile_hi);"),
-    "fwd_no_x": lambda t: in_fwd_instance(t, "if ((h0 >> J) & 1u) apply_x<R, J>(a, rec_cs<L.x(J)>(rv, rb));", "if (((h0 >> J) & 1u) && lane == 77) apply_x<R, J>(a, rec_cs<L.x(J)>(rv, rb));"),
-    "fwd_no_full": lambda t: in_fwd_instance(t, "if (h1 & kFullDiagFlag) apply_full<NV>(a, rv, rb, false);", "if ((h1 & kFullDiagFlag) && lane == 77) apply_full<NV>(a, rv, rb, false);"),
+    "fwd_no_x": lambda t: in_fwd_instance(t, "if ((h0 >> J) & 1u) apply_x_form<R, J>(a, rec_cs<L.x(J)>(rv, rb), x2);", "if (((h0 >> J) & 1u) && lane == 77) apply_x_form<R, J>(a, rec_cs<L.x(J)>(rv, rb), x2);"),
+    "fwd_no_full": lambda t: in_fwd_instance(t, "  if (h1 & kFullDiagFlag) {\n    if (x2) scale_full0(a[0]", "  if ((h1 & kFullDiagFlag) && lane == 77) {\n    if (x2) scale_full0(a[0]"),
     "fwd_no_cph": lambda t: in_fwd_instance(t, "  if (h1 & 0xffu) {", "  if ((h1 & 0xffu) && lane == 77) {"),
     # forward without its HBM traffic (tile neither loaded nor stored): what the memory phase adds to the compute
     "fwd_no_tile_io": lambda t: once(once(t, "    prefetch_tile<K, NT>(r, ld, t, toff);\n    if (a.frozen_old_local) clear_stale",
