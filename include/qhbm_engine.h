@@ -337,6 +337,28 @@ int qhbm_parity_energy_vjp(const int8_t* d_bits, int64_t n_rows, int n_bits,
                            const uint64_t* d_masks, int n_terms, const float* d_weights,
                            float* d_grad, void* stream);
 
+/* Gibbs-With-Gradients chains (qhbmlib/inference/ebm.py:564-760) of the same energies, entirely on the device
+ * (DESIGN.md 6d).  The energy is multilinear in x, so the sampler's first-order estimate is exact:
+ *   h_j(x) = (E(x) - E(x ^ e_j)) / 2 = sum_{k : j in S_k} d_thetas[k] * parity_k(x),   L(x) = logsumexp_j h_j(x);
+ * a step proposes bit i with probability exp(h_i(x) - L(x)) and accepts the flip with probability
+ * min(1, exp(L(x) - L(x ^ e_i))), the reference's exp(E(x) - E(x')) q(i|x') / q(i|x).
+ * d_chain_states[c] holds chain c (column q of the bitstring = bit q) and is advanced in place by n_steps steps; step t
+ * of the call is ABSOLUTE step step0 + t and draws Philox4x32-10 with key (seed mod 2^32, seed >> 32) and counter
+ * {step mod 2^32, step >> 32, 0x47574731, c} (qhbm_sample uses 0x51b0c6a1 in the third word): output words 0, 1 make the
+ * fp64 uniform u1 = c0 2^-32 + c1 2^-64 that picks the first bit whose inclusive fp32 prefix of exp(h_j - max h) exceeds
+ * u1 times their sum, words 2, 3 make u2, compared with expf(min(0, L(x) - L(x'))).  The trajectory of chain c does not
+ * depend on n_chains, on how a run is cut into calls (continue with step0 + n_steps), or on d_out_samples.
+ * d_out_samples, if not NULL, takes the state after every step: [n_steps, n_chains, n_bits] int8 (NULL: burn-in);
+ * d_out_accepted, if not NULL, takes the number of accepted steps per chain of this call (overwritten).
+ * Mask bits at or above n_bits are ignored, a zero mask belongs to no bit, equal masks add.  One wave runs one chain with
+ * the term table and one membership bitmap per bit in LDS: 12 n_terms + 4 ceil(n_terms / 32) n_bits bytes, at most
+ * 160 KiB -- more is an error, there is no slower path.  Runs on the current device and the given stream; no host
+ * synchronisation, no allocation; n_steps == 0 and n_chains == 0 do nothing. */
+int qhbm_gwg_sample(uint64_t* d_chain_states, int n_chains, int n_bits,
+                    const uint64_t* d_masks, const float* d_thetas, int n_terms,
+                    uint64_t seed, uint64_t step0, int64_t n_steps,
+                    int8_t* d_out_samples, int32_t* d_out_accepted, void* stream);
+
 /* ---- introspection (tests, bench, DESIGN.md numbers) ------------------- */
 /* Number of HBM passes (kernel launches over the state) the scheduler emits
  * for one forward of the installed circuit + observables. */

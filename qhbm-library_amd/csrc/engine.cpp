@@ -1648,6 +1648,23 @@ int qhbm_parity_energy_vjp(const int8_t* d_bits, int64_t n_rows, int n_bits, con
   return 0;
 }
 
+int qhbm_gwg_sample(uint64_t* d_chain_states, int n_chains, int n_bits, const uint64_t* d_masks, const float* d_thetas,
+                    int n_terms, uint64_t seed, uint64_t step0, int64_t n_steps, int8_t* d_out_samples,
+                    int32_t* d_out_accepted, void* stream) {
+  if (n_chains < 0 || n_terms < 0 || n_steps < 0) return fail(nullptr, "qhbm_gwg_sample: negative size");
+  if (n_bits < 1 || n_bits > 64) return fail(nullptr, "qhbm_gwg_sample: n_bits must be in [1, 64]");
+  if (n_chains > 0 && !d_chain_states) return fail(nullptr, "qhbm_gwg_sample: d_chain_states is NULL");
+  if (n_terms > 0 && (!d_masks || !d_thetas)) return fail(nullptr, "qhbm_gwg_sample: d_masks / d_thetas is NULL");
+  if (gwg_lds_bytes(n_bits, n_terms) > kGwgLdsMax)
+    return fail(nullptr, "qhbm_gwg_sample: " + std::to_string(n_terms) + " terms over " + std::to_string(n_bits) +
+                             " bits need " + std::to_string(gwg_lds_bytes(n_bits, n_terms)) + " bytes of LDS, " +
+                             std::to_string(kGwgLdsMax) + " fit");
+  hipError_t e = launch_gwg_sample(d_chain_states, n_chains, n_bits, d_masks, d_thetas, n_terms, seed, step0, n_steps,
+                                   d_out_samples, d_out_accepted, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, std::string("qhbm_gwg_sample: ") + hipGetErrorString(e));
+  return 0;
+}
+
 int qhbm_sample(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, int n_shots,
                 uint64_t seed, int shift_gate, double shift, int8_t* d_out_samples, void* stream) {
   if (!h) return 1;

@@ -146,6 +146,15 @@ hipError_t launch_parity_energy(const int8_t* bits, int64_t n_rows, int n, const
                                 const float* thetas, int n_terms, float* energy, hipStream_t stream);
 hipError_t launch_parity_energy_vjp(const int8_t* bits, int64_t n_rows, int n, const uint64_t* masks, int n_terms,
                                     const float* w, float* grad, hipStream_t stream);
+// Gibbs-With-Gradients chains of a spin-parity energy (gwg.hip): n_steps Metropolis steps of n_chains chains, one wave
+// each, whose uint64 states (column q = bit q) are read and written in place.  Step t of the call uses the random numbers
+// of absolute step step0 + t; out (or null) takes [n_steps, n_chains, n_bits] int8, accepted (or null) [n_chains] counts.
+// The term table and the per-bit membership bitmaps take gwg_lds_bytes(n_bits, n_terms) of LDS, at most kGwgLdsMax.
+constexpr size_t kGwgLdsMax = 160u * 1024u;  // the LDS of one CU
+size_t gwg_lds_bytes(int n_bits, int n_terms);
+hipError_t launch_gwg_sample(uint64_t* states, int n_chains, int n_bits, const uint64_t* masks, const float* thetas,
+                             int n_terms, uint64_t seed, uint64_t step0, int64_t n_steps, int8_t* out, int32_t* accepted,
+                             hipStream_t stream);
 // block_cum: n_states * 2^n / 1024 doubles of scratch.
 hipError_t launch_sample(const float2* psi, uint32_t n, int n_user, uint32_t n_states, double* block_cum,
                          uint32_t n_shots, uint64_t seed, uint32_t state0, int8_t* out, hipStream_t stream);

@@ -39,6 +39,7 @@ ABI_SYMBOLS = (
     "qhbm_workspace_bytes", "qhbm_allocated_bytes", "qhbm_expectation", "qhbm_expectation_vjp",
     "qhbm_expectation_retain", "qhbm_expectation_vjp_retained", "qhbm_retained_states", "qhbm_state_gradients",
     "qhbm_expectation_jacobian", "qhbm_statevector", "qhbm_sample", "qhbm_sample_counts", "qhbm_program_vjps", "qhbm_parity_energy", "qhbm_parity_energy_vjp",
+    "qhbm_gwg_sample",
     "qhbm_num_passes", "qhbm_describe_schedule",
     "qhbm_kernel_time_ms", "qhbm_traffic_model", "qhbm_flop_model", "qhbm_op_census", "qhbm_clock_probe", "qhbm_plan_builds",
     "qhbm_table_expectation", "qhbm_table_expectation_retain", "qhbm_table_expectation_vjp",
@@ -107,6 +108,7 @@ def load_library():
   lib.qhbm_sample_counts.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, ctypes.c_uint64, vp, vp]
   lib.qhbm_parity_energy.argtypes = [vp, i64, i32, vp, vp, i32, vp, vp]
   lib.qhbm_parity_energy_vjp.argtypes = [vp, i64, i32, vp, i32, vp, vp, vp]
+  lib.qhbm_gwg_sample.argtypes = [vp, i32, i32, vp, vp, i32, ctypes.c_uint64, ctypes.c_uint64, i64, vp, vp, vp]
   lib.qhbm_num_passes.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
   lib.qhbm_describe_schedule.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t]
   lib.qhbm_kernel_time_ms.argtypes = [
@@ -187,6 +189,40 @@ def parity_energy(thetas, bits, masks):
   if not bits.is_cuda:
     raise EngineError("parity_energy runs on the GPU: pass CUDA bitstrings (CPU tensors use the torch layers)")
   return _ParityEnergyFunction.apply(thetas, bits, masks)
+
+
+GWG_LDS_MAX = 160 * 1024  # csrc/kernels.h kGwgLdsMax
+
+
+def gwg_lds_bytes(n_bits, n_terms):
+  """LDS one Gibbs-With-Gradients chain needs (csrc/gwg.hip gwg_lds_bytes): the 12-byte term table and one membership
+  bitmap over the terms per bit.  More than GWG_LDS_MAX does not run."""
+  return (12 * n_terms + 4 * ((n_terms + 31) // 32) * n_bits + 15) & ~15
+
+
+def gwg_sample(states, n_bits, masks, thetas, seed, step0, n_steps, write_samples=True, count_accepted=False):
+  """n_steps Gibbs-With-Gradients steps of the chains `states` (int64 CUDA [n_chains], column q of a bitstring = bit q;
+  advanced IN PLACE) under E(x) = sum_k thetas[k] parity_k(x) with int64 CUDA column `masks` (qhbm_gwg_sample).  Step t
+  draws the random numbers of absolute step step0 + t.  Returns (samples, accepted): int8 CUDA [n_steps, n_chains, n_bits]
+  or None, int32 CUDA [n_chains] or None."""
+  lib = load_library()
+  if not (states.is_cuda and states.dtype == torch.int64 and states.dim() == 1 and states.is_contiguous()):
+    raise EngineError("gwg_sample needs a contiguous int64 CUDA vector of chain states")
+  dev = states.device
+  masks = masks.to(device=dev, dtype=torch.int64).contiguous()
+  th = thetas.detach().to(device=dev, dtype=torch.float32).contiguous()
+  if masks.numel() != th.numel():
+    raise EngineError(f"gwg_sample: {masks.numel()} masks for {th.numel()} thetas")
+  n_chains, n_steps = states.numel(), int(n_steps)
+  out = torch.empty((max(n_steps, 0), n_chains, int(n_bits)), dtype=torch.int8, device=dev) if write_samples else None
+  acc = torch.zeros((n_chains,), dtype=torch.int32, device=dev) if count_accepted else None
+  with torch.cuda.device(dev):
+    _check_global(lib.qhbm_gwg_sample(
+        states.data_ptr(), n_chains, int(n_bits), masks.data_ptr(), th.data_ptr(), masks.numel(),
+        int(seed) & (2**64 - 1), int(step0) & (2**64 - 1), n_steps,
+        out.data_ptr() if out is not None else None, acc.data_ptr() if acc is not None else None,
+        ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+  return out, acc
 
 
 class Engine:

@@ -443,11 +443,19 @@ class GibbsWithGradientsKernel:
 class GibbsWithGradientsInference(EnergyInference):
   """Inference with a Gibbs-With-Gradients Markov chain (ebm.py:705-760): the chain state
   persists between calls; `num_burnin_samples` steps are discarded whenever the energy's
-  variables have changed."""
+  variables have changed.
+
+  `chain` selects where the chain runs.  "host" (the default) is the reference's loop: autograd through the energy,
+  a host generator.  "device" runs whole chains inside one HIP kernel (`qhbm_gwg_sample`): for a
+  spin-parity energy (`BernoulliEnergy`, `KOBE`) the first-order estimate is exact and needs no autograd.  It needs a
+  `PauliMixin` energy with parity masks, variables on a CUDA device, at most 64 bits and terms that fit in LDS, and
+  raises `ValueError` naming what is missing; "auto" takes the device chain when all of that holds and the host chain
+  otherwise.  `num_chains` > 1 (device only) advances that many independent chains side by side: `sample(m)` runs
+  ceil(m / num_chains) steps and returns the first m rows in [step, chain] order."""
 
   def __init__(self, input_energy: energy.BitstringEnergy, num_expectation_samples: int,
                num_burnin_samples: int, name: Union[None, str] = None,
-               initial_seed: Union[None, int] = None):
+               initial_seed: Union[None, int] = None, chain: str = "host", num_chains: int = 1):
     super().__init__(input_energy, num_expectation_samples, initial_seed, name)
     # the chain owns its random stream (the base class re-seeds the shared generator per call)
     self._chain_generator = torch.Generator().manual_seed(self._seed % (2**63))
@@ -455,6 +463,84 @@ class GibbsWithGradientsInference(EnergyInference):
     self._chain_state = torch.bernoulli(torch.full((self.energy.num_bits,), 0.5),
                                         generator=self._chain_generator).to(torch.int8)
     self.num_burnin_samples = num_burnin_samples
+    if chain not in ("host", "device", "auto"):
+      raise ValueError(f"chain must be 'host', 'device' or 'auto', not {chain!r}")
+    self._num_chains = int(num_chains)
+    if self._num_chains < 1:
+      raise ValueError(f"num_chains must be at least 1, not {num_chains}")
+    missing = self._device_chain_missing() if chain != "host" else []
+    if chain == "device" and missing:
+      raise ValueError("chain='device' needs " + "; ".join(missing))
+    self._device_chain = chain != "host" and not missing
+    if self._num_chains > 1 and not self._device_chain:
+      raise ValueError("num_chains > 1 needs the device chain (chain='device'); the host chain is a single chain" +
+                       ("".join("; missing: " + m for m in missing)))
+    self._chain_states = None
+    self._chain_step = 0
+    self._chain_seed = None
+    if self._device_chain:
+      self._restart_device_chain()
+
+  def _device_chain_missing(self):
+    """What the device chain lacks for this energy (strings; empty: it can run)."""
+    from qhbmlib_amd import _engine  # pylint: disable=import-outside-toplevel
+    e, missing = self._energy, []
+    sets = None
+    if isinstance(e, energy.PauliMixin):
+      try:
+        sets = list(e._parity_index_sets())   # pylint: disable=protected-access
+      except NotImplementedError:
+        sets = None
+    if sets is None:
+      missing.append("a PauliMixin energy with parity masks (_parity_masks); this one is a " + type(e).__name__)
+    if not _device_of(e).type == "cuda":
+      missing.append(f"the energy's variables on a CUDA device (they are on {_device_of(e)})")
+    if e.num_bits > 64:
+      missing.append(f"at most 64 bits (the energy has {e.num_bits})")
+    elif sets is not None and _engine.gwg_lds_bytes(e.num_bits, len(sets)) > _engine.GWG_LDS_MAX:
+      missing.append(f"terms that fit in LDS ({len(sets)} terms over {e.num_bits} bits take "
+                     f"{_engine.gwg_lds_bytes(e.num_bits, len(sets))} of {_engine.GWG_LDS_MAX} bytes)")
+    return missing
+
+  def _restart_device_chain(self):
+    """The chains' initial states, from the chain generator: chain 0 is the host chain's initial state, the others are
+    drawn after it.  Packed (column q = bit q) into one int64 per chain, on the energy's device; the step counter, a
+    launch argument, restarts with them."""
+    n = self.energy.num_bits
+    rows = self._chain_state.reshape(1, n)
+    if self._num_chains > 1:
+      more = torch.bernoulli(torch.full((self._num_chains - 1, n), 0.5), generator=self._chain_generator).to(torch.int8)
+      rows = torch.cat([rows, more], 0)
+    packed = torch.zeros((self._num_chains,), dtype=torch.int64)
+    for q in range(n):   # (bit 63 is the sign bit of the int64 torch stores the word in: shifts wrap, no overflow check)
+      packed |= rows[:, q].to(torch.int64) << q
+    self._chain_states = packed.to(_device_of(self._energy))
+    self._chain_step = 0
+    self._chain_seed = self._seed
+
+  @property
+  def device_chain(self):
+    """True when the chain runs in the HIP kernel."""
+    return self._device_chain
+
+  @property
+  def num_chains(self):
+    return self._num_chains
+
+  @property
+  def chain_states(self):
+    """Device chain: a copy of the packed chain states, int64 [num_chains] (column q of a bitstring = bit q)."""
+    return None if self._chain_states is None else self._chain_states.clone()
+
+  @property
+  def chain_step(self):
+    """Device chain: the absolute index of the next step (the counter of its random stream)."""
+    return self._chain_step
+
+  @property
+  def chain_seed(self):
+    """Device chain: the key of its random stream (the sampler's seed when the chains were last restarted)."""
+    return self._chain_seed
 
   def agree_seed(self, group=None):
     """... and the chain restarts from the agreed seed (its generator and initial state were drawn from the old one)."""
@@ -463,10 +549,25 @@ class GibbsWithGradientsInference(EnergyInference):
     self._chain_generator.manual_seed(self._seed % (2**63))
     self._chain_state = torch.bernoulli(torch.full((self.energy.num_bits,), 0.5),
                                         generator=self._chain_generator).to(torch.int8)
+    if self._device_chain:
+      self._restart_device_chain()
     self._first_inference = True   # burn in again
     return True
 
+  def _device_steps(self, num_steps, write_samples):
+    from qhbmlib_amd import _engine  # pylint: disable=import-outside-toplevel
+    e = self._energy
+    dev = self._chain_states.device
+    out, _ = _engine.gwg_sample(self._chain_states, e.num_bits, e._parity_masks(dev),   # pylint: disable=protected-access
+                                e.post_process[0].kernel, self._chain_seed, self._chain_step, num_steps,
+                                write_samples=write_samples)
+    self._chain_step += int(num_steps)
+    return out
+
   def _ready_inference(self):
+    if self._device_chain:
+      self._device_steps(int(self.num_burnin_samples), write_samples=False)
+      return
     state = self._chain_state
     for _ in range(int(self.num_burnin_samples)):
       state, _ = self._kernel.one_step(state, [])
@@ -476,6 +577,10 @@ class GibbsWithGradientsInference(EnergyInference):
     return self.sample(inputs)
 
   def _sample(self, num_samples: int):
+    if self._device_chain:
+      steps = -(-int(num_samples) // self._num_chains)
+      out = self._device_steps(steps, write_samples=True)
+      return out.reshape(steps * self._num_chains, self.energy.num_bits)[:int(num_samples)]
     out = torch.empty((int(num_samples), self.energy.num_bits), dtype=torch.int8)
     state = self._chain_state
     for i in range(int(num_samples)):
