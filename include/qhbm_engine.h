@@ -101,6 +101,19 @@ void qhbm_destroy(qhbm_engine* h);
 const char* qhbm_last_error(const qhbm_engine* h);
 
 /* ---- model ------------------------------------------------------------- */
+/* Every setter below, and qhbm_set_option, may be called on a live handle between compute calls.  What survives:
+ *   - the observables survive qhbm_set_circuit if and only if n_qubits is unchanged (they are kept, masks and scales as
+ *     installed); after a circuit of another size the calls that need observables fail with "qhbm_set_observables has
+ *     not been called" until they are installed again;
+ *   - the gradient mask never survives qhbm_set_circuit, not even for a circuit with as many parameters;
+ *   - options survive everything;
+ *   - the states kept by qhbm_expectation_retain / qhbm_table_expectation_retain and the rows qhbm_state_gradients
+ *     serves survive NO setter that invalidates a plan: qhbm_set_circuit, qhbm_set_observables, a planning option of
+ *     qhbm_set_option (whatever the value, the current one included), and qhbm_set_gradient_mask with a mask that differs
+ *     from the installed one.  qhbm_retained_states reads 0 from that moment on, and the retained VJPs and
+ *     qhbm_state_gradients fail and write nothing.  A setter that changes no plan drops nothing: the installed mask
+ *     again, or an option that takes no part in planning ("chunk_states", "workspace_budget_mb", "profile_events",
+ *     "values_from_observable", "shift_prefix_sharing", "observable_kernel" and the other kernel choices). */
 /* Installs the total circuit (bit-injector excluded: it is the `bits`
  * argument).  Replaces tfq serialisation + append_circuit
  * (circuit.py:129-160).  The gate list is copied. */
@@ -228,9 +241,12 @@ int qhbm_retained_states(qhbm_engine* h, int* out_U);
 /* Per-state rows of the last adjoint VJP (qhbm_expectation_vjp with method 0, or
  * qhbm_expectation_vjp_retained) on U states:
  *   d_rows[u, p] = sum_k d_upstream[u, k] * d out[u, k] / d params[p]       [U, n_params] float
- * so that sum_u d_rows[u, :] is that call's d_grad.  A multi-GPU host gathers the rows of every
+ * so that sum_u d_rows[u, :] is that call's d_grad up to the fp32 rounding of each row and of d_grad.  A multi-GPU host gathers the rows of every
  * rank and adds them in global state order: the [P] gradient is then bit-identical for any number
- * of ranks (SURVEY.md 8e "fixed-order summation"); an all-reduce of d_grad is the fast path. */
+ * of ranks (SURVEY.md 8e "fixed-order summation"); an all-reduce of d_grad is the fast path.  A forward-only
+ * qhbm_expectation in between keeps the rows; another VJP, qhbm_expectation_jacobian, qhbm_sample_counts,
+ * qhbm_program_vjps and every setter that invalidates a plan (see "model" above) drop them: the call then fails and
+ * writes nothing. */
 int qhbm_state_gradients(qhbm_engine* h, int U, float* d_rows, void* stream);
 
 /* Full Jacobian d_jac[u, k, p] (tests / small n only; adjoint). */

@@ -228,6 +228,17 @@ size_t own_bytes(const qhbm_engine* h) {
          }();
 }
 
+// The ONE place where a setter declares the plans out of date (qhbm_set_circuit, qhbm_set_observables, the planning
+// options).  What was computed under them goes with them: the states a retaining forward left in psi, and the
+// per-state slot rows of the last adjoint VJP -- a rebuilt plan orders its slots, and maps them to parameters, in its
+// own way, so qhbm_state_gradients would scatter the old rows through the new plan's tables (and read past them if the
+// new plan has more slots).  qhbm_set_gradient_mask drops both itself: it invalidates the backward plan alone.
+void invalidate_plans(qhbm_engine* h) {
+  h->plans_valid = false;
+  h->retained_U = 0;
+  h->state_grad_U = 0;
+}
+
 int need_device(qhbm_engine* h) {
   if (h->device < 0)
     return fail(h, "engine was created without a device (planning only); no CPU fallback exists");
@@ -383,8 +394,7 @@ double adjoint_plan_seconds(const Plan& plan, const Model& m) {
 }
 
 int build_plans(qhbm_engine* h) {
-  if (h->plans_valid && h->adj_valid) return 0;
-  h->retained_U = 0;
+  if (h->plans_valid && h->adj_valid) return 0;  // (whoever invalidated them dropped the retained states and the VJP rows)
   if (!h->have_circuit) return fail(h, "qhbm_set_circuit has not been called");
   if (h->model.n_ops > kMaxOps) return fail(h, "too many observables (max 1024)");
   std::string err;
@@ -1329,7 +1339,7 @@ int qhbm_set_circuit(qhbm_engine* h, int n_qubits, int n_gates, const qhbm_gate*
   if (!build_plan(no_obs, h->opt_tile, h->opt_round, false, &probe, &err)) return fail(h, err);
   h->model = std::move(m);
   h->have_circuit = true;
-  h->plans_valid = false;
+  invalidate_plans(h);
   h->block_choice = -1;
   return 0;
 }
@@ -1407,7 +1417,7 @@ int qhbm_set_observables(qhbm_engine* h, int n_ops, const int32_t* term_offsets,
   }
   h->model.n_ops = n_ops;
   h->model.terms = std::move(terms);
-  h->plans_valid = false;
+  invalidate_plans(h);
   h->block_choice = -1;
   h->terms.release();
   return 0;
@@ -1416,21 +1426,21 @@ int qhbm_set_observables(qhbm_engine* h, int n_ops, const int32_t* term_offsets,
 int qhbm_set_option(qhbm_engine* h, const char* name, int64_t value) {
   if (!h || !name) return 1;
   const std::string k(name);
-  if (k == "tile_qubits") { h->opt_tile = int(value); h->plans_valid = false; h->block_choice = -1; }
-  else if (k == "round_qubits") { h->opt_round = int(value); h->plans_valid = false; }
+  if (k == "tile_qubits") { h->opt_tile = int(value); invalidate_plans(h); h->block_choice = -1; }
+  else if (k == "round_qubits") { h->opt_round = int(value); invalidate_plans(h); }
   else if (k == "force_general_kernels") h->opt_force_general = int(value);
-  else if (k == "full_diag_threshold") { h->opt_full_fwd = int(value); h->plans_valid = false; }
-  else if (k == "adjoint_full_diag_threshold") { h->opt_full_adj = int(value); h->plans_valid = false; }
-  else if (k == "adjoint_tile_qubits") { h->opt_adj_tile = int(value); h->plans_valid = false; }
-  else if (k == "adjoint_exchange") { h->opt_adj_exchange = int(value); h->plans_valid = false; }
-  else if (k == "x_two_shear") { h->opt_x_two_shear = value != 0; h->plans_valid = false; h->adj_cache.clear(); }
-  else if (k == "adjoint_relabel") { h->opt_adj_relabel = int(value); h->plans_valid = false; }
+  else if (k == "full_diag_threshold") { h->opt_full_fwd = int(value); invalidate_plans(h); }
+  else if (k == "adjoint_full_diag_threshold") { h->opt_full_adj = int(value); invalidate_plans(h); }
+  else if (k == "adjoint_tile_qubits") { h->opt_adj_tile = int(value); invalidate_plans(h); }
+  else if (k == "adjoint_exchange") { h->opt_adj_exchange = int(value); invalidate_plans(h); }
+  else if (k == "x_two_shear") { h->opt_x_two_shear = value != 0; invalidate_plans(h); h->adj_cache.clear(); }
+  else if (k == "adjoint_relabel") { h->opt_adj_relabel = int(value); invalidate_plans(h); }
   else if (k == "forward_pairs") h->opt_fwd_pair = int(value);
   else if (k == "shift_prefix_sharing") { h->opt_shift_prefix = int(value); h->shift_ready = false; }
   else if (k == "forward_values_from_observable") h->opt_fwd_values_obs = int(value);
-  else if (k == "adjoint_stop_early") { h->opt_adj_stop_early = int(value); h->plans_valid = false; }
-  else if (k == "adjoint_plan_search") { h->opt_adj_plan_search = int(value); h->plans_valid = false; }
-  else if (k == "wide_last_pass") { h->opt_wide_last = int(value); h->plans_valid = false; }
+  else if (k == "adjoint_stop_early") { h->opt_adj_stop_early = int(value); invalidate_plans(h); }
+  else if (k == "adjoint_plan_search") { h->opt_adj_plan_search = int(value); invalidate_plans(h); }
+  else if (k == "wide_last_pass") { h->opt_wide_last = int(value); invalidate_plans(h); }
   else if (k == "observable_xcd_states") h->opt_obs_xcd_states = int(value);
   else if (k == "observable_kernel") { h->opt_obs_kernel = int(value); h->block_choice = -1; }
   else if (k == "observable_split_rows") h->opt_obs_split_rows = value != 0;
@@ -1441,9 +1451,9 @@ int qhbm_set_option(qhbm_engine* h, const char* name, int64_t value) {
   else if (k == "multi_observable_values") h->opt_multi_values = int(value);
   else if (k == "gather_multi_values") h->opt_gather_multi = int(value);
   else if (k == "observable_far_windows") { h->opt_far_windows = int(value); h->terms.release(); h->model_uploaded = false; }
-  else if (k == "measure_tile_qubits") { h->opt_meas_tile = int(value); h->plans_valid = false; }
+  else if (k == "measure_tile_qubits") { h->opt_meas_tile = int(value); invalidate_plans(h); }
   else if (k == "values_from_observable") h->opt_values_from_obs = int(value);
-  else if (k == "cph_wave_bits") { h->opt_cph_wave_bits = int(value); h->plans_valid = false; }
+  else if (k == "cph_wave_bits") { h->opt_cph_wave_bits = int(value); invalidate_plans(h); }
   else if (k == "chunk_states") h->opt_chunk = value;
   else if (k == "workspace_budget_mb") h->opt_budget_mb = std::max<int64_t>(0, value);  // 0 = default
   else if (k == "profile_events") h->opt_profile = int(value);

@@ -257,6 +257,11 @@ class Engine:
       raise EngineError(self._lib.qhbm_last_error(self._h).decode())
 
   # ---- model -------------------------------------------------------------
+  def _setter_done(self):
+    """A setter that invalidates a plan drops the retained states (include/qhbm_engine.h): the token follows."""
+    if self.retained is not None and self.retained_states() == 0:
+      self.retained = None
+
   def set_circuit(self, n_qubits, gates, n_params):
     """gates: iterable of (kind, q0, q1, param_idx, scalar, offset[, global_shift])."""
     gates = list(gates)
@@ -272,6 +277,7 @@ class Engine:
       self.n_ops = 0
     self.n_qubits, self.n_params = int(n_qubits), int(n_params)
     self._grad_mask = None  # (qhbm_set_circuit resets the engine's mask)
+    self._setter_done()
 
   def set_observables(self, ops):
     """ops: list of ops, each a list of (coeff, x_mask, z_mask), qubit space."""
@@ -292,6 +298,7 @@ class Engine:
                                        cf.ctypes.data, xm.ctypes.data,
                                        zm.ctypes.data))
     self.n_ops = len(ops)
+    self._setter_done()
 
   def set_gradient_mask(self, needs_grad):
     """needs_grad: one truth value per parameter (None: all).  Frozen parameters get zero gradient entries and no
@@ -308,9 +315,11 @@ class Engine:
         raise EngineError(f"gradient mask of shape {mask.shape} for {self.n_params} parameters")
       self._check(self._lib.qhbm_set_gradient_mask(self._h, mask.ctypes.data, self.n_params))
     self._grad_mask = key
+    self._setter_done()
 
   def set_option(self, name, value):
     self._check(self._lib.qhbm_set_option(self._h, name.encode(), int(value)))
+    self._setter_done()
 
   # ---- introspection -------------------------------------------------------
   def num_passes(self):
