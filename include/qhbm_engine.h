@@ -375,6 +375,25 @@ int qhbm_gwg_sample(uint64_t* d_chain_states, int n_chains, int n_bits,
                     uint64_t seed, uint64_t step0, int64_t n_steps,
                     int8_t* d_out_samples, int32_t* d_out_accepted, void* stream);
 
+/* The table of ALL 2^n_bits energies of the same form by a fast Walsh-Hadamard transform: n 2^n additions
+ * instead of n_terms 2^n parity evaluations, and no bitstring table.  1 <= n_bits <= 30.
+ * qhbm_walsh_hadamard transforms d_data[2^n_bits] in place, unnormalised: H[y] = sum_m c[m] (-1)^popcount(y & m).
+ * qhbm_parity_table overwrites d_table[y] with sum_k d_thetas[k] * parity_k(bitstring y), where bitstring y holds its
+ * column q at bit n_bits-1-q of y (the row order of qhbm_statevector's amplitudes); column q is bit q of a mask.  Mask
+ * bits at or above n_bits are ignored, a zero mask is a constant term, equal masks add in ascending term order;
+ * n_terms == 0 gives zeros.
+ * qhbm_parity_table_vjp overwrites d_grad[k] with sum_y d_weights[y] * parity_k(bitstring y): d_weights is transformed
+ * into d_scratch (a second array of 2^n_bits floats, not d_weights) and never modified.
+ * The order of the additions is a function of n_bits alone: bit-identical from call to call; each output carries at
+ * most n_bits (+ the multiplicity of a mask) roundings.  No atomics, no allocation, no host synchronisation; they run on
+ * the current device and the given stream. */
+int qhbm_walsh_hadamard(float* d_data, int n_bits, void* stream);
+int qhbm_parity_table(const uint64_t* d_masks, const float* d_thetas, int n_terms, int n_bits,
+                      float* d_table, void* stream);
+int qhbm_parity_table_vjp(const uint64_t* d_masks, int n_terms, int n_bits,
+                          const float* d_weights, float* d_scratch,
+                          float* d_grad, void* stream);
+
 /* ---- introspection (tests, bench, DESIGN.md numbers) ------------------- */
 /* Number of HBM passes (kernel launches over the state) the scheduler emits
  * for one forward of the installed circuit + observables. */

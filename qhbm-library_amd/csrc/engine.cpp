@@ -1675,6 +1675,38 @@ int qhbm_gwg_sample(uint64_t* d_chain_states, int n_chains, int n_bits, const ui
   return 0;
 }
 
+int qhbm_walsh_hadamard(float* d_data, int n_bits, void* stream) {
+  if (n_bits < 1 || n_bits > 30) return fail(nullptr, "qhbm_walsh_hadamard: n_bits must be in [1, 30]");
+  if (!d_data) return fail(nullptr, "qhbm_walsh_hadamard: d_data is NULL");
+  hipError_t e = launch_walsh_hadamard(d_data, d_data, n_bits, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, std::string("qhbm_walsh_hadamard: ") + hipGetErrorString(e));
+  return 0;
+}
+
+int qhbm_parity_table(const uint64_t* d_masks, const float* d_thetas, int n_terms, int n_bits, float* d_table,
+                      void* stream) {
+  if (n_terms < 0) return fail(nullptr, "qhbm_parity_table: negative size");
+  if (n_bits < 1 || n_bits > 30) return fail(nullptr, "qhbm_parity_table: n_bits must be in [1, 30]");
+  if (!d_table) return fail(nullptr, "qhbm_parity_table: d_table is NULL");
+  if (n_terms > 0 && (!d_masks || !d_thetas)) return fail(nullptr, "qhbm_parity_table: d_masks / d_thetas is NULL");
+  hipError_t e = launch_parity_table(d_masks, d_thetas, n_terms, n_bits, d_table, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, std::string("qhbm_parity_table: ") + hipGetErrorString(e));
+  return 0;
+}
+
+int qhbm_parity_table_vjp(const uint64_t* d_masks, int n_terms, int n_bits, const float* d_weights, float* d_scratch,
+                          float* d_grad, void* stream) {
+  if (n_terms < 0) return fail(nullptr, "qhbm_parity_table_vjp: negative size");
+  if (n_bits < 1 || n_bits > 30) return fail(nullptr, "qhbm_parity_table_vjp: n_bits must be in [1, 30]");
+  if (!d_weights || !d_scratch) return fail(nullptr, "qhbm_parity_table_vjp: d_weights / d_scratch is NULL");
+  if (d_weights == d_scratch) return fail(nullptr, "qhbm_parity_table_vjp: d_scratch must not be d_weights");
+  if (n_terms > 0 && (!d_masks || !d_grad)) return fail(nullptr, "qhbm_parity_table_vjp: d_masks / d_grad is NULL");
+  hipError_t e = launch_parity_table_vjp(d_masks, n_terms, n_bits, d_weights, d_scratch, d_grad,
+                                         static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, std::string("qhbm_parity_table_vjp: ") + hipGetErrorString(e));
+  return 0;
+}
+
 int qhbm_sample(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, int n_shots,
                 uint64_t seed, int shift_gate, double shift, int8_t* d_out_samples, void* stream) {
   if (!h) return 1;

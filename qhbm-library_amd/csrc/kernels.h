@@ -155,6 +155,16 @@ size_t gwg_lds_bytes(int n_bits, int n_terms);
 hipError_t launch_gwg_sample(uint64_t* states, int n_chains, int n_bits, const uint64_t* masks, const float* thetas,
                              int n_terms, uint64_t seed, uint64_t step0, int64_t n_steps, int8_t* out, int32_t* accepted,
                              hipStream_t stream);
+// Walsh-Hadamard transform over float[2^n_bits] and the spin-parity energy tables built on it (parity_table.hip),
+// 1 <= n_bits <= 30.  dst = WHT(src): src == dst transforms in place, otherwise src is only read.  The table is zero
+// filled, the thetas scattered to the bit-reversed masks and transformed; its VJP transforms `weights` into `scratch`
+// and gathers grad[k] = scratch[rev(mask_k)].  wht_num_passes: launches over the array.
+int wht_num_passes(int n_bits);
+hipError_t launch_walsh_hadamard(const float* src, float* dst, int n_bits, hipStream_t stream);
+hipError_t launch_parity_table(const uint64_t* masks, const float* thetas, int n_terms, int n_bits, float* table,
+                               hipStream_t stream);
+hipError_t launch_parity_table_vjp(const uint64_t* masks, int n_terms, int n_bits, const float* weights, float* scratch,
+                                   float* grad, hipStream_t stream);
 // block_cum: n_states * 2^n / 1024 doubles of scratch.
 hipError_t launch_sample(const float2* psi, uint32_t n, int n_user, uint32_t n_states, double* block_cum,
                          uint32_t n_shots, uint64_t seed, uint32_t state0, int8_t* out, hipStream_t stream);

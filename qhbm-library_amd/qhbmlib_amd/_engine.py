@@ -39,7 +39,7 @@ ABI_SYMBOLS = (
     "qhbm_workspace_bytes", "qhbm_allocated_bytes", "qhbm_expectation", "qhbm_expectation_vjp",
     "qhbm_expectation_retain", "qhbm_expectation_vjp_retained", "qhbm_retained_states", "qhbm_state_gradients",
     "qhbm_expectation_jacobian", "qhbm_statevector", "qhbm_sample", "qhbm_sample_counts", "qhbm_program_vjps", "qhbm_parity_energy", "qhbm_parity_energy_vjp",
-    "qhbm_gwg_sample",
+    "qhbm_gwg_sample", "qhbm_walsh_hadamard", "qhbm_parity_table", "qhbm_parity_table_vjp",
     "qhbm_num_passes", "qhbm_describe_schedule",
     "qhbm_kernel_time_ms", "qhbm_traffic_model", "qhbm_flop_model", "qhbm_op_census", "qhbm_clock_probe", "qhbm_plan_builds",
     "qhbm_table_expectation", "qhbm_table_expectation_retain", "qhbm_table_expectation_vjp",
@@ -109,6 +109,9 @@ def load_library():
   lib.qhbm_parity_energy.argtypes = [vp, i64, i32, vp, vp, i32, vp, vp]
   lib.qhbm_parity_energy_vjp.argtypes = [vp, i64, i32, vp, i32, vp, vp, vp]
   lib.qhbm_gwg_sample.argtypes = [vp, i32, i32, vp, vp, i32, ctypes.c_uint64, ctypes.c_uint64, i64, vp, vp, vp]
+  lib.qhbm_walsh_hadamard.argtypes = [vp, i32, vp]
+  lib.qhbm_parity_table.argtypes = [vp, vp, i32, i32, vp, vp]
+  lib.qhbm_parity_table_vjp.argtypes = [vp, i32, i32, vp, vp, vp, vp]
   lib.qhbm_num_passes.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
   lib.qhbm_describe_schedule.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t]
   lib.qhbm_kernel_time_ms.argtypes = [
@@ -189,6 +192,85 @@ def parity_energy(thetas, bits, masks):
   if not bits.is_cuda:
     raise EngineError("parity_energy runs on the GPU: pass CUDA bitstrings (CPU tensors use the torch layers)")
   return _ParityEnergyFunction.apply(thetas, bits, masks)
+
+
+WHT_MAX_BITS = 30   # csrc/parity_table.hip kWhtMaxBits
+WHT_TILE_BITS = 14  # kWhtTileBits: up to here the transform is one launch
+WHT_ROW_BITS = 9    # kWhtRowBits: index bits every further pass adds
+
+
+def walsh_hadamard_passes(n_bits):
+  """Launches over the array of one transform of 2^n_bits floats (csrc/parity_table.hip wht_num_passes)."""
+  return 1 if n_bits <= WHT_TILE_BITS else 1 + -(-(n_bits - WHT_TILE_BITS) // WHT_ROW_BITS)
+
+
+def _table_bits(n_bits, what):
+  n_bits = int(n_bits)
+  if not 1 <= n_bits <= WHT_MAX_BITS:
+    raise EngineError(f"{what}: n_bits must be in [1, {WHT_MAX_BITS}], got {n_bits}")
+  return n_bits
+
+
+def walsh_hadamard_(tensor):
+  """Unnormalised Walsh-Hadamard transform of a contiguous float32 CUDA tensor of 2^n entries, IN PLACE
+  (qhbm_walsh_hadamard): H[y] = sum_m c[m] (-1)^popcount(y & m).  Returns the tensor."""
+  if not (torch.is_tensor(tensor) and tensor.is_cuda and tensor.dtype == torch.float32 and tensor.is_contiguous()):
+    raise EngineError("walsh_hadamard_ needs a contiguous float32 CUDA tensor")
+  size = tensor.numel()
+  if size < 2 or size & (size - 1):
+    raise EngineError(f"walsh_hadamard_ needs 2^n entries with 1 <= n <= {WHT_MAX_BITS}, got {size}")
+  n_bits = _table_bits(size.bit_length() - 1, "walsh_hadamard_")
+  with torch.cuda.device(tensor.device):
+    _check_global(load_library().qhbm_walsh_hadamard(
+        tensor.data_ptr(), n_bits, ctypes.c_void_p(torch.cuda.current_stream(tensor.device).cuda_stream)))
+  return tensor
+
+
+class _ParityTableFunction(torch.autograd.Function):
+  """table[y] = sum_k thetas[k] * parity_k(bitstring y) over all 2^n_bits bitstrings by a Walsh-Hadamard transform
+  (qhbm_parity_table); the backward is qhbm_parity_table_vjp on the upstream.  `masks` is an int64 CUDA tensor of
+  column masks; the table lives on its device."""
+
+  @staticmethod
+  def forward(ctx, thetas, masks, n_bits):
+    lib = load_library()
+    dev = masks.device
+    th = thetas.detach().to(device=dev, dtype=torch.float32).contiguous()
+    out = torch.empty((1 << n_bits,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+      _check_global(lib.qhbm_parity_table(
+          masks.data_ptr(), th.data_ptr(), masks.numel(), n_bits, out.data_ptr(),
+          ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    ctx.masks, ctx.n_bits = masks, n_bits
+    ctx.theta_device = thetas.device
+    return out
+
+  @staticmethod
+  def backward(ctx, upstream):
+    lib = load_library()
+    masks, n_bits = ctx.masks, ctx.n_bits
+    dev = masks.device
+    w = upstream.to(device=dev, dtype=torch.float32).contiguous()
+    scratch = torch.empty_like(w)
+    grad = torch.empty((masks.numel(),), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+      _check_global(lib.qhbm_parity_table_vjp(
+          masks.data_ptr(), masks.numel(), n_bits, w.data_ptr(), scratch.data_ptr(), grad.data_ptr(),
+          ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return grad.to(ctx.theta_device), None, None
+
+
+def parity_table(thetas, masks, n_bits):
+  """Differentiable (w.r.t. `thetas`) float32 CUDA table [2^n_bits] of the spin-parity energies of ALL bitstrings, row
+  y = the bitstring whose column q is bit n_bits-1-q of y (`energy_utils.all_bitstrings`), for int64 CUDA column `masks`:
+  n 2^n additions whatever the number of terms, and no bitstring table.  1 <= n_bits <= 30."""
+  n_bits = _table_bits(n_bits, "parity_table")
+  if not (torch.is_tensor(masks) and masks.is_cuda and masks.dtype == torch.int64):
+    raise EngineError("parity_table runs on the GPU: pass the column masks as an int64 CUDA tensor")
+  masks = masks.contiguous()
+  if masks.numel() != thetas.numel():
+    raise EngineError(f"parity_table: {masks.numel()} masks for {thetas.numel()} thetas")
+  return _ParityTableFunction.apply(thetas, masks, n_bits)
 
 
 GWG_LDS_MAX = 160 * 1024  # csrc/kernels.h kGwgLdsMax

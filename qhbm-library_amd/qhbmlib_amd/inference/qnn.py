@@ -286,7 +286,11 @@ class AnalyticQuantumInference(QuantumInference):
   circuit's qubits -- one streaming pass over the final states (`qhbm_table_expectation`), gradients by the adjoint
   sweep into the circuits and through the table into the energy's variables.  "all": every Hamiltonian goes through
   its table (one engine call whatever the number of Pauli shards).  Tables need n <= `max_table_qubits` (default 24: a
-  64-MiB table, 16 M energy rows), the adjoint gradient method, and no process group."""
+  64-MiB table, 16 M energy rows), the adjoint gradient method, and no process group.
+  `parity_tables`: how the table of a `PauliMixin` energy routed through its table is built.  "terms" (default): the
+  energy evaluated on all 2^n bitstrings; "transform": a Walsh-Hadamard transform of its coefficients
+  (`energy_utils.energy_table(method="transform")`), whose cost does not depend on the number of terms.
+  Other energies are not touched by it."""
 
   MAX_OPS_PER_CALL = 1024  # kMaxOps of the engine (csrc/program.h)
   ENERGY_TABLES = ("off", "general", "all")
@@ -295,11 +299,14 @@ class AnalyticQuantumInference(QuantumInference):
                device: Union[None, int] = None, gradient_method: int = _engine.GRAD_ADJOINT,
                process_group=None, max_cached_engines: int = 4, ordered_reduction: bool = False,
                check_consistency: bool = True, shard_weights=None, energy_tables: str = "off",
-               max_table_qubits: int = 24):
+               max_table_qubits: int = 24, parity_tables: str = "terms"):
     if energy_tables not in self.ENERGY_TABLES:
       raise ValueError(f"energy_tables must be one of {self.ENERGY_TABLES}, got {energy_tables!r}")
+    if parity_tables not in energy_utils.ENERGY_TABLE_METHODS:
+      raise ValueError(f"parity_tables must be one of {energy_utils.ENERGY_TABLE_METHODS}, got {parity_tables!r}")
     super().__init__(input_circuit, name)
     self.energy_tables = energy_tables
+    self.parity_tables = parity_tables
     self.max_table_qubits = int(max_table_qubits)
     if shard_weights is not None and ordered_reduction:
       raise ValueError("ordered_reduction=True (regression runs that compare rank counts) uses equal blocks only")
@@ -367,7 +374,9 @@ class AnalyticQuantumInference(QuantumInference):
                        "parameter-shift rule")
     # row y = the bitstring of amplitude index y (qubit 0 most significant), as the sampled path maps a shot outcome;
     # under tfq_compat_bit_order only the injector columns are permuted (_engine_bits), never the table
-    table = energy_utils.energy_table(observables.energy, n, self.max_table_qubits)
+    by_transform = self.parity_tables == "transform" and isinstance(observables.energy, energy.PauliMixin)
+    table = energy_utils.energy_table(observables.energy, n, self.max_table_qubits,
+                                      method="transform" if by_transform else "terms")
     bits = _engine_bits(total_circuit, unique_states)
     values = _row_of_tiled(symbol_values, total_circuit).to(torch.float32)
     flat_gates = total_circuit.pqc.flat_gates(qubits, list(symbol_names))

@@ -92,11 +92,54 @@ def all_bitstrings(n: int, device=None) -> torch.Tensor:
   return rows
 
 
-def energy_table(input_energy, n: int, max_qubits: int = 24) -> torch.Tensor:
+ENERGY_TABLE_METHODS = ("terms", "transform")
+
+
+def parity_transform_missing(input_energy, n: int) -> List[str]:
+  """What `energy_table(..., method="transform")` lacks for this energy (strings; empty: it can run): the transform is a
+  HIP kernel over the parity masks of a spin-parity energy and has no CPU fallback."""
+  from qhbmlib_amd import _engine  # pylint: disable=import-outside-toplevel
+  missing, sets = [], None
+  if hasattr(input_energy, "_parity_index_sets") and hasattr(input_energy, "post_process"):
+    try:
+      sets = list(input_energy._parity_index_sets())   # pylint: disable=protected-access
+    except NotImplementedError:
+      sets = None
+  if sets is None:
+    missing.append("a PauliMixin energy with parity masks (_parity_index_sets); this one is a " +
+                   type(input_energy).__name__)
+  device = next(iter(input_energy.parameters()), torch.zeros(())).device
+  if device.type != "cuda":
+    missing.append(f"the energy's variables on a CUDA device (they are on {device})")
+  if input_energy.num_bits != n:
+    missing.append(f"an energy over the table's {n} bits (it has {input_energy.num_bits})")
+  if n > _engine.WHT_MAX_BITS:
+    missing.append(f"at most {_engine.WHT_MAX_BITS} bits (the table has {n})")
+  return missing
+
+
+def parity_transform_table(input_energy, n: int) -> torch.Tensor:
+  """float32 [2^n] energies of a spin-parity energy in `all_bitstrings(n)` order by `_engine.parity_table`."""
+  from qhbmlib_amd import _engine  # pylint: disable=import-outside-toplevel
+  missing = parity_transform_missing(input_energy, n)
+  if missing:
+    raise ValueError("an energy table by the Walsh-Hadamard transform needs " + "; ".join(missing))
+  kernel = input_energy.post_process[0].kernel
+  return _engine.parity_table(kernel, input_energy._parity_masks(kernel.device), n)   # pylint: disable=protected-access
+
+
+def energy_table(input_energy, n: int, max_qubits: int = 24, method: str = "terms") -> torch.Tensor:
   """float32 [2^n]: E[y] = input_energy(row y of `all_bitstrings(n)`), the diagonal of the energy's operator in the
-  computational basis, evaluated on the device of the energy's variables and differentiable with respect to them."""
+  computational basis, evaluated on the device of the energy's variables and differentiable with respect to them.
+  `method`: "terms" (default) evaluates the energy on the bitstring table; "transform" builds the table of a spin-parity
+  energy (`BernoulliEnergy`, `KOBE`) by a Walsh-Hadamard transform of its coefficients -- it needs a
+  `PauliMixin` energy with parity masks, CUDA variables and `num_bits == n <= 30`, and raises `ValueError` otherwise."""
+  if method not in ENERGY_TABLE_METHODS:
+    raise ValueError(f"method must be one of {ENERGY_TABLE_METHODS}, got {method!r}")
   if n > max_qubits:
     raise ValueError(f"an energy table over {n} qubits has 2^{n} entries: above max_table_qubits = {max_qubits}")
+  if method == "transform":
+    return parity_transform_table(input_energy, n)
   device = next(iter(input_energy.parameters()), torch.zeros(())).device
   e = input_energy(all_bitstrings(n, device))
   if e.numel() != 1 << n or not (e.dim() == 1 or (e.dim() == 2 and e.shape[1] == 1)):

@@ -1,4 +1,4 @@
-"""Register / LDS / occupancy table of the pass, observable and Gibbs-With-Gradients kernels as hipcc reports them, and WHERE their spills sit
+"""Register / LDS / occupancy table of the pass, observable, Gibbs-With-Gradients and parity-table kernels as hipcc reports them, and WHERE their spills sit
 (developer tool and CPU test, no GPU needed):
     python scripts/kernel_resources.py            # the table, then every spill site with its loop context
 `check()` is what tests/test_scripts_cpu.py runs: a kernel the DEFAULT planner can select must not spill a VGPR at all and
@@ -45,7 +45,7 @@ def resource_rows():
       cur[m.group(1).strip()] = int(m.group(2))
   for r in rows:
     r["name"] = _demangle(r["mangled"])
-  return [r for r in rows if any(k in r["name"] for k in ("pass_", "apply_obs", "observable_blocks", "gwg_chain"))]
+  return [r for r in rows if any(k in r["name"] for k in ("pass_", "apply_obs", "observable_blocks", "gwg_chain", "wht_", "parity_scatter", "parity_gather"))]
 
 
 def assembly(src):
