@@ -160,14 +160,14 @@ struct qhbm_engine {
   DevBuf<float> state_grad, slot_factor, vals_tmp, upstream_tmp, phase_cs;
   DevBuf<ShiftPhase> shift_phases;  // gates with a cirq global_shift (qhbm_statevector restores their phases)
   int n_shift_phases = 0;
-  // parameter-shift batches: per-program coefficient buffers, shift tables, accumulators
+  // batches of shifted programs: per-program coefficient buffers, ONE set of shift tables (upload_shift_tables), accumulators
   DevBuf<float> coef_batch, shift_vals, shift_weight, vals_batch;
   DevBuf<int> shift_gates, shift_param;
-  DevBuf<int> shift_dst;             // execution order -> gate order of the shifted programs (prog_acc index)
-  std::vector<uint32_t> shift_group_end;  // programs (execution order) whose shifted gate sits in pass <= i end here
+  DevBuf<int> shift_dst;             // execution order -> the caller's order of the programs (ProgramOrder::dst)
+  ProgramOrder shift_order;          // the parameter-shift VJP's programs (valid while shift_ready)
   DevBuf<double> prog_acc;
   size_t coef_batch_programs = 0;  // copies of the forward plan's static words already in coef_batch
-  bool shift_ready = false;        // shift tables on the device match the model
+  bool shift_ready = false;        // the shift tables on the device are the parameter-shift VJP's and match the model
   bool shift_tables_from_obs = false;  // ... and were ordered for values taken from the observable kernel (or in the passes)
   uint32_t shift_programs = 0, shift_gate_count = 0;
   DevBuf<float> tile_grad;              // [chunk states * tiles, slots of one adjoint pass]
@@ -177,12 +177,11 @@ struct qhbm_engine {
   DevBuf<double> block_cum;
   DevBuf<int> param_slot_begin, param_slots;
   // qhbm_program_vjps: per-element copies of bitstrings and upstream rows, the base program's states of a shared prefix,
-  // the gradient rows of the programs in flight, fp64 value accumulators, the programs' shift tables
+  // the gradient rows of the programs in flight, fp64 value accumulators
   DevBuf<int8_t> pv_bits;
-  DevBuf<float> pv_upstream, pv_rows, pv_shifts;
+  DevBuf<float> pv_upstream, pv_rows;
   DevBuf<float2> pv_base;
   DevBuf<double> pv_vals;
-  DevBuf<int> pv_gates, pv_dst;
   // energy tables (energy_table.hip): per (state, y-block) value partials, per-group folds of the table gradient, the
   // fold a chunk boundary cut, the running fp64 table gradient
   DevBuf<double> tab_vpart, tab_gpart, tab_carry, tab_gsum;
@@ -219,8 +218,7 @@ size_t own_bytes(const qhbm_engine* h) {
          buf_bytes(h->global_terms) + buf_bytes(h->obs_groups) + buf_bytes(h->far[0].terms) + buf_bytes(h->far[0].groups) +
          buf_bytes(h->far[1].terms) + buf_bytes(h->far[1].groups) + buf_bytes(h->far[2].terms) + buf_bytes(h->far[2].groups) + buf_bytes(h->obs_bterms) + buf_bytes(h->obs_bgroups) + buf_bytes(h->op_scale) + buf_bytes(h->op_inv_scale) +
          buf_bytes(h->param_slot_begin) + buf_bytes(h->param_slots) + buf_bytes(h->pv_bits) + buf_bytes(h->pv_upstream) +
-         buf_bytes(h->pv_rows) + buf_bytes(h->pv_shifts) + buf_bytes(h->pv_base) + buf_bytes(h->pv_vals) +
-         buf_bytes(h->pv_gates) + buf_bytes(h->pv_dst) + buf_bytes(h->tab_vpart) + buf_bytes(h->tab_gpart) +
+         buf_bytes(h->pv_rows) + buf_bytes(h->pv_base) + buf_bytes(h->pv_vals) + buf_bytes(h->tab_vpart) + buf_bytes(h->tab_gpart) +
          buf_bytes(h->tab_carry) + buf_bytes(h->tab_gsum) + plan_bytes(h->fwd) + plan_bytes(h->adj) + [&] {
            size_t cached = 0;  // backward plans of other gradient masks, kept with their device copies (adj_cache)
            for (const auto& kv : h->adj_cache) cached += plan_bytes(*kv.second);
@@ -902,22 +900,44 @@ bool forward_values_from_observable(const qhbm_engine* h) {
   return wide_observables(h) && h->fwd.plan.passes.size() > 1;
 }
 
-// `skip_measure`: the caller takes the values from lambda = O psi (value_mode): measurement groups
-// are ignored, measurement-only passes and the wide-term kernel are not launched.
+// The coefficients of one plan for this call: exponents to matrices and phases (gate `gate`'s exponent moved by
+// `shift`; -1: none), then the diagonal tables of its records.
+int prepare_coefs(qhbm_engine* h, DevicePlan& d, const float* d_params, int gate, double shift, hipStream_t stream) {
+  HIPCHK(launch_prep_coefs(d.jobs.p, int(d.plan.jobs.size()), d_params, d.coef.p, gate, shift, stream));
+  HIPCHK(launch_combine_diag(d.coef.p, d.rec_offsets.p, int(d.plan.record_offsets.size()), 1u, 0u, stream));
+  return 0;
+}
+
+// The arguments of forward pass i: the ONE place where its flags are composed.  `skip_measure`: the caller takes the
+// values from the observable kernel, or takes none -- measurement groups are ignored (and the callers launch neither
+// the measurement-only passes nor the wide-term kernel).  A pass stores its tiles unless it only measures, or completes
+// the circuit with nobody left to read the final state: `keep_state` (lambda = O psi, sampling, a retained batch), a
+// measurement-only pass or the global-term measurement behind it.  `prog_states` > 0: element e runs program
+// e / prog_states on its own copy of the coefficients, `coef_stride` floats apart (PassArgs::prog_states).
+PassArgs forward_pass_args(const qhbm_engine* h, size_t i, bool keep_state, bool skip_measure, uint32_t prog_states = 0,
+                           uint32_t coef_stride = 0) {
+  const Plan& plan = h->fwd.plan;
+  const Pass& p = plan.passes[i];
+  bool read_after = keep_state || !plan.global_terms.empty();  // (global terms are measured on the final state in HBM)
+  for (const Pass& q : plan.passes) read_after |= q.is_measure_only;
+  PassArgs a = h->fwd.args[i];
+  a.flags = p.flags & (PASS_INIT_BASIS | PASS_GENERAL | PASS_NO_ZERO_FILL);
+  if (h->opt_force_general) a.flags |= PASS_GENERAL;
+  if (skip_measure) a.flags |= PASS_SKIP_MEASURE;
+  if (!p.is_measure_only && (!p.completes_circuit || read_after)) a.flags |= PASS_STORE;
+  a.prog_states = prog_states;
+  a.coef_stride = coef_stride;
+  return a;
+}
+
+// Forward passes for one chunk (`keep_state`, `skip_measure`: forward_pass_args).
 int run_forward_chunk(qhbm_engine* h, const int8_t* d_bits, uint32_t s0, uint32_t cs, bool keep_state,
                       hipStream_t stream, bool skip_measure = false) {
   DevicePlan& d = h->fwd;
-  const size_t np = d.plan.passes.size();
-  bool measure_only_after = !d.plan.global_terms.empty();  // they read the final state from HBM
-  for (const Pass& p : d.plan.passes) measure_only_after |= p.is_measure_only;
-  for (size_t i = 0; i < np; ++i) {
+  for (size_t i = 0; i < d.plan.passes.size(); ++i) {
     const Pass& p = d.plan.passes[i];
     if (skip_measure && p.is_measure_only) continue;
-    PassArgs a = d.args[i];
-    a.flags = p.flags & (PASS_INIT_BASIS | PASS_GENERAL | PASS_NO_ZERO_FILL);
-    if (h->opt_force_general) a.flags |= PASS_GENERAL;
-    if (skip_measure) a.flags |= PASS_SKIP_MEASURE;
-    if (!p.is_measure_only && (!p.completes_circuit || keep_state || measure_only_after)) a.flags |= PASS_STORE;
+    const PassArgs a = forward_pass_args(h, i, keep_state, skip_measure);
     hipEvent_t* ev = timer_begin(h, 0, stream);
     // dense lean passes without a measurement to take: two states per workgroup, tiles in registers
     const bool pair = h->opt_fwd_pair && cs >= 2 && !(a.flags & (PASS_INIT_BASIS | PASS_GENERAL)) && a.zero_mask == 0 &&
@@ -980,9 +1000,7 @@ int forward(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, 
             int shift_gate, double shift, hipStream_t stream) {
   DevicePlan& d = h->fwd;
   h->retained_U = 0;
-  HIPCHK(launch_prep_coefs(d.jobs.p, int(d.plan.jobs.size()), d_params, d.coef.p, shift_gate,
-                           shift, stream));
-  HIPCHK(launch_combine_diag(d.coef.p, d.rec_offsets.p, int(d.plan.record_offsets.size()), 1u, 0u, stream));
+  if (int rc = prepare_coefs(h, d, d_params, shift_gate, shift, stream)) return rc;
   if (int rc = values_begin(h, U, stream)) return rc;
   const uint32_t cs = chunk_states(h, U);
   if (int rc = ensure_state_buffers(h, cs, false)) return rc;
@@ -1103,10 +1121,8 @@ int adjoint_sweep(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_pa
   h->retained_U = 0;
   h->state_grad_U = 0;
   const uint32_t n_slots = uint32_t(b.plan.slot_gate.size());
-  HIPCHK(launch_prep_coefs(f.jobs.p, int(f.plan.jobs.size()), d_params, f.coef.p, -1, 0.0, stream));
-  HIPCHK(launch_combine_diag(f.coef.p, f.rec_offsets.p, int(f.plan.record_offsets.size()), 1u, 0u, stream));
-  HIPCHK(launch_prep_coefs(b.jobs.p, int(b.plan.jobs.size()), d_params, b.coef.p, -1, 0.0, stream));
-  HIPCHK(launch_combine_diag(b.coef.p, b.rec_offsets.p, int(b.plan.record_offsets.size()), 1u, 0u, stream));
+  if (int rc = prepare_coefs(h, f, d_params, -1, 0.0, stream)) return rc;
+  if (int rc = prepare_coefs(h, b, d_params, -1, 0.0, stream)) return rc;
   if (int rc = values_begin(h, U, stream)) return rc;
   HIPCHK(h->state_grad.reserve(size_t(U) * std::max<uint32_t>(n_slots, 1)));
   HIPCHK(launch_zero_fill(h->state_grad.p, size_t(U) * std::max<uint32_t>(n_slots, 1) * sizeof(float), stream));
@@ -1135,55 +1151,138 @@ int check_call(qhbm_engine* h, int U) {
   return upload_model(h);
 }
 
-// Parameter shift with a shared prefix.  A shifted program differs from the base program in the coefficients of ONE gate;
-// the passes in front of the first pass that reads them compute, state by state, the bits the base program computes.
-// first_dependent_pass()[g] = that pass for gate g (the pass count for a gate no record depends on); `first_measuring` =
-// the first pass with a measurement op (a program must not start behind it: a pass measures into the program's own
-// accumulators).  Record ranges come from the pass programs (OP_ROUND: n_instances records from its first record;
-// OP_GATE2: a 4 x 4 matrix), jobs from the plan (CoefJob::gate writes at CoefJob::out_off).  Sound only on plans whose
-// first pass has PASS_NO_ZERO_FILL: a program that starts at pass k > 0 loads only the tiles pass k launches, and on a
-// zero-filling plan the others must already hold zeros of its own state (both callers check the flag).
-std::vector<int> first_dependent_pass(const Plan& plan, size_t n_gates, int* first_measuring) {
-  const RecordLayout L(plan.R, false);
-  struct Range { uint32_t lo, hi; int pass; };
-  std::vector<Range> ranges;
-  const int n_pass = int(plan.passes.size());
-  *first_measuring = n_pass;
-  for (int i = 0; i < n_pass; ++i) {
-    const std::vector<uint32_t>& prog = plan.passes[size_t(i)].prog;
-    size_t pc = 0;
-    while (pc < prog.size()) {
-      const uint32_t w0 = prog[pc], opc = w0 & 0xffu;
-      if (opc == OP_END) break;
-      if (opc == OP_ROUND) {
-        const uint32_t n_inst = (w0 & ~kRoundNoBarrier) >> 8, rec = prog[pc + 2];
-        ranges.push_back(Range{rec, rec + n_inst * uint32_t(L.words()), i});
-        pc += kRoundWords;
-      } else if (opc == OP_GATE2) {
-        ranges.push_back(Range{prog[pc + 2], prog[pc + 2] + 32u, i});
-        pc += kGate2Words;
-      } else if (opc == OP_MEASURE_WHT) {
-        *first_measuring = std::min(*first_measuring, i);
-        pc += size_t(kWhtHeaderWords) + size_t(w0 >> 8) * kMeasTermWords;
-      } else if (opc == OP_MEASURE) {
-        const uint32_t n_groups = w0 >> 8;
-        if (n_groups) *first_measuring = std::min(*first_measuring, i);
-        pc += 1;
-        for (uint32_t g = 0; g < n_groups && pc + 1 < prog.size(); ++g) pc += 2u + size_t(prog[pc + 1]) * kMeasTermWords;
-      } else {
-        return std::vector<int>(n_gates, 0);  // an opcode this walk does not know: share nothing
-      }
+// ---- batches of (state, shifted program) pairs: qhbm_expectation_vjp(parameter shift), qhbm_program_vjps and
+// qhbm_sample_counts.  The pairs are the ELEMENTS of a launch set: Uc states x Pc programs, element e = program
+// e / c on state e % c, every program on its own copy of the coefficient buffer.  Programs run in the order of
+// schedule.h order_programs(); the programs of group k start at pass k from the base program's state after passes < k.
+
+// The shift tables of a batch in execution order.  ONE set serves every caller: the parameter-shift VJP keeps its own
+// across calls (shift_ready: no synchronisation and no copy on a repeated call, so a captured step stays capturable), the
+// other callers overwrite them.
+int upload_shift_tables(qhbm_engine* h, const ProgramOrder& order, const int* gates, const float* shifts, hipStream_t s) {
+  std::vector<int> sg(order.dst.size());
+  std::vector<float> sv(order.dst.size());
+  for (size_t q = 0; q < sg.size(); ++q) {
+    sg[q] = std::max(gates[order.dst[q]], -1);  // any negative value = the unshifted circuit
+    sv[q] = shifts[order.dst[q]];
+  }
+  h->shift_ready = false;
+  HIPCHK(hipStreamSynchronize(s));  // synchronous copies into buffers an earlier call on this stream may still read
+  HIPCHK(h->shift_gates.upload(sg));
+  HIPCHK(h->shift_vals.upload(sv));
+  HIPCHK(h->shift_dst.upload(order.dst));
+  return 0;
+}
+
+// Launch-set geometry.  `buffers`: state-sized buffers per element -- 1 (psi), or 2 (psi and lambda: the backward passes
+// run on the elements too, and their grids count).  `grid_cap`: some kernel of the caller puts the elements on a grid
+// dimension of at most 65535.  Sharing takes room for Uc base states on top.  `caps_bound_base`: those count against
+// the element caps as well as against the memory budget -- the parameter-shift VJP has always cut its sets that way
+// ("chunk_states" = 5: 2 states x 1 program + 2 base states) and qhbm_program_vjps against the budget alone; each keeps
+// its cut, so each issues the launches it always did.
+struct LaunchSets {
+  uint32_t stride;  // floats between the coefficient copies of two programs
+  uint32_t Uc, Pc;
+  bool share;
+};
+LaunchSets launch_set_geometry(qhbm_engine* h, int U, uint32_t n_prog, const ProgramOrder& order, int buffers, bool grid_cap,
+                               bool caps_bound_base) {
+  LaunchSets g;
+  g.stride = uint32_t((h->fwd.plan.coef_init.size() + 64 + 63) / 64 * 64);
+  const size_t states_cap = std::max<size_t>(1, budget_bytes(h) / state_bytes(h)), B = size_t(buffers);
+  uint32_t max_nl = 0;
+  for (const PassArgs& a : h->fwd.args) max_nl = std::max(max_nl, a.n_nonlocal);
+  if (buffers == 2)
+    for (const PassArgs& a : h->adj.args) max_nl = std::max(max_nl, a.n_nonlocal);
+  size_t el_cap = std::max<size_t>(1, states_cap / B);
+  el_cap = std::min<size_t>(el_cap, (size_t(1) << 30) >> max_nl);                             // grid.x = elements << n_nonlocal
+  el_cap = std::min<size_t>(el_cap, (size_t(2) << 30) / (size_t(g.stride) * sizeof(float)));  // <= 2 GiB of coefficient copies
+  if (grid_cap) el_cap = std::min<size_t>(el_cap, 65535);
+  if (h->opt_chunk > 0) el_cap = std::min<size_t>(el_cap, size_t(h->opt_chunk));
+  el_cap = std::max<size_t>(el_cap, 1);
+  const size_t pool = caps_bound_base ? std::min(states_cap, el_cap) : states_cap;
+  g.share = order.shares && pool >= B + 1;  // a buffer of base states beside one element, and a pass to skip
+  g.Uc = uint32_t(std::min<size_t>(size_t(U), g.share ? std::max<size_t>(1, std::min(el_cap, pool / (B + 1))) : el_cap));
+  g.Pc = uint32_t(std::max<size_t>(1, std::min<size_t>(n_prog, std::min(el_cap, (pool - (g.share ? g.Uc : 0)) / B) / g.Uc)));
+  return g;
+}
+
+// coef_batch holds the forward plan's static words for Pc programs.
+int grow_coef_batch(qhbm_engine* h, const LaunchSets& g, hipStream_t s) {
+  if (h->coef_batch_programs >= g.Pc) return 0;
+  HIPCHK(h->coef_batch.reserve(size_t(g.Pc) * g.stride));
+  HIPCHK(launch_replicate(h->fwd.coef.p, h->coef_batch.p, uint32_t(h->fwd.plan.coef_init.size()), g.stride, g.Pc, s));
+  h->coef_batch_programs = g.Pc;
+  return 0;
+}
+
+// What the passes of a launch set do with states and values (`keep_state`, `skip_measure`: forward_pass_args).
+// `takes_values` false is qhbm_sample_counts: it reads no value, so its sets never zeroed the accumulators, and its passes
+// never entered the profile (qhbm_kernel_time_ms counts what it always counted).
+struct LaunchSetPolicy {
+  bool keep_state, skip_measure, takes_values;
+};
+
+// The forward launches of one launch set: programs [q0, q0 + nq) of group k on states [s0, s0 + c) -- their
+// coefficients, the passes from k on (the first one loads the base program's states from `base` when k > 0), the
+// global-term measurement.  The final states are elements 0 .. nq * c of psi, the values rows 0 .. nq * c of vals64.
+int run_launch_set(qhbm_engine* h, const int8_t* d_bits, const float* d_params, const LaunchSets& g, uint32_t q0, uint32_t nq,
+                   size_t k, uint32_t s0, uint32_t c, const float2* base, LaunchSetPolicy pol, hipStream_t s) {
+  DevicePlan& d = h->fwd;
+  const uint32_t ne = nq * c, T = uint32_t(h->model.n_ops);
+  HIPCHK(launch_prep_coefs_batch(d.jobs.p, int(d.plan.jobs.size()), d_params, h->coef_batch.p, h->shift_gates.p + q0,
+                                 h->shift_vals.p + q0, nq, g.stride, s));
+  HIPCHK(launch_combine_diag(h->coef_batch.p, d.rec_offsets.p, int(d.plan.record_offsets.size()), nq, g.stride, s));
+  if (pol.takes_values) HIPCHK(launch_zero_fill(h->vals64.p, size_t(ne) * T * sizeof(unsigned long long), s));
+  const float2* src = k > 0 ? base : nullptr;
+  for (size_t i = k; i < d.plan.passes.size(); ++i) {
+    const Pass& p = d.plan.passes[i];
+    if (pol.skip_measure && p.is_measure_only) continue;
+    const PassArgs a = forward_pass_args(h, i, pol.keep_state, pol.skip_measure, c, g.stride);
+    hipEvent_t* ev = pol.takes_values ? timer_begin(h, 0, s) : nullptr;
+    HIPCHK(launch_pass_fwd(p.K, d.plan.R, a, ne, h->psi.p, d_bits, h->model.n, d.prog.p, d.tables.p, h->coef_batch.p,
+                           h->op_scale.p, h->vals64.p, s0, s, src));
+    timer_end(ev, s);
+    src = nullptr;
+  }
+  if (!pol.skip_measure && !d.plan.global_terms.empty())
+    HIPCHK(launch_measure_global(h->psi.p, uint32_t(d.plan.n_eff), ne, h->global_terms.p,
+                                 uint32_t(d.plan.global_terms.size()), h->op_scale.p, h->vals64.p, T, 0u, s));
+  return 0;
+}
+
+// The base program's states [s0, s0 + c) in `base` advance by pass k, on the base program's coefficients (its values
+// are not taken here).
+int advance_base(qhbm_engine* h, const int8_t* d_bits, size_t k, uint32_t s0, uint32_t c, float2* base, hipStream_t s) {
+  DevicePlan& d = h->fwd;
+  const PassArgs a = forward_pass_args(h, k, true, true);
+  hipEvent_t* ev = timer_begin(h, 0, s);
+  HIPCHK(launch_pass_fwd(d.plan.passes[k].K, d.plan.R, a, c, base, d_bits, h->model.n, d.prog.p, d.tables.p, d.coef.p,
+                         h->op_scale.p, h->vals64.p, s0, s));
+  timer_end(ev, s);
+  return 0;
+}
+
+// Programs [qa, qb) (execution order) on states [s0, s0 + c): group by group, at most Pc programs per launch set;
+// `after(q0, nq)` is the caller's own work on the set's final states.  Without sharing the range is one group that
+// starts at pass 0.  The base program advances by pass k while a later program of the range needs it.
+template <typename After>
+int run_program_groups(qhbm_engine* h, const int8_t* d_bits, const float* d_params, const LaunchSets& g,
+                       const ProgramOrder& order, uint32_t qa, uint32_t qb, uint32_t s0, uint32_t c, float2* base,
+                       LaunchSetPolicy pol, hipStream_t s, After&& after) {
+  const std::vector<Pass>& passes = h->fwd.plan.passes;
+  for (size_t k = 0; k < (g.share ? passes.size() : size_t(1)); ++k) {
+    const uint32_t lo = std::max(g.share && k ? order.group_end[k - 1] : 0u, qa);
+    const uint32_t hi = std::min(g.share ? order.group_end[k] : qb, qb);
+    for (uint32_t q0 = lo; q0 < hi; q0 += g.Pc) {
+      const uint32_t nq = std::min<uint32_t>(g.Pc, hi - q0);
+      if (int rc = run_launch_set(h, d_bits, d_params, g, q0, nq, k, s0, c, base, pol, s)) return rc;
+      if (int rc = after(q0, nq)) return rc;
     }
+    if (g.share && order.group_end[k] < qb && !passes[k].is_measure_only)
+      if (int rc = advance_base(h, d_bits, k, s0, c, base, s)) return rc;
   }
-  std::vector<int> first(n_gates, n_pass);
-  for (const CoefJob& j : plan.jobs) {
-    if (j.gate < 0 || size_t(j.gate) >= n_gates) continue;
-    int pass = 0;  // (a job whose record no pass claims: share nothing for its gate)
-    for (const Range& r : ranges)
-      if (uint32_t(j.out_off) >= r.lo && uint32_t(j.out_off) < r.hi) { pass = r.pass; break; }
-    first[size_t(j.gate)] = std::min(first[size_t(j.gate)], pass);
-  }
-  return first;
+  return 0;
 }
 
 // ---- energy tables: E = sum_y table[y] |y><y| (a general BitstringEnergy's modular Hamiltonian) ----
@@ -1224,8 +1323,7 @@ int table_forward(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_pa
   DevicePlan& d = h->fwd;
   h->retained_U = 0;
   if (retain && adjoint_chunk_states(h, U) < uint32_t(U)) retain = false;  // the batch does not fit one backward chunk
-  HIPCHK(launch_prep_coefs(d.jobs.p, int(d.plan.jobs.size()), d_params, d.coef.p, -1, 0.0, s));
-  HIPCHK(launch_combine_diag(d.coef.p, d.rec_offsets.p, int(d.plan.record_offsets.size()), 1u, 0u, s));
+  if (int rc = prepare_coefs(h, d, d_params, -1, 0.0, s)) return rc;
   const uint32_t cs = retain ? uint32_t(U) : chunk_states(h, U);
   if (int rc = ensure_state_buffers(h, cs, retain)) return rc;
   if (int rc = reserve_table_scratch(h, cs, false)) return rc;
@@ -1252,12 +1350,9 @@ int table_vjp(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params
   h->retained_U = 0;  // (the backward sweep un-applies psi in place: retained states are consumed)
   h->state_grad_U = 0;
   const uint32_t n_slots = uint32_t(b.plan.slot_gate.size());
-  if (!retained) {
-    HIPCHK(launch_prep_coefs(f.jobs.p, int(f.plan.jobs.size()), d_params, f.coef.p, -1, 0.0, s));
-    HIPCHK(launch_combine_diag(f.coef.p, f.rec_offsets.p, int(f.plan.record_offsets.size()), 1u, 0u, s));
-  }
-  HIPCHK(launch_prep_coefs(b.jobs.p, int(b.plan.jobs.size()), d_params, b.coef.p, -1, 0.0, s));
-  HIPCHK(launch_combine_diag(b.coef.p, b.rec_offsets.p, int(b.plan.record_offsets.size()), 1u, 0u, s));
+  if (!retained)
+    if (int rc = prepare_coefs(h, f, d_params, -1, 0.0, s)) return rc;
+  if (int rc = prepare_coefs(h, b, d_params, -1, 0.0, s)) return rc;
   HIPCHK(h->state_grad.reserve(size_t(U) * std::max<uint32_t>(n_slots, 1)));
   HIPCHK(launch_zero_fill(h->state_grad.p, size_t(U) * std::max<uint32_t>(n_slots, 1) * sizeof(float), s));
   const uint32_t cs = retained ? uint32_t(U) : adjoint_chunk_states(h, U);
@@ -1507,8 +1602,7 @@ int qhbm_expectation_retain(qhbm_engine* h, const int8_t* d_bits, int U, const f
     return forward(h, d_bits, U, d_params, d_out, -1, 0.0, s);
   DevicePlan& d = h->fwd;
   h->retained_U = 0;
-  HIPCHK(launch_prep_coefs(d.jobs.p, int(d.plan.jobs.size()), d_params, d.coef.p, -1, 0.0, s));
-  HIPCHK(launch_combine_diag(d.coef.p, d.rec_offsets.p, int(d.plan.record_offsets.size()), 1u, 0u, s));
+  if (int rc = prepare_coefs(h, d, d_params, -1, 0.0, s)) return rc;
   if (int rc = values_begin(h, U, s)) return rc;
   if (int rc = ensure_state_buffers(h, uint32_t(U), true)) return rc;  // psi AND lambda, so psi is not moved later
   const bool vm = value_mode(h), mv = multi_value_mode(h);
@@ -1535,8 +1629,7 @@ int qhbm_expectation_vjp_retained(qhbm_engine* h, const int8_t* d_bits, int U, c
   h->retained_U = 0;  // the backward sweep un-applies psi in place: the state is consumed
   h->state_grad_U = 0;
   const uint32_t n_slots = uint32_t(b.plan.slot_gate.size());
-  HIPCHK(launch_prep_coefs(b.jobs.p, int(b.plan.jobs.size()), d_params, b.coef.p, -1, 0.0, s));
-  HIPCHK(launch_combine_diag(b.coef.p, b.rec_offsets.p, int(b.plan.record_offsets.size()), 1u, 0u, s));
+  if (int rc = prepare_coefs(h, b, d_params, -1, 0.0, s)) return rc;
   HIPCHK(h->state_grad.reserve(size_t(U) * std::max<uint32_t>(n_slots, 1)));
   HIPCHK(launch_zero_fill(h->state_grad.p, size_t(U) * std::max<uint32_t>(n_slots, 1) * sizeof(float), s));
   if (h->retained_mu) {  // lambda = O psi (unweighted) was computed with the values: weight the rows instead
@@ -1573,8 +1666,7 @@ int qhbm_statevector(qhbm_engine* h, const int8_t* d_bits, int U, const float* d
   hipStream_t s = static_cast<hipStream_t>(stream);
   DevicePlan& d = h->fwd;
   h->retained_U = 0;
-  HIPCHK(launch_prep_coefs(d.jobs.p, int(d.plan.jobs.size()), d_params, d.coef.p, -1, 0.0, s));
-  HIPCHK(launch_combine_diag(d.coef.p, d.rec_offsets.p, int(d.plan.record_offsets.size()), 1u, 0u, s));
+  if (int rc = prepare_coefs(h, d, d_params, -1, 0.0, s)) return rc;
   // expectation values of installed observables are a by-product; they stay in the fixed-point scratch
   if (int rc = values_begin(h, U, s)) return rc;
   const uint32_t cs = chunk_states(h, U);
@@ -1722,8 +1814,7 @@ int qhbm_sample(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_para
   hipStream_t s = static_cast<hipStream_t>(stream);
   DevicePlan& d = h->fwd;
   h->retained_U = 0;
-  HIPCHK(launch_prep_coefs(d.jobs.p, int(d.plan.jobs.size()), d_params, d.coef.p, shift_gate, shift, s));
-  HIPCHK(launch_combine_diag(d.coef.p, d.rec_offsets.p, int(d.plan.record_offsets.size()), 1u, 0u, s));
+  if (int rc = prepare_coefs(h, d, d_params, shift_gate, shift, s)) return rc;
   if (int rc = values_begin(h, U, s)) return rc;
   const uint32_t cs = std::min<uint32_t>(chunk_states(h, U), 65535u);
   if (int rc = ensure_state_buffers(h, cs, false)) return rc;
@@ -1758,58 +1849,26 @@ int qhbm_sample_counts(qhbm_engine* h, const int8_t* d_bits, int U, const float*
   DevicePlan& d = h->fwd;
   h->retained_U = 0;
   h->state_grad_U = 0;
-  h->shift_ready = false;  // the shift tables below replace those of the parameter-shift VJP
-  {
-    std::vector<int> sg(shift_gates, shift_gates + n_programs);
-    for (int& g : sg) g = std::max(g, -1);  // any negative value = the unshifted circuit
-    std::vector<float> sv(shifts, shifts + n_programs);
-    HIPCHK(hipStreamSynchronize(s));  // synchronous copies into buffers an earlier call on this stream may still read
-    HIPCHK(h->shift_gates.upload(sg));
-    HIPCHK(h->shift_vals.upload(sv));
-  }
+  // every program from pass 0, in the caller's order (no prefix sharing here)
   const uint32_t n_prog = uint32_t(n_programs), n_eff = uint32_t(d.plan.n_eff);
-  const uint32_t stride = uint32_t((d.plan.coef_init.size() + 64 + 63) / 64 * 64);
-  // launch-set geometry as in the parameter-shift VJP: Uc states x Pc programs per set
-  size_t cap = std::max<size_t>(1, budget_bytes(h) / state_bytes(h));
-  uint32_t max_nl = 0;
-  for (const PassArgs& a : d.args) max_nl = std::max(max_nl, a.n_nonlocal);
-  cap = std::min<size_t>(cap, (size_t(1) << 30) >> max_nl);
-  cap = std::min<size_t>(cap, (size_t(2) << 30) / (size_t(stride) * sizeof(float)));
-  cap = std::min<size_t>(cap, 65535);  // grid.y of the per-element kernels
-  if (h->opt_chunk > 0) cap = std::min<size_t>(cap, size_t(h->opt_chunk));
-  const uint32_t Uc = uint32_t(std::min<size_t>(size_t(U), cap));
-  const uint32_t Pc = uint32_t(std::max<size_t>(1, std::min<size_t>(n_prog, cap / Uc)));
-  if (int rc = ensure_state_buffers(h, Uc * Pc, false)) return rc;
-  HIPCHK(h->block_cum.reserve((size_t(Uc) * Pc) << (n_eff - 10)));
-  if (int rc = values_begin(h, int(Uc * Pc), s)) return rc;  // measurement by-products land in the fixed-point scratch
-  if (h->coef_batch_programs < Pc) {
-    HIPCHK(h->coef_batch.reserve(size_t(Pc) * stride));
-    HIPCHK(launch_replicate(d.coef.p, h->coef_batch.p, uint32_t(d.plan.coef_init.size()), stride, Pc, s));
-    h->coef_batch_programs = Pc;
-  }
+  const ProgramOrder order = order_programs(d.plan, h->model.gates.size(), shift_gates, n_prog, false, true);
+  if (int rc = upload_shift_tables(h, order, shift_gates, shifts, s)) return rc;
+  const LaunchSets g = launch_set_geometry(h, U, n_prog, order, 1, true, false);
+  if (int rc = ensure_state_buffers(h, g.Uc * g.Pc, false)) return rc;
+  HIPCHK(h->block_cum.reserve((size_t(g.Uc) * g.Pc) << (n_eff - 10)));
+  if (int rc = values_begin(h, int(g.Uc * g.Pc), s)) return rc;  // measurement by-products land in the fixed-point scratch
+  if (int rc = grow_coef_batch(h, g, s)) return rc;
   if (n_eff > uint32_t(kMinTileBits))
     HIPCHK(launch_zero_fill(d_out_counts, ((size_t(n_prog) * size_t(U)) << h->model.n) * sizeof(int32_t), s));
-  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += Uc) {
-    const uint32_t c = std::min<uint32_t>(Uc, uint32_t(U) - s0);
-    for (uint32_t q0 = 0; q0 < n_prog; q0 += Pc) {
-      const uint32_t nq = std::min<uint32_t>(Pc, n_prog - q0);
-      HIPCHK(launch_prep_coefs_batch(d.jobs.p, int(d.plan.jobs.size()), d_params, h->coef_batch.p, h->shift_gates.p + q0,
-                                     h->shift_vals.p + q0, nq, stride, s));
-      HIPCHK(launch_combine_diag(h->coef_batch.p, d.rec_offsets.p, int(d.plan.record_offsets.size()), nq, stride, s));
-      for (size_t i = 0; i < d.plan.passes.size(); ++i) {
-        const Pass& p = d.plan.passes[i];
-        if (p.is_measure_only) continue;
-        PassArgs a = d.args[i];
-        a.flags = (p.flags & (PASS_INIT_BASIS | PASS_GENERAL | PASS_NO_ZERO_FILL)) | PASS_STORE | PASS_SKIP_MEASURE;
-        if (h->opt_force_general) a.flags |= PASS_GENERAL;
-        a.prog_states = c;
-        a.coef_stride = stride;
-        HIPCHK(launch_pass_fwd(p.K, d.plan.R, a, nq * c, h->psi.p, d_bits, h->model.n, d.prog.p, d.tables.p,
-                               h->coef_batch.p, h->op_scale.p, h->vals64.p, s0, s));
-      }
+  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += g.Uc) {
+    const uint32_t c = std::min<uint32_t>(g.Uc, uint32_t(U) - s0);
+    auto draw = [&](uint32_t q0, uint32_t nq) -> int {
       HIPCHK(launch_sample_counts(h->psi.p, n_eff, h->model.n, nq * c, c, q0, h->block_cum.p, uint32_t(n_shots), seed, s0,
                                   uint32_t(U), d_out_counts, s));
-    }
+      return 0;
+    };
+    if (int rc = run_program_groups(h, d_bits, d_params, g, order, 0u, n_prog, s0, c, nullptr, {true, true, false}, s, draw))
+      return rc;
   }
   return 0;
 }
@@ -1844,11 +1903,6 @@ int qhbm_expectation_vjp(qhbm_engine* h, const int8_t* d_bits, int U, const floa
   if (int rc = forward(h, d_bits, U, d_params, d_out_vals, -1, 0.0, s)) return rc;
   DevicePlan& d = h->fwd;
   const bool from_obs = forward_values_from_observable(h);
-  // Prefix sharing only when the first forward pass has PASS_NO_ZERO_FILL, as in qhbm_program_vjps: without it (an index
-  // bit no non-diagonal gate acts on) later passes, the observable kernel and the global-term measurement rely on pass 0
-  // having zero-filled every tile of a program's OWN state, which a program that starts behind it from the base state
-  // never did -- they would read what an earlier call or launch set left there.
-  const bool can_share = h->opt_shift_prefix != 0 && (d.plan.passes.front().flags & PASS_NO_ZERO_FILL);
   if (!h->shift_ready || h->shift_tables_from_obs != from_obs) {  // shift tables: once per model
     h->shift_tables_from_obs = from_obs;
     std::vector<int> sg, sp;
@@ -1863,36 +1917,10 @@ int qhbm_expectation_vjp(qhbm_engine* h, const int8_t* d_bits, int U, const floa
       sp.push_back(G.param_idx);
       sw.push_back(float(1.5707963267948966 * double(G.scalar)));
     }
-    // Execution order: by the first pass that reads the shifted gate's coefficients (first_dependent_pass), gate order
-    // within a pass; the sums of program q land at prog_acc[dst[q]], i.e. in GATE order, so the combination per parameter
-    // adds in the order it always did.  Without sharing every program "starts" at pass 0.
-    const int n_pass = int(d.plan.passes.size());
-    int first_measuring = n_pass;
-    std::vector<int> first(h->model.gates.size(), 0);
-    if (can_share) first = first_dependent_pass(d.plan, h->model.gates.size(), &first_measuring);
-    auto start_of = [&](int gate) {
-      int k = std::min(first[size_t(gate)], n_pass - 1);
-      if (!from_obs) k = std::min(k, first_measuring);   // measuring passes write the program's own accumulators
-      return std::max(k, 0);
-    };
-    std::vector<int> order(sg.size());
-    for (size_t q = 0; q < order.size(); ++q) order[q] = int(q);
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return start_of(sg[size_t(x)]) < start_of(sg[size_t(y)]); });
-    std::vector<int> sg_exec(sg.size()), dst(sg.size());
-    std::vector<float> sv_exec(sg.size());
-    h->shift_group_end.assign(size_t(std::max(n_pass, 1)), 0u);
-    for (size_t q = 0; q < order.size(); ++q) {
-      sg_exec[q] = sg[size_t(order[q])];
-      sv_exec[q] = sv[size_t(order[q])];
-      dst[q] = order[q];
-      h->shift_group_end[size_t(start_of(sg_exec[q]))] = uint32_t(q + 1);
-    }
-    for (size_t i = 1; i < h->shift_group_end.size(); ++i)
-      h->shift_group_end[i] = std::max(h->shift_group_end[i], h->shift_group_end[i - 1]);
-    HIPCHK(hipStreamSynchronize(s));  // synchronous copies into buffers an earlier call on this stream may still read
-    HIPCHK(h->shift_gates.upload(sg_exec));
-    HIPCHK(h->shift_vals.upload(sv_exec));
-    HIPCHK(h->shift_dst.upload(dst));
+    // The sums of program q land at prog_acc[dst[q]], i.e. in GATE order whatever the execution order: the combination per
+    // parameter adds in the order it always did.
+    h->shift_order = order_programs(d.plan, h->model.gates.size(), sg.data(), sg.size(), h->opt_shift_prefix != 0, from_obs);
+    if (int rc = upload_shift_tables(h, h->shift_order, sg.data(), sv.data(), s)) return rc;
     HIPCHK(h->shift_param.upload(sp));
     HIPCHK(h->shift_weight.upload(sw));
     h->shift_programs = uint32_t(sg.size());
@@ -1904,97 +1932,34 @@ int qhbm_expectation_vjp(qhbm_engine* h, const int8_t* d_bits, int U, const floa
     if (P) HIPCHK(launch_zero_fill(d_grad, size_t(P) * sizeof(float), s));
     return 0;
   }
-  const uint32_t stride = uint32_t((d.plan.coef_init.size() + 64 + 63) / 64 * 64);
-  // batch geometry: Uc states x Pc programs per launch set (+ Uc base states when programs share their prefix)
-  size_t cap = std::max<size_t>(1, budget_bytes(h) / state_bytes(h));
-  uint32_t max_nl = 0;
-  for (const PassArgs& a : d.args) max_nl = std::max(max_nl, a.n_nonlocal);
-  cap = std::min<size_t>(cap, (size_t(1) << 30) >> max_nl);  // grid.x = elements << n_nonlocal
-  cap = std::min<size_t>(cap, (size_t(2) << 30) / (size_t(stride) * sizeof(float)));  // <= 2 GiB of coefficient copies
-  if (h->opt_chunk > 0) cap = std::min<size_t>(cap, size_t(h->opt_chunk));
-  // sharing needs a second buffer of Uc base states and at least one pass to skip
-  const bool share = can_share && h->shift_group_end.size() > 1 && h->shift_group_end[0] < n_prog && cap >= 2;
-  const uint32_t Uc = uint32_t(std::min<size_t>(size_t(U), share ? cap / 2 : cap));
-  const uint32_t Pc = uint32_t(std::max<size_t>(1, std::min<size_t>(n_prog, (cap - (share ? Uc : 0)) / Uc)));
-  if (int rc = ensure_state_buffers(h, Uc * Pc, false)) return rc;
-  if (share) HIPCHK(h->lam.reserve(size_t(Uc) << d.plan.n_eff, false));   // the base states live where lambda would
-  const size_t nvb = size_t(Uc) * Pc * size_t(h->model.n_ops);
+  const LaunchSets g = launch_set_geometry(h, U, n_prog, h->shift_order, 1, false, true);
+  if (int rc = ensure_state_buffers(h, g.Uc * g.Pc, false)) return rc;
+  if (g.share) HIPCHK(h->lam.reserve(size_t(g.Uc) << d.plan.n_eff, false));   // the base states live where lambda would
+  const uint32_t T = uint32_t(h->model.n_ops);
+  const size_t nvb = size_t(g.Uc) * g.Pc * T;
   HIPCHK(h->vals64.reserve(nvb));
   HIPCHK(h->vals_batch.reserve(nvb));
   HIPCHK(h->prog_acc.reserve(n_prog));
   HIPCHK(launch_zero_fill(h->prog_acc.p, size_t(n_prog) * sizeof(double), s));
-  if (h->coef_batch_programs < Pc) {
-    HIPCHK(h->coef_batch.reserve(size_t(Pc) * stride));
-    HIPCHK(launch_replicate(d.coef.p, h->coef_batch.p, uint32_t(d.plan.coef_init.size()), stride, Pc, s));
-    h->coef_batch_programs = Pc;
-  }
+  if (int rc = grow_coef_batch(h, g, s)) return rc;
   h->retained_U = 0;
   h->state_grad_U = 0;
-  bool measure_only_after = !d.plan.global_terms.empty();
-  for (const Pass& p : d.plan.passes) measure_only_after |= p.is_measure_only;
   // The values of a shifted program come the way a forward-only call takes them: where that is the observable kernel
   // (wide terms: lean passes, then one sweep over the final states, the lower block of every pair only), the
-  // shifted programs do the same -- config 4's 480 masks cost 51 measurement passes per program otherwise.
-  auto pass_args = [&](size_t i, uint32_t prog_states) {
-    const Pass& p = d.plan.passes[i];
-    PassArgs a = d.args[i];
-    a.flags = p.flags & (PASS_INIT_BASIS | PASS_GENERAL | PASS_NO_ZERO_FILL);
-    if (h->opt_force_general) a.flags |= PASS_GENERAL;
-    if (from_obs) a.flags |= PASS_SKIP_MEASURE;
-    if (!p.is_measure_only && (!p.completes_circuit || measure_only_after || from_obs)) a.flags |= PASS_STORE;
-    a.prog_states = prog_states;
-    a.coef_stride = prog_states ? stride : 0u;
-    return a;
-  };
-  const size_t n_pass = d.plan.passes.size();
-  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += Uc) {
-    const uint32_t c = std::min<uint32_t>(Uc, uint32_t(U) - s0);
-    // k: the pass the programs of this group start at; the base buffer holds the base program's states after passes < k
-    for (size_t k = 0; k < (share ? n_pass : size_t(1)); ++k) {
-      const uint32_t group_begin = share ? (k ? h->shift_group_end[k - 1] : 0u) : 0u;
-      const uint32_t group_end = share ? h->shift_group_end[k] : n_prog;
-      for (uint32_t q0 = group_begin; q0 < group_end; q0 += Pc) {
-        const uint32_t nq = std::min<uint32_t>(Pc, group_end - q0);
-        HIPCHK(launch_prep_coefs_batch(d.jobs.p, int(d.plan.jobs.size()), d_params, h->coef_batch.p, h->shift_gates.p + q0,
-                                       h->shift_vals.p + q0, nq, stride, s));
-        HIPCHK(launch_combine_diag(h->coef_batch.p, d.rec_offsets.p, int(d.plan.record_offsets.size()), nq, stride, s));
-        HIPCHK(launch_zero_fill(h->vals64.p, size_t(nq) * c * size_t(h->model.n_ops) * sizeof(unsigned long long), s));
-        bool first_pass = true;
-        for (size_t i = k; i < n_pass; ++i) {
-          const Pass& p = d.plan.passes[i];
-          if (from_obs && p.is_measure_only) continue;
-          const PassArgs a = pass_args(i, c);
-          hipEvent_t* ev = timer_begin(h, 0, s);
-          // (the first pass a prefix-sharing program runs loads the base program's state of its bitstring)
-          HIPCHK(launch_pass_fwd(p.K, d.plan.R, a, nq * c, h->psi.p, d_bits, h->model.n, d.prog.p, d.tables.p,
-                                 h->coef_batch.p, h->op_scale.p, h->vals64.p, s0, s,
-                                 (first_pass && k > 0) ? h->lam.p : nullptr));
-          timer_end(ev, s);
-          first_pass = false;
-        }
-        if (from_obs) {
-          if (int rc = run_values_chunk(h, 0u, nq * c, s)) return rc;
-        } else if (!d.plan.global_terms.empty()) {
-          HIPCHK(launch_measure_global(h->psi.p, uint32_t(d.plan.n_eff), nq * c, h->global_terms.p,
-                                       uint32_t(d.plan.global_terms.size()), h->op_scale.p, h->vals64.p,
-                                       uint32_t(h->model.n_ops), 0u, s));
-        }
-        HIPCHK(launch_values_from_fixed(h->vals64.p, h->op_inv_scale.p, h->vals_batch.p,
-                                        nq * c * uint32_t(h->model.n_ops), uint32_t(h->model.n_ops), s));
-        HIPCHK(launch_shift_program_accumulate(h->vals_batch.p, d_upstream, nq, c, uint32_t(h->model.n_ops), s0,
-                                               h->prog_acc.p, s, h->shift_dst.p + q0));
-      }
-      // the base program advances by pass k (its own coefficients: d.coef, prepared by the forward call above) unless
-      // no later program needs it
-      if (share && group_end < n_prog && !(from_obs && d.plan.passes[k].is_measure_only)) {
-        PassArgs a = pass_args(k, 0u);
-        a.flags |= PASS_STORE | PASS_SKIP_MEASURE;   // (its values were taken by the forward call)
-        hipEvent_t* ev = timer_begin(h, 0, s);
-        HIPCHK(launch_pass_fwd(d.plan.passes[k].K, d.plan.R, a, c, h->lam.p, d_bits, h->model.n, d.prog.p, d.tables.p,
-                               d.coef.p, h->op_scale.p, h->vals64.p, s0, s));
-        timer_end(ev, s);
-      }
-    }
+  // shifted programs do the same -- config 4's 480 masks cost 51 measurement passes per program otherwise.  The base
+  // program's coefficients are those the forward call above prepared.
+  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += g.Uc) {
+    const uint32_t c = std::min<uint32_t>(g.Uc, uint32_t(U) - s0);
+    auto accumulate = [&](uint32_t q0, uint32_t nq) -> int {
+      if (from_obs)
+        if (int rc = run_values_chunk(h, 0u, nq * c, s)) return rc;
+      HIPCHK(launch_values_from_fixed(h->vals64.p, h->op_inv_scale.p, h->vals_batch.p, nq * c * T, T, s));
+      HIPCHK(launch_shift_program_accumulate(h->vals_batch.p, d_upstream, nq, c, T, s0, h->prog_acc.p, s, h->shift_dst.p + q0));
+      return 0;
+    };
+    if (int rc = run_program_groups(h, d_bits, d_params, g, h->shift_order, 0u, n_prog, s0, c, h->lam.p,
+                                    {from_obs, from_obs, true}, s, accumulate))
+      return rc;
   }
   HIPCHK(launch_shift_combine(h->prog_acc.p, h->shift_param.p, h->shift_weight.p, int(n_shift_gates), d_grad, P, s));
   return 0;
@@ -2040,72 +2005,34 @@ int qhbm_program_vjps(qhbm_engine* h, const int8_t* d_bits, int U, const float* 
   DevicePlan& b = h->adj;
   h->retained_U = 0;
   h->state_grad_U = 0;
-  const int n_pass = int(d.plan.passes.size());
   const uint32_t n_slots = uint32_t(b.plan.slot_gate.size()), ns1 = std::max<uint32_t>(n_slots, 1);
   // values and lambda exactly as the adjoint VJP (adjoint_sweep) takes them: an unshifted program is its d_grad bit for bit
   const bool vm = value_mode(h), mv = multi_value_mode(h), gm = mv && gather_multi_mode(h), skip = vm || mv;
-  // Prefix sharing.  Only when the first forward pass has PASS_NO_ZERO_FILL, as in qhbm_expectation_vjp(method 1):
-  // without it (an index bit no non-diagonal gate acts on) later passes rely on pass 0 having zero-filled every tile of
-  // an element's OWN state, which a program that starts behind it from the base state never did.
-  const bool can_share = h->opt_shift_prefix != 0 && n_pass > 1 && (d.plan.passes[0].flags & PASS_NO_ZERO_FILL);
-  int first_measuring = n_pass;
-  std::vector<int> first;
-  if (can_share) first = first_dependent_pass(d.plan, size_t(n_gates), &first_measuring);
-  auto start_of = [&](int g) {
-    if (!can_share) return 0;
-    int k = g < 0 ? n_pass - 1 : std::min(first[size_t(g)], n_pass - 1);
-    if (!skip) k = std::min(k, first_measuring);  // measuring passes write the program's own accumulators
-    while (k > 0 && d.plan.passes[size_t(k)].is_measure_only) --k;  // a program starts at a pass that stores its state
-    return std::max(k, 0);
-  };
+  const ProgramOrder order = order_programs(d.plan, size_t(n_gates), shift_gates, n_prog, h->opt_shift_prefix != 0, skip);
   int first_live = n_gates;  // the backward sweep un-applies gates behind this one only
   for (int g = 0; g < n_gates; ++g) {
     const Gate& G = h->model.gates[size_t(g)];
     if (G.param_idx >= 0 && !h->model.frozen(G.param_idx)) { first_live = g; break; }
   }
-  std::vector<int> order(n_prog);
-  for (uint32_t q = 0; q < n_prog; ++q) order[q] = int(q);
-  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return start_of(shift_gates[x]) < start_of(shift_gates[y]); });
-  std::vector<int> sg(n_prog), dst(n_prog);
+  std::vector<int> sg(n_prog);  // (execution order, as the device tables)
   std::vector<float> sv(n_prog);
   std::vector<char> swept(n_prog);
-  std::vector<uint32_t> group_end(size_t(std::max(n_pass, 1)), 0u);
   for (uint32_t q = 0; q < n_prog; ++q) {
-    sg[q] = std::max(shift_gates[order[q]], -1);
-    sv[q] = shifts[order[q]];
-    dst[q] = order[q];
+    sg[q] = shift_gates[order.dst[q]];
+    sv[q] = shifts[order.dst[q]];
     swept[q] = sg[q] >= first_live && sv[q] != 0.f;
-    group_end[size_t(start_of(sg[q]))] = q + 1;
   }
-  for (size_t i = 1; i < group_end.size(); ++i) group_end[i] = std::max(group_end[i], group_end[i - 1]);
-  HIPCHK(hipStreamSynchronize(s));  // synchronous copies into buffers an earlier call on this stream may still read
-  HIPCHK(h->pv_gates.upload(sg));
-  HIPCHK(h->pv_shifts.upload(sv));
-  HIPCHK(h->pv_dst.upload(dst));
-
-  // launch-set geometry: Uc states x Pc programs, every element with psi and lambda (+ Uc base states when sharing)
-  const uint32_t stride = uint32_t((d.plan.coef_init.size() + 64 + 63) / 64 * 64);
-  const size_t states_cap = std::max<size_t>(1, budget_bytes(h) / state_bytes(h));
-  uint32_t max_nl = 0;
-  for (const PassArgs& a : d.args) max_nl = std::max(max_nl, a.n_nonlocal);
-  for (const PassArgs& a : b.args) max_nl = std::max(max_nl, a.n_nonlocal);
-  size_t el_cap = std::max<size_t>(1, states_cap / 2);
-  el_cap = std::min<size_t>(el_cap, (size_t(1) << 30) >> max_nl);                         // grid.x = elements << n_nonlocal
-  el_cap = std::min<size_t>(el_cap, (size_t(2) << 30) / (size_t(stride) * sizeof(float)));  // <= 2 GiB of coefficient copies
-  el_cap = std::min<size_t>(el_cap, 65535);                                                // per-state grids of the observable kernels
-  if (h->opt_chunk > 0) el_cap = std::min<size_t>(el_cap, size_t(h->opt_chunk));
-  el_cap = std::max<size_t>(el_cap, 1);
-  const bool share = can_share && group_end[0] < n_prog && states_cap >= 3;
-  const uint32_t Uc = uint32_t(std::min<size_t>(size_t(U), share ? std::max<size_t>(1, std::min(el_cap, states_cap / 3)) : el_cap));
-  const uint32_t Pc = uint32_t(std::max<size_t>(
-      1, std::min<size_t>(n_prog, std::min<size_t>(el_cap, (states_cap - (share ? Uc : 0)) / 2) / Uc)));
+  if (int rc = upload_shift_tables(h, order, shift_gates, shifts, s)) return rc;
+  // every element with psi and lambda; the base program's states of a shared prefix in a buffer of their own
+  const LaunchSets g = launch_set_geometry(h, U, n_prog, order, 2, true, false);
+  const uint32_t Uc = g.Uc, Pc = g.Pc;
   // gradient rows of the programs in flight: [R, U, n_slots] (a quarter of the budget, at least one program)
   const size_t row_bytes = size_t(U) * ns1 * sizeof(float);
   const uint32_t R = uint32_t(std::max<size_t>(1, std::min<size_t>(std::min<size_t>(n_prog, 65535), budget_bytes(h) / 4 / row_bytes)));
   const uint32_t n_eff = uint32_t(d.plan.n_eff), n = uint32_t(h->model.n);
   const size_t ne_max = size_t(Uc) * Pc;
   if (int rc = ensure_state_buffers(h, uint32_t(ne_max), true)) return rc;
-  if (share) HIPCHK(h->pv_base.reserve(size_t(Uc) << n_eff, false));
+  if (g.share) HIPCHK(h->pv_base.reserve(size_t(Uc) << n_eff, false));
   HIPCHK(h->pv_bits.reserve(ne_max * n));
   HIPCHK(h->pv_upstream.reserve(ne_max * T));
   HIPCHK(h->vals64.reserve(ne_max * T));
@@ -2115,98 +2042,56 @@ int qhbm_program_vjps(qhbm_engine* h, const int8_t* d_bits, int U, const float* 
   HIPCHK(h->pv_vals.reserve(size_t(n_prog) * T));
   HIPCHK(launch_zero_fill(h->pv_vals.p, size_t(n_prog) * T * sizeof(double), s));
   // coefficients: the base program's (forward) and the shared backward ones
-  HIPCHK(launch_prep_coefs(d.jobs.p, int(d.plan.jobs.size()), d_params, d.coef.p, -1, 0.0, s));
-  HIPCHK(launch_combine_diag(d.coef.p, d.rec_offsets.p, int(d.plan.record_offsets.size()), 1u, 0u, s));
-  auto prep_adjoint = [&](int gate, double shift) {
-    hipError_t e = launch_prep_coefs(b.jobs.p, int(b.plan.jobs.size()), d_params, b.coef.p, gate, shift, s);
-    if (e == hipSuccess) e = launch_combine_diag(b.coef.p, b.rec_offsets.p, int(b.plan.record_offsets.size()), 1u, 0u, s);
-    return e;
-  };
-  HIPCHK(prep_adjoint(-1, 0.0));
+  if (int rc = prepare_coefs(h, d, d_params, -1, 0.0, s)) return rc;
+  auto prep_adjoint = [&](int gate, double shift) { return prepare_coefs(h, b, d_params, gate, shift, s); };
+  if (int rc = prep_adjoint(-1, 0.0)) return rc;
   bool adjoint_shifted = false;
-  if (h->coef_batch_programs < Pc) {
-    HIPCHK(h->coef_batch.reserve(size_t(Pc) * stride));
-    HIPCHK(launch_replicate(d.coef.p, h->coef_batch.p, uint32_t(d.plan.coef_init.size()), stride, Pc, s));
-    h->coef_batch_programs = Pc;
-  }
+  if (int rc = grow_coef_batch(h, g, s)) return rc;
   for (uint32_t qa = 0; qa < n_prog; qa += R) {
     const uint32_t qb = std::min<uint32_t>(n_prog, qa + R);
     for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += Uc) {
       const uint32_t c = std::min<uint32_t>(Uc, uint32_t(U) - s0);
       HIPCHK(launch_replicate_rows(d_bits, h->pv_bits.p, n, c, s0, Pc * c, s));
       HIPCHK(launch_replicate_rows(d_upstream, h->pv_upstream.p, T * uint32_t(sizeof(float)), c, s0, Pc * c, s));
-      // k: the pass the programs of this group start at; pv_base holds the base program's states after passes < k
-      for (int k = 0; k < (share ? n_pass : 1); ++k) {
-        const uint32_t gb = share ? (k ? group_end[size_t(k) - 1] : 0u) : 0u, ge = share ? group_end[size_t(k)] : n_prog;
-        const uint32_t lo = std::max(gb, qa), hi = std::min(ge, qb);
-        for (uint32_t q0 = lo; q0 < hi; q0 += Pc) {
-          const uint32_t nq = std::min<uint32_t>(Pc, hi - q0), ne = nq * c;
-          HIPCHK(launch_prep_coefs_batch(d.jobs.p, int(d.plan.jobs.size()), d_params, h->coef_batch.p, h->pv_gates.p + q0,
-                                         h->pv_shifts.p + q0, nq, stride, s));
-          HIPCHK(launch_combine_diag(h->coef_batch.p, d.rec_offsets.p, int(d.plan.record_offsets.size()), nq, stride, s));
-          HIPCHK(launch_zero_fill(h->vals64.p, size_t(ne) * T * sizeof(unsigned long long), s));
-          bool first_pass = true;
-          for (int i = k; i < n_pass; ++i) {
-            const Pass& p = d.plan.passes[size_t(i)];
-            if (skip && p.is_measure_only) continue;
-            PassArgs a = d.args[size_t(i)];
-            a.flags = p.flags & (PASS_INIT_BASIS | PASS_GENERAL | PASS_NO_ZERO_FILL);
-            if (h->opt_force_general) a.flags |= PASS_GENERAL;
-            if (skip) a.flags |= PASS_SKIP_MEASURE;
-            if (!p.is_measure_only || (first_pass && k > 0)) a.flags |= PASS_STORE;  // the final states feed lambda
-            a.prog_states = c;
-            a.coef_stride = stride;
-            hipEvent_t* ev = timer_begin(h, 0, s);
-            HIPCHK(launch_pass_fwd(p.K, d.plan.R, a, ne, h->psi.p, d_bits, int(n), d.prog.p, d.tables.p, h->coef_batch.p,
-                                   h->op_scale.p, h->vals64.p, s0, s, (first_pass && k > 0) ? h->pv_base.p : nullptr));
-            timer_end(ev, s);
-            first_pass = false;
+      // the caller's own work on a launch set: lambda = O psi, the backward sweeps, rows and values of its programs
+      auto backward = [&](uint32_t q0, uint32_t nq) -> int {
+        const uint32_t ne = nq * c;
+        if (mv && !gm)
+          if (int rc = run_values_chunk(h, 0u, ne, s)) return rc;
+        HIPCHK(launch_zero_fill(h->state_grad.p, size_t(ne) * ns1 * sizeof(float), s));
+        if (int rc = run_observable_chunk(h, 0u, ne, h->pv_upstream.p, vm, s, true, gm)) return rc;
+        // backward sweeps: runs of programs on the shared coefficients, a program behind the first live gate on its own
+        for (uint32_t j = 0; j < nq;) {
+          uint32_t j1 = j + 1;
+          if (swept[q0 + j]) {
+            if (int rc = prep_adjoint(sg[q0 + j], double(sv[q0 + j]))) return rc;
+            adjoint_shifted = true;
+          } else {
+            while (j1 < nq && !swept[q0 + j1]) ++j1;
+            if (adjoint_shifted)
+              if (int rc = prep_adjoint(-1, 0.0)) return rc;
+            adjoint_shifted = false;
           }
-          if (!skip && !d.plan.global_terms.empty())
-            HIPCHK(launch_measure_global(h->psi.p, n_eff, ne, h->global_terms.p, uint32_t(d.plan.global_terms.size()),
-                                         h->op_scale.p, h->vals64.p, T, 0u, s));
-          if (mv && !gm)
-            if (int rc = run_values_chunk(h, 0u, ne, s)) return rc;
-          HIPCHK(launch_zero_fill(h->state_grad.p, size_t(ne) * ns1 * sizeof(float), s));
-          if (int rc = run_observable_chunk(h, 0u, ne, h->pv_upstream.p, vm, s, true, gm)) return rc;
-          // backward sweeps: runs of programs on the shared coefficients, a program behind the first live gate on its own
-          for (uint32_t j = 0; j < nq;) {
-            uint32_t j1 = j + 1;
-            if (swept[q0 + j]) {
-              HIPCHK(prep_adjoint(sg[q0 + j], double(sv[q0 + j])));
-              adjoint_shifted = true;
-            } else {
-              while (j1 < nq && !swept[q0 + j1]) ++j1;
-              if (adjoint_shifted) HIPCHK(prep_adjoint(-1, 0.0));
-              adjoint_shifted = false;
-            }
-            if (int rc = run_adjoint_chunk(h, h->pv_bits.p, j * c, (j1 - j) * c, s, j * c)) return rc;
-            j = j1;
-          }
-          // value mode: the sweep ran on the unweighted lambda, the upstream weight goes onto the rows (as adjoint_sweep)
-          if (vm) HIPCHK(launch_scale_rows(h->state_grad.p, ne, ns1, h->pv_upstream.p, s));
-          HIPCHK(launch_scatter_program_rows(h->state_grad.p, h->pv_rows.p, n_slots, c, s0, uint32_t(U), q0 - qa, ne, s));
-          HIPCHK(launch_values_from_fixed(h->vals64.p, h->op_inv_scale.p, h->vals_batch.p, ne * T, T, s));
-          HIPCHK(launch_accumulate_program_values(h->vals_batch.p, d_row_weights, nq, c, T, s0, h->pv_dst.p + q0,
-                                                  h->pv_vals.p, s));
+          if (int rc = run_adjoint_chunk(h, h->pv_bits.p, j * c, (j1 - j) * c, s, j * c)) return rc;
+          j = j1;
         }
-        // the base program advances by pass k (its own coefficients) while a later program of this range needs it
-        if (share && ge < qb && !d.plan.passes[size_t(k)].is_measure_only) {
-          const Pass& p = d.plan.passes[size_t(k)];
-          PassArgs a = d.args[size_t(k)];
-          a.flags = (p.flags & (PASS_INIT_BASIS | PASS_GENERAL | PASS_NO_ZERO_FILL)) | PASS_STORE | PASS_SKIP_MEASURE;
-          if (h->opt_force_general) a.flags |= PASS_GENERAL;
-          hipEvent_t* ev = timer_begin(h, 0, s);
-          HIPCHK(launch_pass_fwd(p.K, d.plan.R, a, c, h->pv_base.p, d_bits, int(n), d.prog.p, d.tables.p, d.coef.p,
-                                 h->op_scale.p, h->vals64.p, s0, s));
-          timer_end(ev, s);
-        }
-      }
+        // value mode: the sweep ran on the unweighted lambda, the upstream weight goes onto the rows (as adjoint_sweep)
+        if (vm) HIPCHK(launch_scale_rows(h->state_grad.p, ne, ns1, h->pv_upstream.p, s));
+        HIPCHK(launch_scatter_program_rows(h->state_grad.p, h->pv_rows.p, n_slots, c, s0, uint32_t(U), q0 - qa, ne, s));
+        HIPCHK(launch_values_from_fixed(h->vals64.p, h->op_inv_scale.p, h->vals_batch.p, ne * T, T, s));
+        HIPCHK(launch_accumulate_program_values(h->vals_batch.p, d_row_weights, nq, c, T, s0, h->shift_dst.p + q0,
+                                                h->pv_vals.p, s));
+        return 0;
+      };
+      // (the final states feed lambda: every pass that is not measurement-only stores)
+      if (int rc = run_program_groups(h, d_bits, d_params, g, order, qa, qb, s0, c, h->pv_base.p, {true, skip, true}, s, backward))
+        return rc;
     }
     HIPCHK(launch_reduce_program_grad(h->pv_rows.p, uint32_t(U), n_slots, h->param_slot_begin.p, h->param_slots.p,
-                                      h->slot_factor.p, h->pv_dst.p + qa, qb - qa, d_prog_grad, P, s));
+                                      h->slot_factor.p, h->shift_dst.p + qa, qb - qa, d_prog_grad, P, s));
   }
-  if (adjoint_shifted) HIPCHK(prep_adjoint(-1, 0.0));
+  if (adjoint_shifted)
+    if (int rc = prep_adjoint(-1, 0.0)) return rc;
   if (d_prog_vals) HIPCHK(launch_doubles_to_floats(h->pv_vals.p, d_prog_vals, size_t(n_prog) * T, s));
   return 0;
 }

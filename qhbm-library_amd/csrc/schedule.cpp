@@ -1582,4 +1582,93 @@ std::string describe_plan(const Plan& p) {
   return os.str();
 }
 
+// Parameter shift with a shared prefix.  A shifted program differs from the base program in the coefficients of ONE gate;
+// the passes in front of the first pass that reads them compute, state by state, the bits the base program computes.
+// Record ranges come from the pass programs (OP_ROUND: n_instances records from its first record; OP_GATE2: a 4 x 4
+// matrix), jobs from the plan (CoefJob::gate writes at CoefJob::out_off).
+std::vector<int> first_dependent_pass(const Plan& plan, size_t n_gates, int* first_measuring) {
+  const RecordLayout L(plan.R, false);
+  struct Range { uint32_t lo, hi; int pass; };
+  std::vector<Range> ranges;
+  const int n_pass = int(plan.passes.size());
+  *first_measuring = n_pass;
+  for (int i = 0; i < n_pass; ++i) {
+    const std::vector<uint32_t>& prog = plan.passes[size_t(i)].prog;
+    size_t pc = 0;
+    while (pc < prog.size()) {
+      const uint32_t w0 = prog[pc], opc = w0 & 0xffu;
+      if (opc == OP_END) break;
+      if (opc == OP_ROUND) {
+        const uint32_t n_inst = (w0 & ~kRoundNoBarrier) >> 8, rec = prog[pc + 2];
+        ranges.push_back(Range{rec, rec + n_inst * uint32_t(L.words()), i});
+        pc += kRoundWords;
+      } else if (opc == OP_GATE2) {
+        ranges.push_back(Range{prog[pc + 2], prog[pc + 2] + 32u, i});
+        pc += kGate2Words;
+      } else if (opc == OP_MEASURE_WHT) {
+        *first_measuring = std::min(*first_measuring, i);
+        pc += size_t(kWhtHeaderWords) + size_t(w0 >> 8) * kMeasTermWords;
+      } else if (opc == OP_MEASURE) {
+        const uint32_t n_groups = w0 >> 8;
+        if (n_groups) *first_measuring = std::min(*first_measuring, i);
+        pc += 1;
+        for (uint32_t g = 0; g < n_groups && pc + 1 < prog.size(); ++g) pc += 2u + size_t(prog[pc + 1]) * kMeasTermWords;
+      } else {
+        return std::vector<int>(n_gates, 0);  // an opcode this walk does not know: share nothing
+      }
+    }
+  }
+  std::vector<int> first(n_gates, n_pass);
+  for (const CoefJob& j : plan.jobs) {
+    if (j.gate < 0 || size_t(j.gate) >= n_gates) continue;
+    int pass = 0;  // (a job whose record no pass claims: share nothing for its gate)
+    for (const Range& r : ranges)
+      if (uint32_t(j.out_off) >= r.lo && uint32_t(j.out_off) < r.hi) { pass = r.pass; break; }
+    first[size_t(j.gate)] = std::min(first[size_t(j.gate)], pass);
+  }
+  return first;
+}
+
+// Where a program starts -- the ONE rule, for every caller (engine.cpp run_program_groups):
+//  * at the first pass that reads its gate's coefficients; the unshifted program (a negative gate) and a gate no record
+//    reads (an identity) at the last pass;
+//  * not behind the first measuring pass when the values are measured in the passes: a pass measures into the program's
+//    own accumulators;
+//  * walked back to a pass that stores its state: measurement-only passes store nothing, so the passes behind a
+//    program's first one would read a state the program never wrote.
+// Any earlier start is as good: the passes a program runs in front of its gate recompute, bit for bit, what the base
+// program computed (the premise of sharing; tests hold sharing against no sharing bit for bit), so a caller whose
+// programs once started later gets the same bits from this rule.
+// Sound only on plans with more than one pass whose first pass has PASS_NO_ZERO_FILL: a program that starts at pass
+// k > 0 loads only the tiles pass k launches, and on a zero-filling plan (an index bit no non-diagonal gate acts on) later
+// passes, the observable kernel and the global-term measurement rely on pass 0 having zero-filled every tile of the
+// program's OWN state -- they would read what an earlier call or launch set left there.  Then, as with `may_share`
+// false, every program is in group 0 in the caller's order.
+ProgramOrder order_programs(const Plan& fwd, size_t n_gates, const int* shift_gates, size_t n_programs, bool may_share,
+                            bool values_outside_passes) {
+  const int n_pass = int(fwd.passes.size());
+  ProgramOrder o;
+  o.dst.resize(n_programs);
+  for (size_t q = 0; q < n_programs; ++q) o.dst[q] = int(q);
+  o.group_end.assign(size_t(std::max(n_pass, 1)), uint32_t(n_programs));
+  if (!may_share || n_pass < 2 || !(fwd.passes[0].flags & PASS_NO_ZERO_FILL)) return o;
+  int first_measuring = n_pass;
+  const std::vector<int> first = first_dependent_pass(fwd, n_gates, &first_measuring);
+  std::vector<int> start(n_programs);
+  for (size_t q = 0; q < n_programs; ++q) {
+    const int g = shift_gates[q];
+    int k = g < 0 ? n_pass - 1 : std::min(first[size_t(g)], n_pass - 1);
+    if (!values_outside_passes) k = std::min(k, first_measuring);
+    while (k > 0 && fwd.passes[size_t(k)].is_measure_only) --k;
+    start[q] = k;
+  }
+  // by start pass, the caller's order within a pass
+  std::stable_sort(o.dst.begin(), o.dst.end(), [&](int x, int y) { return start[size_t(x)] < start[size_t(y)]; });
+  o.group_end.assign(size_t(n_pass), 0u);
+  for (size_t q = 0; q < n_programs; ++q) o.group_end[size_t(start[size_t(o.dst[q])])] = uint32_t(q + 1);
+  for (size_t i = 1; i < o.group_end.size(); ++i) o.group_end[i] = std::max(o.group_end[i], o.group_end[i - 1]);
+  o.shares = o.group_end[0] < n_programs;
+  return o;
+}
+
 }  // namespace qhbm

@@ -150,4 +150,21 @@ bool build_plan(const Model& m, int tile_bits, int round_bits, bool adjoint, Pla
 
 std::string describe_plan(const Plan& p);
 
+// For every gate of a forward plan: the first pass that reads its coefficients (the pass count for a gate no record
+// depends on; 0 for every gate if the walk meets a program it does not know).  `first_measuring`: the first pass with a
+// measurement op (the pass count if none has one).
+std::vector<int> first_dependent_pass(const Plan& plan, size_t n_gates, int* first_measuring);
+
+// Execution order of a batch of shifted programs (program q = the circuit with gate shift_gates[q] shifted; a negative
+// gate = the unshifted circuit).  Programs of group k start at pass k from the base program's state after passes < k.
+struct ProgramOrder {
+  std::vector<int> dst;             // execution slot -> the caller's program index
+  std::vector<uint32_t> group_end;  // programs (execution order) that start at a pass <= i end here; size max(n_pass, 1)
+  bool shares = false;              // some program starts behind pass 0
+};
+// `may_share`: the caller's option; false = every program in group 0, in the caller's order.  `values_outside_passes`: the
+// observable kernel takes the values (the passes measure nothing, so a program may start behind the first measuring pass).
+ProgramOrder order_programs(const Plan& fwd, size_t n_gates, const int* shift_gates, size_t n_programs, bool may_share,
+                            bool values_outside_passes);
+
 }  // namespace qhbm

@@ -309,6 +309,54 @@ static void fill_terms(Case* c) {
     }
 }
 
+// order_programs (schedule.h) on a forward plan: a program per parametrised gate plus the unshifted program, values
+// taken in the passes and outside them, sharing allowed and not.
+static long g_orders_shared = 0, g_programs_behind_pass_0 = 0;  // (the run must see both: the checks below are not vacuous)
+static void check_program_order(const Model& m, const Plan& plan) {
+  const size_t n_pass = plan.passes.size();
+  std::vector<int> gates;
+  for (size_t g = 0; g < m.gates.size(); ++g)
+    if (m.gates[g].param_idx >= 0) gates.push_back(int(g));
+  gates.push_back(-1);
+  const size_t np = gates.size();
+  int first_measuring = 0;
+  const std::vector<int> first = first_dependent_pass(plan, m.gates.size(), &first_measuring);
+  const bool sound = n_pass > 1 && (plan.passes[0].flags & PASS_NO_ZERO_FILL);
+  for (int variant = 0; variant < 4; ++variant) {
+    const bool may_share = variant & 1, outside = variant & 2;
+    const ProgramOrder o = order_programs(plan, m.gates.size(), gates.data(), np, may_share, outside);
+    CHECK(o.dst.size() == np && o.group_end.size() == std::max<size_t>(n_pass, 1), "sizes %zu %zu", o.dst.size(), o.group_end.size());
+    if (o.dst.size() != np || o.group_end.size() != std::max<size_t>(n_pass, 1)) return;
+    std::vector<char> seen(np, 0);
+    for (int d : o.dst) {
+      CHECK(d >= 0 && size_t(d) < np && !seen[size_t(d)], "dst is no permutation (%d)", d);
+      if (d < 0 || size_t(d) >= np) return;
+      seen[size_t(d)] = 1;
+    }
+    for (size_t i = 1; i < o.group_end.size(); ++i) CHECK(o.group_end[i] >= o.group_end[i - 1], "group_end decreases at %zu", i);
+    CHECK(o.group_end.back() == np, "group_end ends at %u of %zu programs", o.group_end.back(), np);
+    if (o.group_end.back() != np) return;
+    if (!may_share || !sound) {  // every program in group 0, in the caller's order
+      for (size_t q = 0; q < np; ++q) CHECK(o.dst[q] == int(q), "order changed without sharing");
+      CHECK(o.group_end[0] == np && !o.shares, "programs behind pass 0 without sharing");
+      continue;
+    }
+    long behind = 0;
+    size_t k = 0;  // the pass the program in slot q starts at
+    for (size_t q = 0; q < np; ++q) {
+      while (o.group_end[k] <= q) ++k;
+      const int g = gates[size_t(o.dst[q])];
+      if (g >= 0) CHECK(int(k) <= first[size_t(g)], "gate %d: starts at pass %zu, read by pass %d", g, k, first[size_t(g)]);
+      if (!outside) CHECK(int(k) <= first_measuring, "starts at pass %zu behind the first measuring pass %d", k, first_measuring);
+      CHECK(k == 0 || !plan.passes[k].is_measure_only, "starts at pass %zu, which stores no state", k);
+      behind += k > 0;
+    }
+    CHECK(o.shares == (behind > 0), "shares = %d with %ld programs behind pass 0", int(o.shares), behind);
+    g_orders_shared += o.shares;
+    g_programs_behind_pass_0 += behind;
+  }
+}
+
 static int fuzz_one(std::mt19937_64& rng, int n, int index) {
   auto U = [&](int lo, int hi) { return int(std::uniform_int_distribution<int>(lo, hi)(rng)); };
   Case c = random_case(rng, n);
@@ -340,6 +388,7 @@ static int fuzz_one(std::mt19937_64& rng, int n, int index) {
       if (!have_ref) { ref_jobs = jobs; have_ref = true; }
       else CHECK(jobs == ref_jobs, "the scheduled micro-ops differ from the first plan's (%zu vs %zu kinds)", jobs.size(), ref_jobs.size());
       if (adjoint) check_trainable_covered(c.m, plan, jobs);
+      else check_program_order(c.m, plan);
       (void)describe_plan(plan);
     }
   }
@@ -1379,6 +1428,7 @@ int main(int argc, char** argv) {
   }
   std::printf("plan_fuzz: %d cases (seed %llu), qubit counts", cases, (unsigned long long)seed);
   for (int n = 3; n <= n_max; ++n) std::printf(" %d:%d", n, by_n[n]);
-  std::printf("\nplan_fuzz: %d failures\n", g_failures);
+  std::printf("\nplan_fuzz: program orders shared=%ld programs_behind_pass_0=%ld\n", g_orders_shared, g_programs_behind_pass_0);
+  std::printf("plan_fuzz: %d failures\n", g_failures);
   return g_failures ? 1 : 0;
 }

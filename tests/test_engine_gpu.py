@@ -472,19 +472,25 @@ def test_parameter_shift_batches_states_and_programs():
       np.testing.assert_allclose(eng.expectation(bits, params).cpu().numpy(), want_vals, atol=1e-4)
 
 
-@pytest.mark.parametrize("n,layers,tile,kinds", [(13, 3, 10, "hea"), (14, 2, 10, "all kinds"), (15, 4, 11, "hea"), (16, 2, 0, "hea")])
+@pytest.mark.parametrize("n,layers,tile,kinds", [(13, 3, 10, "hea"), (14, 2, 10, "all kinds"), (15, 4, 11, "hea"), (16, 2, 0, "hea"),
+                                                 (13, 3, 10, "hea + unread gate")])
 def test_parameter_shift_programs_share_the_base_program_s_prefix_bit_for_bit(n, layers, tile, kinds):
   """A shifted program differs from the base program in ONE gate: it starts at the first pass that reads that gate's
   coefficients, from the base program's state (`shift_prefix_sharing`, default on; round 5's review, item 2 i).  The
   passes it skips would have computed the same bits, so gradient and values must EQUAL the unshared run bit for bit --
   values taken by the observable kernel (a wide random Pauli sum) and measured in the passes (TFIM, shards), tied
-  parameters, a gradient mask, launch sets cut by `chunk_states` -- and agree with the oracle's adjoint VJP."""
+  parameters, a gradient mask, launch sets cut by `chunk_states` -- and agree with the oracle's adjoint VJP.
+  "hea + unread gate": the circuit also holds a parametrised identity, a gate whose coefficients no record of any pass
+  reads, under the two layouts that decide where a program may start (shards: measurement-only passes behind the circuit;
+  TFIM + XXZ)."""
   from oracle import qhbm_cpu as C
   rng = np.random.default_rng(700 + n)
-  if kinds == "hea":
+  if kinds.startswith("hea"):
     gates, names = O.hea_gates(n, layers, "ps")
     n_params = len(names)
     gates = gates + [(O.GATE_XXPOW, 2, n - 3, 3, 0.7, 0.1), (O.GATE_ZZPOW, 0, n - 1, 5, -1.3, 0.0)]   # tied parameters
+    if kinds == "hea + unread gate":
+      gates = gates[:len(gates) // 2] + [(O.GATE_I, 4, -1, 2, 0.9, 0.2)] + gates[len(gates) // 2:]
   else:
     n_params = 9
     gates = random_circuit(rng, n, 60, n_params, kinds=[k for k in range(12) if k != O.GATE_ISWAPPOW])
@@ -493,6 +499,8 @@ def test_parameter_shift_programs_share_the_base_program_s_prefix_bit_for_bit(n,
   layouts = {"wide sum": [O.random_pauli_op(n, 40, n, p_identity=0.6)],
              "tfim + xxz": [O.tfim_ring_op(n), O.xxz_chain_op(n)],
              "shards": [[(1.0, 0, 1 << q)] for q in range(n)] + [[(0.5, 0, (1 << q) | (1 << ((q + 5) % n)))] for q in range(n)]}
+  if kinds == "hea + unread gate":
+    del layouts["wide sum"]
   mask = rng.random(n_params) < 0.6
   for name, ops in layouts.items():
     up = rng.normal(size=(3, len(ops))).astype(np.float32)

@@ -227,6 +227,46 @@ def test_prefix_sharing_with_a_diagonal_only_qubit():
     np.testing.assert_allclose(results[1][1][q].cpu().numpy(), want, atol=1e-4 * max(1.0, np.abs(want).max()))
 
 
+@pytest.mark.parametrize("ops_kind", ["shards", "tfim + xxz"])
+def test_prefix_sharing_with_programs_that_no_pass_reads(ops_kind):
+  """Programs whose shifted gate no record of any pass reads -- a parametrised identity, and the unshifted program
+  (a negative gate) -- start at the last pass that stores its state: never at a measurement-only pass (shards), never
+  behind the first measuring pass when the passes measure.  Sharing on equals sharing off bit for bit, launch sets
+  whole and cut, and both match the C oracle."""
+  from oracle import qhbm_cpu as C
+  n, tile = 13, 10
+  rng = np.random.default_rng(1300)
+  gates, names = O.hea_gates(n, 3, "nr")
+  n_params = len(names)
+  ident = len(gates) // 2
+  gates = gates[:ident] + [(E.GATE_I, 4, -1, 2, 0.9, 0.2)] + gates[ident:]
+  params = rng.uniform(-1, 1, n_params).astype(np.float32)
+  ops = {"shards": [[(1.0, 0, 1 << q)] for q in range(n)] + [[(0.5, 0, (1 << q) | (1 << ((q + 5) % n)))] for q in range(n)],
+         "tfim + xxz": [O.tfim_ring_op(n), O.xxz_chain_op(n)]}[ops_kind]
+  bits = rng.integers(0, 2, size=(3, n)).astype(np.int8)
+  up = rng.normal(size=(3, len(ops))).astype(np.float32)
+  live = [g for g, gate in enumerate(gates) if gate[3] >= 0 and g != ident]
+  sg = [live[0], ident, live[len(live) // 2], ident, live[-1], -1]
+  sv = [0.5, 0.5, -0.5, -0.5, 0.5, 0.0]
+  for chunk in (0, 5):
+    results = []
+    for sharing in (0, 1):
+      eng = _engine(n, gates, n_params, ops, tile_qubits=tile, adjoint_tile_qubits=tile, chunk_states=chunk,
+                    shift_prefix_sharing=sharing)
+      assert eng.num_passes()[0] > 1
+      eng.expectation(1 - bits, params)                  # leaves other states in the workspace
+      vals, grad = eng.program_vjps(bits, params, sg, sv, up)
+      results.append((vals.clone(), grad.clone()))
+    assert torch.equal(results[0][0], results[1][0]), chunk
+    assert torch.equal(results[0][1], results[1][1]), (chunk, float((results[0][1] - results[1][1]).abs().max()))
+    for q in (1, 2, 3, 5):
+      want_v, want = C.expectation_vjp(n, _shifted(gates, sg[q], sv[q]), params, bits, ops, up)
+      for vals, grad in results:
+        np.testing.assert_allclose(grad[q].cpu().numpy(), want, atol=1e-4 * max(1.0, np.abs(want).max()), err_msg=f"program {q}")
+        np.testing.assert_allclose(vals[q].cpu().numpy(), want_v.sum(0), atol=1e-4 * max(1.0, np.abs(want_v).max()),
+                                   err_msg=f"program {q}")
+
+
 def test_twenty_qubits_against_the_c_oracle():
   from oracle import qhbm_cpu as C
   n = 20

@@ -3,8 +3,9 @@
 tests/sanitize/plan_fuzz.cpp plans >= 2,000 random circuits over all twelve gate kinds x tile / relabel / wave-bit /
 FULL-threshold options at 3..28 qubits with planning-only engines (no device) and checks every plan structurally:
 every lowered micro-op scheduled exactly once, <= 384 gradient slots per adjoint pass and each written once, programs
-and tables inside their buffers, cost models finite, and a plan rebuilt after gradient-mask changes identical to a
-fresh engine's.  csrc/schedule.cpp and csrc/engine.cpp are compiled with -fsanitize=address,undefined (host only; GPU
+and tables inside their buffers, cost models finite, a plan rebuilt after gradient-mask changes identical to a
+fresh engine's, and the execution order of a batch of shifted programs on every forward plan (schedule.h order_programs: a
+permutation, no program behind the pass that reads its gate or behind the first measuring pass, every start pass storing).  csrc/schedule.cpp and csrc/engine.cpp are compiled with -fsanitize=address,undefined (host only; GPU
 sanitizers are not available on this pool): any report aborts the run.  A clean log is committed as
 profiles/r05_sanitizer_plan_fuzz.txt.
 
@@ -52,6 +53,11 @@ def test_scheduler_under_asan_and_ubsan_on_random_circuits():
   assert run.returncode == 0, tail
   assert f"plan_fuzz: {cases} cases" in run.stdout and "plan_fuzz: 0 failures" in run.stdout, tail
   assert "ERROR: AddressSanitizer" not in run.stderr and "runtime error" not in run.stderr, tail
+  # the program-order property met what it is about: plans that shared, programs that started behind pass 0
+  line = next(l for l in run.stdout.splitlines() if l.startswith("plan_fuzz: program orders"))
+  counts = {name: int(count) for name, count in (item.split("=") for item in line.split()[3:])}
+  assert set(counts) == {"shared", "programs_behind_pass_0"}, line
+  assert counts["shared"] > 0 and counts["programs_behind_pass_0"] > 0, line
 
 
 @pytest.mark.timeout(1500)
