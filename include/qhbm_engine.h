@@ -265,6 +265,40 @@ int qhbm_expectation_jacobian(qhbm_engine* h, const int8_t* d_bits, int U,
 int qhbm_statevector(qhbm_engine* h, const int8_t* d_bits, int U,
                      const float* d_params, void* d_out_states, void* stream);
 
+/* ---- Circuits that start from caller-supplied states (quantum data) ----
+ * Added WITHIN ABI version 5: purely additive, no existing entry point changes, QHBM_ABI_VERSION stays 5.
+ *
+ *   d_states [U, 2^n_qubits] complex64 as interleaved (re, im) floats (device, 16-byte aligned), the amplitude index
+ *   being the bitstring read big-endian: exactly what qhbm_statevector writes.  The buffer is only read, and must not
+ *   lie inside the engine's workspace (an error).  The states need not be normalised: the engine normalises its copy
+ *   (its values accumulate in fixed point on the premise ||psi|| = 1) and keeps ||phi_u||^2 on the device, so that
+ *   every output is the plain quadratic (values, gradients) or linear (states) function of the states AS GIVEN.  A
+ *   state of norm 0 gives zeros.
+ *
+ * The circuit runs on dense-start plans, kept beside the basis-state plans: built on the first such
+ * call, cached per gradient mask, invalidated by the same setters; qhbm_plan_builds and qhbm_num_passes keep
+ * reporting the basis-state plans.  chunk_states, workspace_budget_mb and profile_events apply as for the bits calls.
+ * Each call is "another compute call": it drops the states of qhbm_expectation_retain, and the VJP replaces the rows
+ * qhbm_state_gradients serves.
+ *
+ * OUT OF SCOPE from caller states: the parameter-shift method, the retain / vjp_retained pair, energy tables,
+ * sampling and qhbm_program_vjps.
+ *
+ *   qhbm_expectation_from_states       d_out[u, k] = <phi_u| C^dagger O_k C |phi_u>  (not divided by the norm)
+ *   qhbm_expectation_vjp_from_states   the adjoint method only: d_grad [n_params] = sum_{u,k} d_upstream[u, k] *
+ *                                      d(value[u, k]) / d(params), d_out_vals [U, n_ops] may be NULL; the gradient
+ *                                      mask applies as in qhbm_expectation_vjp
+ *   qhbm_statevector_from_states       d_out_states [U, 2^n_qubits] = C |phi_u>, global phase as qhbm_statevector
+ *                                      (16-byte aligned; observables need not be installed)
+ *   qhbm_describe_schedule_from_states the dense-start plans as text; works without a device */
+int qhbm_expectation_from_states(qhbm_engine* h, const void* d_states, int U, const float* d_params,
+                                 float* d_out, void* stream);
+int qhbm_expectation_vjp_from_states(qhbm_engine* h, const void* d_states, int U, const float* d_params,
+                                     const float* d_upstream, float* d_out_vals, float* d_grad, void* stream);
+int qhbm_statevector_from_states(qhbm_engine* h, const void* d_states, int U, const float* d_params,
+                                 void* d_out_states, void* stream);
+int qhbm_describe_schedule_from_states(qhbm_engine* h, char* buf, size_t buf_len);
+
 /* Computational-basis samples of the final states (tfq.layers.Sample as used at
  * qhbmlib/inference/qnn.py:169,177-181,286-291):
  *   d_out_samples [U, n_shots, n_qubits] int8 (device); shot j of state u is drawn from

@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -70,6 +71,28 @@ struct DevicePlan {
   }
 };
 
+// What follows from one pair of plans.  The engine holds two such sets: its own members (basis-state plans) and
+// qhbm_engine::dense (dense-start plans of the from-states calls); swap_plan_sets exchanges them, so every routine
+// below runs either set through the same members.
+// INVARIANT: every member of qhbm_engine that is derived from a plan -- built by build_plans, uploaded by upload_model or
+// upload_plan, or cached per gradient mask -- has a twin here AND a line in swap_plan_sets.  A plan-dependent member
+// added to the engine alone would carry the basis-state plans' data into a from-states call (and back).  What is
+// derived from the model alone (the observable tables: terms, obs_groups, obs_bterms, far windows, op_scale) is shared
+// by both sets, which is why upload_model's early return also asks for terms.p.
+struct PlanSet {
+  bool plans_valid = false, adj_valid = false, model_uploaded = false;
+  DevicePlan fwd, adj;
+  std::vector<std::pair<std::vector<char>, std::unique_ptr<DevicePlan>>> adj_cache;
+  int64_t fwd_plans_built = 0, adj_plans_built = 0;
+  DevBuf<DevTerm> global_terms;
+  DevBuf<int> param_slot_begin, param_slots;
+  DevBuf<float> slot_factor;
+  DevBuf<ShiftPhase> shift_phases;
+  int n_shift_phases = 0;
+  bool shift_ready = false;  // (the shift tables and coefficient copies follow the basis-state forward plan: parked here
+  size_t coef_batch_programs = 0;  // while the dense-start set is in, so that building it does not reset them)
+};
+
 struct TimedEvent {
   hipEvent_t a, b;
   int kind;  // 0 forward pass, 1 adjoint pass, 2 lambda = O psi
@@ -107,6 +130,7 @@ struct qhbm_engine {
   int64_t opt_budget_mb = 0;  // 0: a third of the device's memory, resolved at first use (budget_bytes)
   size_t resolved_budget = 0; // the default budget of THIS engine once a device query has succeeded
   // plans
+  // (everything below that follows from a plan is exchanged by swap_plan_sets with its twin in `dense`: see PlanSet's INVARIANT)
   bool plans_valid = false;
   bool adj_valid = false;  // the backward plan matches the gradient mask (qhbm_set_gradient_mask invalidates only this)
   // Backward plans (and their device copies) of the gradient masks this model has been used with: two inference paths
@@ -187,6 +211,18 @@ struct qhbm_engine {
   DevBuf<double> tab_vpart, tab_gpart, tab_carry, tab_gsum;
   std::vector<TimedEvent> events;
   std::vector<TimedEvent> free_events;
+  // Caller-supplied start states (qhbm_*_from_states).  Their plans (schedule.h Model::dense_input) are kept BESIDE the
+  // basis-state plans: built on the first such call, cached per gradient mask, invalidated by the same setters.  An
+  // engine that never makes such a call builds and allocates nothing of this.
+  PlanSet dense;
+  bool dense_active = false;      // the dense-start set is swapped into the members above (swap_plan_sets)
+  bool state_grad_dense = false;  // the rows in state_grad are a from-states VJP's (slots of the dense-start backward plan)
+  const float2* import_src = nullptr;     // during a from-states call: run_forward_chunk imports its chunk first
+  const float* import_upstream = nullptr; // ... and multiplies the chunk's upstream rows by ||phi||^2 into import_up
+  int import_U = 0;
+  DevBuf<double> import_parts, import_norm2;  // import_states.hip: scratch, ||phi_u||^2 [U]
+  DevBuf<float> import_up;                    // upstream rows times ||phi_u||^2
+  DevBuf<int8_t> import_bits;                 // zeros: the bitstrings the pass kernels are handed (no pass reads them)
 };
 
 namespace {
@@ -223,6 +259,13 @@ size_t own_bytes(const qhbm_engine* h) {
            size_t cached = 0;  // backward plans of other gradient masks, kept with their device copies (adj_cache)
            for (const auto& kv : h->adj_cache) cached += plan_bytes(*kv.second);
            return cached;
+         }() + [&] {  // the other plan set and the import's buffers (nothing before the first from-states call)
+           const PlanSet& o = h->dense;
+           size_t b = plan_bytes(o.fwd) + plan_bytes(o.adj) + buf_bytes(o.global_terms) + buf_bytes(o.param_slot_begin) +
+                      buf_bytes(o.param_slots) + buf_bytes(o.slot_factor) + buf_bytes(o.shift_phases) + buf_bytes(h->import_parts) +
+                      buf_bytes(h->import_norm2) + buf_bytes(h->import_up) + buf_bytes(h->import_bits);
+           for (const auto& kv : o.adj_cache) b += plan_bytes(*kv.second);
+           return b;
          }();
 }
 
@@ -233,9 +276,47 @@ size_t own_bytes(const qhbm_engine* h) {
 // new plan has more slots).  qhbm_set_gradient_mask drops both itself: it invalidates the backward plan alone.
 void invalidate_plans(qhbm_engine* h) {
   h->plans_valid = false;
+  h->dense.plans_valid = false;  // (the dense-start plans of the from-states calls: the same setters)
   h->retained_U = 0;
   h->state_grad_U = 0;
 }
+
+// Exchanges the basis-state plans and everything uploaded for them with the dense-start set (PlanSet), and plans for
+// the matching kind of start state from then on.
+void swap_plan_sets(qhbm_engine* h) {
+  PlanSet& o = h->dense;
+  std::swap(h->plans_valid, o.plans_valid);
+  std::swap(h->adj_valid, o.adj_valid);
+  std::swap(h->model_uploaded, o.model_uploaded);
+  h->fwd.swap(o.fwd);
+  h->adj.swap(o.adj);
+  h->adj_cache.swap(o.adj_cache);
+  std::swap(h->fwd_plans_built, o.fwd_plans_built);
+  std::swap(h->adj_plans_built, o.adj_plans_built);
+  swap_buf(h->global_terms, o.global_terms);
+  swap_buf(h->param_slot_begin, o.param_slot_begin);
+  swap_buf(h->param_slots, o.param_slots);
+  swap_buf(h->slot_factor, o.slot_factor);
+  swap_buf(h->shift_phases, o.shift_phases);
+  std::swap(h->n_shift_phases, o.n_shift_phases);
+  std::swap(h->shift_ready, o.shift_ready);
+  std::swap(h->coef_batch_programs, o.coef_batch_programs);
+  h->dense_active = !h->dense_active;
+  h->model.dense_input = h->dense_active;
+}
+
+// The dense-start set for the length of a from-states call.
+struct DenseScope {
+  qhbm_engine* h;
+  explicit DenseScope(qhbm_engine* e) : h(e) { swap_plan_sets(h); }
+  ~DenseScope() {
+    h->import_src = nullptr;
+    h->import_upstream = nullptr;
+    swap_plan_sets(h);
+  }
+  DenseScope(const DenseScope&) = delete;
+  DenseScope& operator=(const DenseScope&) = delete;
+};
 
 int need_device(qhbm_engine* h) {
   if (h->device < 0)
@@ -316,7 +397,7 @@ void qhbm::fill_args(const Plan& plan, const Model& m, std::vector<PassArgs>* ar
     }
     args->push_back(a);
   }
-  if (!plan.adjoint) {
+  if (!plan.adjoint && !plan.dense_input) {  // (a caller-supplied start state has no zeros to count on)
     // Amplitude-space pruning of the head of the forward sweep: an index bit no non-diagonal op has
     // acted on yet still equals the input bitstring wherever psi is non-zero.  A tile of pass p that
     // differs from the input on such a bit among its NON-LOCAL bits is identically zero, stays zero
@@ -529,7 +610,8 @@ int upload_model(qhbm_engine* h) {
     h->terms.release();
     h->model_uploaded = false;
   }
-  if (h->model_uploaded) return 0;
+  // (the observable tables serve both plan sets: whoever released them -- an option, new observables -- is seen by either)
+  if (h->model_uploaded && h->terms.p) return 0;
   if (int rc = upload_plan(h, &h->fwd)) return rc;
   if (int rc = upload_plan(h, &h->adj)) return rc;
   if (!h->terms.p) {
@@ -930,10 +1012,40 @@ PassArgs forward_pass_args(const qhbm_engine* h, size_t i, bool keep_state, bool
   return a;
 }
 
+// Does [p, p + bytes) meet the statevector workspace?
+bool aliases_workspace(const qhbm_engine* h, const void* p, size_t bytes) {
+  const char* a = static_cast<const char*>(p);
+  auto meets = [&](const DevBuf<float2>& b) {
+    const char* w = reinterpret_cast<const char*>(b.p);
+    return b.p && a < w + b.n * sizeof(float2) && w < a + bytes;
+  };
+  return meets(h->psi) || meets(h->lam);
+}
+
+// From-states calls: states s0 .. s0 + c of the caller's batch, normalised, into the workspace (import_states.hip);
+// their squared norms into import_norm2, and the chunk's upstream rows times those into import_up.
+int import_chunk(qhbm_engine* h, uint32_t s0, uint32_t c, hipStream_t stream) {
+  const uint32_t n = uint32_t(h->model.n), n_eff = uint32_t(h->fwd.plan.n_eff);
+  if (aliases_workspace(h, h->import_src, size_t(h->import_U) * (size_t(8) << n)))
+    return fail(h, "d_states lies inside the engine's workspace");
+  HIPCHK(h->import_parts.reserve(import_norm_parts_count(n, c)));
+  hipEvent_t* ev = timer_begin(h, 0, stream);  // (profile_events: the import counts as a launch of the forward sweep)
+  HIPCHK(launch_import_states(h->import_src, n, n_eff, c, s0, h->psi.p, h->import_parts.p, h->import_norm2.p, stream));
+  timer_end(ev, stream);
+  if (h->import_upstream) {
+    const size_t w = size_t(h->model.n_ops);
+    HIPCHK(launch_scale_by_norm2(h->import_upstream + size_t(s0) * w, h->import_up.p + size_t(s0) * w, c, uint32_t(w),
+                                 h->import_norm2.p + s0, stream));
+  }
+  return 0;
+}
+
 // Forward passes for one chunk (`keep_state`, `skip_measure`: forward_pass_args).
 int run_forward_chunk(qhbm_engine* h, const int8_t* d_bits, uint32_t s0, uint32_t cs, bool keep_state,
                       hipStream_t stream, bool skip_measure = false) {
   DevicePlan& d = h->fwd;
+  if (h->import_src)  // a from-states call: the chunk's start states come from the caller
+    if (int rc = import_chunk(h, s0, cs, stream)) return rc;
   for (size_t i = 0; i < d.plan.passes.size(); ++i) {
     const Pass& p = d.plan.passes[i];
     if (skip_measure && p.is_measure_only) continue;
@@ -1371,6 +1483,7 @@ int table_vjp(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params
   HIPCHK(launch_reduce_grad(h->state_grad.p, uint32_t(U), n_slots, h->param_slot_begin.p, h->param_slots.p,
                             h->slot_factor.p, d_grad, P, 0, s));
   h->state_grad_U = U;
+  h->state_grad_dense = false;
   if (d_table_grad) HIPCHK(launch_doubles_to_floats(h->tab_gsum.p, d_table_grad, dim, s));
   return 0;
 }
@@ -1452,21 +1565,28 @@ int qhbm_set_gradient_mask(qhbm_engine* h, const uint8_t* needs_grad, int n_para
   }
   if (frozen != h->model.param_frozen) {
     // the backward plan and the shift tables depend on the mask; the forward plan does not
-    if (h->plans_valid && h->adj_valid) {  // keep the plan of the mask that is leaving (at most four)
-      if (h->adj_cache.size() >= 4) h->adj_cache.erase(h->adj_cache.begin());
-      h->adj_cache.emplace_back(h->model.param_frozen, std::unique_ptr<DevicePlan>(new DevicePlan()));
-      h->adj_cache.back().second->swap(h->adj);
-    }
-    h->model.param_frozen = std::move(frozen);
-    h->adj_valid = false;
-    for (size_t i = 0; i < h->adj_cache.size(); ++i)
-      if (h->plans_valid && h->adj_cache[i].first == h->model.param_frozen) {  // seen before: swap it back in
-        h->adj.swap(*h->adj_cache[i].second);
-        h->adj_cache.erase(h->adj_cache.begin() + long(i));
-        h->adj_valid = true;
-        h->model_uploaded = false;  // (the parameter -> slot tables follow the plan: a few KiB, no planning)
-        break;
+    const std::vector<char> leaving = h->model.param_frozen;
+    auto retarget = [&]() {  // the backward plan of the plan set that is in
+      if (h->plans_valid && h->adj_valid) {  // keep the plan of the mask that is leaving (at most four)
+        if (h->adj_cache.size() >= 4) h->adj_cache.erase(h->adj_cache.begin());
+        h->adj_cache.emplace_back(leaving, std::unique_ptr<DevicePlan>(new DevicePlan()));
+        h->adj_cache.back().second->swap(h->adj);
       }
+      h->adj_valid = false;
+      for (size_t i = 0; i < h->adj_cache.size(); ++i)
+        if (h->plans_valid && h->adj_cache[i].first == frozen) {  // seen before: swap it back in
+          h->adj.swap(*h->adj_cache[i].second);
+          h->adj_cache.erase(h->adj_cache.begin() + long(i));
+          h->adj_valid = true;
+          h->model_uploaded = false;  // (the parameter -> slot tables follow the plan: a few KiB, no planning)
+          break;
+        }
+    };
+    retarget();
+    swap_plan_sets(h);  // ... and of the dense-start set (nothing to do before the first from-states call)
+    retarget();
+    swap_plan_sets(h);
+    h->model.param_frozen = std::move(frozen);
     h->shift_ready = false;
     h->retained_U = 0;
     h->state_grad_U = 0;
@@ -1528,7 +1648,7 @@ int qhbm_set_option(qhbm_engine* h, const char* name, int64_t value) {
   else if (k == "adjoint_full_diag_threshold") { h->opt_full_adj = int(value); invalidate_plans(h); }
   else if (k == "adjoint_tile_qubits") { h->opt_adj_tile = int(value); invalidate_plans(h); }
   else if (k == "adjoint_exchange") { h->opt_adj_exchange = int(value); invalidate_plans(h); }
-  else if (k == "x_two_shear") { h->opt_x_two_shear = value != 0; invalidate_plans(h); h->adj_cache.clear(); }
+  else if (k == "x_two_shear") { h->opt_x_two_shear = value != 0; invalidate_plans(h); h->adj_cache.clear(); h->dense.adj_cache.clear(); }
   else if (k == "adjoint_relabel") { h->opt_adj_relabel = int(value); invalidate_plans(h); }
   else if (k == "forward_pairs") h->opt_fwd_pair = int(value);
   else if (k == "shift_prefix_sharing") { h->opt_shift_prefix = int(value); h->shift_ready = false; }
@@ -1642,12 +1762,16 @@ int qhbm_expectation_vjp_retained(qhbm_engine* h, const int8_t* d_bits, int U, c
   HIPCHK(launch_reduce_grad(h->state_grad.p, uint32_t(U), n_slots, h->param_slot_begin.p, h->param_slots.p,
                             h->slot_factor.p, d_grad, h->model.n_params, 0, s));
   h->state_grad_U = U;
+  h->state_grad_dense = false;
   return 0;
 }
 
 int qhbm_state_gradients(qhbm_engine* h, int U, float* d_rows, void* stream) {
   if (!h || !d_rows) return 1;
   if (int rc = need_device(h)) return rc;
+  // (rows of a from-states VJP: the slots are those of the dense-start backward plan)
+  std::optional<DenseScope> scope;
+  if (h->state_grad_dense && h->state_grad_U > 0) scope.emplace(h);
   if (U <= 0 || U != h->state_grad_U || !h->plans_valid || !h->adj_valid)
     return fail(h, "qhbm_state_gradients: the last call was not an adjoint VJP on this many states");
   HIPCHK(launch_scatter_jac(h->state_grad.p, uint32_t(U), uint32_t(h->adj.plan.slot_gate.size()),
@@ -1685,6 +1809,132 @@ int qhbm_statevector(qhbm_engine* h, const int8_t* d_bits, int U, const float* d
   HIPCHK(launch_global_phase(d.jobs.p, int(d.plan.jobs.size()), h->shift_phases.p, h->n_shift_phases, d_params,
                              h->phase_cs.p, s));
   HIPCHK(launch_scale_states(static_cast<float2*>(d_out_states), size_t(U) << h->model.n, h->phase_cs.p, s));
+  return 0;
+}
+
+// ---- caller-supplied start states (include/qhbm_engine.h): the same sweeps on the dense-start plan set, the chunk's
+// states imported by run_forward_chunk (import_chunk) ----
+}  // extern "C"
+
+namespace {
+
+// Argument checks of a from-states call, before the plan sets are exchanged.
+int check_states_call(qhbm_engine* h, const void* d_states, int U, bool need_observables) {
+  if (!h) return 1;
+  if (int rc = need_device(h)) return rc;
+  if (U < 0) return fail(h, "negative batch size");
+  if (!h->have_circuit) return fail(h, "qhbm_set_circuit has not been called");
+  if (need_observables && h->model.n_ops <= 0) return fail(h, "qhbm_set_observables has not been called");
+  if (U > 0 && !d_states) return fail(h, "d_states is NULL");
+  if (U > 0 && (reinterpret_cast<uintptr_t>(d_states) & 15u)) return fail(h, "d_states must be 16-byte aligned");
+  if (U > 0 && aliases_workspace(h, d_states, size_t(U) * (size_t(8) << h->model.n)))
+    return fail(h, "d_states lies inside the engine's workspace");
+  return 0;
+}
+
+// The import's per-call buffers; from here on run_forward_chunk imports (the DenseScope of the call ends that).
+int begin_import(qhbm_engine* h, const void* d_states, int U, const float* d_upstream, hipStream_t stream) {
+  HIPCHK(h->import_norm2.reserve(size_t(U)));
+  const size_t nb = (size_t(U) * size_t(h->model.n) + 15u) & ~size_t(15);
+  if (nb > h->import_bits.n) {
+    HIPCHK(h->import_bits.reserve(nb, false));
+    HIPCHK(launch_zero_fill(h->import_bits.p, h->import_bits.n, stream));
+  }
+  if (d_upstream) HIPCHK(h->import_up.reserve(size_t(U) * size_t(h->model.n_ops)));
+  h->import_src = static_cast<const float2*>(d_states);
+  h->import_upstream = d_upstream;
+  h->import_U = U;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qhbm_expectation_from_states(qhbm_engine* h, const void* d_states, int U, const float* d_params, float* d_out,
+                                 void* stream) {
+  if (int rc = check_states_call(h, d_states, U, true)) return rc;
+  DenseScope scope(h);
+  if (int rc = upload_model(h)) return rc;
+  if (U == 0) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = begin_import(h, d_states, U, nullptr, s)) return rc;
+  if (int rc = forward(h, h->import_bits.p, U, d_params, d_out, -1, 0.0, s)) return rc;
+  // the sweep ran on phi / ||phi||: the values of the states as given
+  if (d_out) HIPCHK(launch_scale_by_norm2(d_out, d_out, uint32_t(U), uint32_t(h->model.n_ops), h->import_norm2.p, s));
+  return 0;
+}
+
+int qhbm_expectation_vjp_from_states(qhbm_engine* h, const void* d_states, int U, const float* d_params,
+                                     const float* d_upstream, float* d_out_vals, float* d_grad, void* stream) {
+  if (int rc = check_states_call(h, d_states, U, true)) return rc;
+  if (!d_grad || (U > 0 && !d_upstream)) return fail(h, "d_upstream or d_grad is NULL");
+  DenseScope scope(h);
+  if (int rc = upload_model(h)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int P = h->model.n_params;
+  if (U == 0) {
+    if (P) HIPCHK(launch_zero_fill(d_grad, size_t(P) * sizeof(float), s));
+    return 0;
+  }
+  if (!d_out_vals) {
+    HIPCHK(h->vals_tmp.reserve(size_t(U) * size_t(h->model.n_ops)));
+    d_out_vals = h->vals_tmp.p;
+  }
+  if (int rc = begin_import(h, d_states, U, d_upstream, s)) return rc;
+  // lambda = sum_k (upstream[u, k] ||phi_u||^2) O_k psi_u on the normalised psi_u: the gradient of the states as given
+  if (int rc = adjoint_sweep(h, h->import_bits.p, U, d_params, h->import_up.p, d_out_vals, s)) return rc;
+  HIPCHK(launch_scale_by_norm2(d_out_vals, d_out_vals, uint32_t(U), uint32_t(h->model.n_ops), h->import_norm2.p, s));
+  HIPCHK(launch_reduce_grad(h->state_grad.p, uint32_t(U), uint32_t(h->adj.plan.slot_gate.size()), h->param_slot_begin.p,
+                            h->param_slots.p, h->slot_factor.p, d_grad, P, 0, s));
+  h->state_grad_U = U;
+  h->state_grad_dense = true;
+  return 0;
+}
+
+int qhbm_statevector_from_states(qhbm_engine* h, const void* d_states, int U, const float* d_params, void* d_out_states,
+                                 void* stream) {
+  if (int rc = check_states_call(h, d_states, U, false)) return rc;
+  if (U > 0 && !d_out_states) return fail(h, "d_out_states is NULL");
+  if (reinterpret_cast<uintptr_t>(d_out_states) & 15u) return fail(h, "d_out_states must be 16-byte aligned");
+  DenseScope scope(h);
+  if (int rc = upload_model(h)) return rc;
+  if (U == 0) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DevicePlan& d = h->fwd;
+  h->retained_U = 0;
+  if (int rc = begin_import(h, d_states, U, nullptr, s)) return rc;
+  if (int rc = prepare_coefs(h, d, d_params, -1, 0.0, s)) return rc;
+  if (int rc = values_begin(h, U, s)) return rc;  // (by-product values of installed observables stay in the scratch)
+  const uint32_t cs = chunk_states(h, U);
+  if (int rc = ensure_state_buffers(h, cs, false)) return rc;
+  const size_t row = size_t(8) << h->model.n, pitch = size_t(8) << d.plan.n_eff;
+  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += cs) {
+    const uint32_t c = std::min<uint32_t>(cs, uint32_t(U) - s0);
+    // (a circuit without gates: the imported states are the result.  The plan's one pass would load and store them
+    // unchanged; it is skipped -- and with it the by-product values of installed observables, which nobody can read --
+    // so that the forward events of such a call time the import alone: scripts/from_states_time.py measures it this way)
+    if (int rc = h->model.gates.empty() ? import_chunk(h, s0, c, s) : run_forward_chunk(h, h->import_bits.p, s0, c, true, s)) return rc;
+    char* out = static_cast<char*>(d_out_states) + size_t(s0) * row;
+    HIPCHK(hipMemcpy2DAsync(out, row, h->psi.p, pitch, row, c, hipMemcpyDeviceToDevice, s));
+    HIPCHK(launch_scale_state_rows(reinterpret_cast<float2*>(out), c, uint32_t(h->model.n), h->import_norm2.p + s0, s));
+  }
+  HIPCHK(h->phase_cs.reserve(2));  // the global phase the kernels leave out, as qhbm_statevector restores it
+  HIPCHK(launch_global_phase(d.jobs.p, int(d.plan.jobs.size()), h->shift_phases.p, h->n_shift_phases, d_params,
+                             h->phase_cs.p, s));
+  HIPCHK(launch_scale_states(static_cast<float2*>(d_out_states), size_t(U) << h->model.n, h->phase_cs.p, s));
+  return 0;
+}
+
+int qhbm_describe_schedule_from_states(qhbm_engine* h, char* buf, size_t buf_len) {
+  if (!h || !buf || !buf_len) return 1;
+  DenseScope scope(h);
+  if (int rc = build_plans(h)) return rc;
+  std::string s = describe_plan(h->fwd.plan) + describe_plan(h->adj.plan);
+  char line[96];
+  std::snprintf(line, sizeof(line), "adjoint time model: %.2f us per state\n", 1e6 * adjoint_plan_seconds(h->adj.plan, h->model));
+  s += line;
+  std::snprintf(buf, buf_len, "%s", s.c_str());
   return 0;
 }
 
@@ -1893,6 +2143,7 @@ int qhbm_expectation_vjp(qhbm_engine* h, const int8_t* d_bits, int U, const floa
     HIPCHK(launch_reduce_grad(h->state_grad.p, uint32_t(U), uint32_t(h->adj.plan.slot_gate.size()),
                               h->param_slot_begin.p, h->param_slots.p, h->slot_factor.p, d_grad, P, 0, s));
     h->state_grad_U = U;
+    h->state_grad_dense = false;
     return 0;
   }
   if (method != QHBM_GRAD_PARAMETER_SHIFT) return fail(h, "unknown gradient method");

@@ -245,4 +245,18 @@ hipError_t launch_energy_table(int mode, const float2* psi, float2* lam, const f
                                uint32_t c, uint32_t s0, uint32_t U, const float* upstream, double* vpart, float* d_out,
                                double* gpart, double* carry, double* gsum, hipStream_t stream);
 
+// ---- caller-supplied start states (import_states.hip) ----
+// Doubles of scratch (`parts`) the import of a chunk of c states of n qubits needs.
+size_t import_norm_parts_count(uint32_t n, uint32_t c);
+// Input states s0 .. s0 + c of `src` ([., 2^n] complex64, read only, 16-byte aligned): norm2[s0 + i] = ||phi||^2 in fp64
+// (fixed order, no atomics), psi element i = phi / ||phi|| at a pitch of 2^n_eff amplitudes, zeros in the padding and
+// for a state of norm 0.  Reads the input twice.
+hipError_t launch_import_states(const float2* src, uint32_t n, uint32_t n_eff, uint32_t c, uint32_t s0, float2* psi,
+                                double* parts, double* norm2, hipStream_t stream);
+// out[r, k] = in[r, k] * norm2[r] (in == out allowed)
+hipError_t launch_scale_by_norm2(const float* in, float* out, uint32_t rows, uint32_t width, const double* norm2,
+                                 hipStream_t stream);
+// st[r, :] *= sqrt(norm2[r]) for `rows` (<= 65535) states of 2^n amplitudes
+hipError_t launch_scale_state_rows(float2* st, uint32_t rows, uint32_t n, const double* norm2, hipStream_t stream);
+
 }  // namespace qhbm

@@ -692,3 +692,5 @@ hipError_t launch_observable_blocks(int mode, int block_bits, const float2* psi,
 // in the source tree and part of this object: the engine links against exactly kernels.o and observable.o, also in the
 // planning-only host build of tests/sanitize.
 #include "energy_table.hip"
+// ... and so is the import of caller-supplied start states.
+#include "import_states.hip"

@@ -870,6 +870,7 @@ bool build_plan(const Model& m, int tile_bits, int round_bits, bool adjoint, Pla
   plan->K = K;
   plan->R = R;
   plan->adjoint = adjoint;
+  plan->dense_input = m.dense_input;
 
   std::vector<LoweredOp> ops;
   if (!lower(m, &ops, err, &plan->const_phase, &plan->gate_phases)) return false;
@@ -888,6 +889,8 @@ bool build_plan(const Model& m, int tile_bits, int round_bits, bool adjoint, Pla
       if (mixes) { always_pending = (1u << std::max(m.n, kMinTileBits)) - 1u; plan->dense_tail = true; }
     }
   }
+  // A caller-supplied start state (Model::dense_input) is no basis state either, wherever the sweep stops.
+  if (adjoint && m.dense_input) { always_pending = (1u << std::max(m.n, kMinTileBits)) - 1u; plan->dense_tail = true; }
   std::vector<int> order(ops.size());
   for (size_t i = 0; i < ops.size(); ++i) order[i] = adjoint ? int(ops.size() - 1 - i) : int(i);
 
@@ -1382,14 +1385,16 @@ bool build_plan(const Model& m, int tile_bits, int round_bits, bool adjoint, Pla
     const uint32_t S = K >= n_eff ? all_bits : ((1u << K) - 1);
     plan->passes.push_back(b.begin_pass(S));
   }
-  plan->passes.front().flags |= PASS_INIT_BASIS;
+  // (Model::dense_input: the first pass loads the caller's state like any later pass, every tile of it, and no
+  // pass may count on zeros off the input bitstring -- none of the flags and masks below)
+  if (!m.dense_input) plan->passes.front().flags |= PASS_INIT_BASIS;
   plan->passes.back().completes_circuit = true;
   // The first pass writes the basis state: ONE tile per state is not zero.  If every index bit is acted on
   // by some non-diagonal gate, the other tiles need not be written at all: a later pass skips the tiles that
   // differ from the input on a bit nothing has acted on yet (engine.cpp fill_args: zero_mask), and clears,
   // when it loads a tile, the amplitudes that differ on such a bit among its LOCAL bits -- the only places
   // never written before.  (With an idle bit the final state would keep unwritten regions: zeros are filled.)
-  if (plan->passes.size() > 1 && ever_mat == all_bits) {
+  if (!m.dense_input && plan->passes.size() > 1 && ever_mat == all_bits) {
     plan->passes.front().flags |= PASS_NO_ZERO_FILL;
     uint32_t touched = plan->passes.front().mat_bits;
     for (size_t i = 1; i < plan->passes.size(); ++i) {
@@ -1551,6 +1556,7 @@ std::string describe_plan(const Plan& p) {
        << (q.is_measure_only ? " [measure-only]" : "");
     // the first forward pass writes one tile per state, or zero-fills every tile (an index bit no non-diagonal op acts on)
     if (!p.adjoint && (q.flags & PASS_INIT_BASIS)) os << ((q.flags & PASS_NO_ZERO_FILL) ? " [basis tile only]" : " [zero-fill]");
+    if (!p.adjoint && p.dense_input && i == 0) os << " [loads caller states]";
     os << " words=" << q.prog.size() << " regs=";
     for (size_t r = 0; r < q.round_regmasks.size(); ++r) os << (r ? "," : "") << std::hex << q.round_regmasks[r] << std::dec;
     if (p.relabel) {

@@ -118,6 +118,9 @@ struct Plan {
   // adjoint plans of a model with frozen leading gates: the sweep ends at an intermediate state of the circuit, not
   // at the basis state -- no index bit ever "finishes", nothing is pruned (engine.cpp fill_args)
   bool dense_tail = false;
+  // plans of a model with Model::dense_input: the sweep starts from (forward) or ends at (adjoint) a caller-supplied
+  // state in HBM -- no pass writes a basis state, and nothing is pruned on zeros of psi (engine.cpp fill_args)
+  bool dense_input = false;
   // constant global phase, in units of pi, that the lowering of constant Hadamards / CNOTs owes the exported state
   // (schedule.cpp lower(): -1/4 per lowered H)
   double const_phase = 0.0;
@@ -136,6 +139,9 @@ struct Model {
   bool frozen(int param_idx) const { return param_idx >= 0 && size_t(param_idx) < param_frozen.size() && param_frozen[size_t(param_idx)]; }
   int n_ops = 0;
   std::vector<PauliTerm> terms;
+  // The circuit starts from a state the caller put into the workspace (qhbm_*_from_states), not from |bits>: the
+  // forward plan loads its first tiles and prunes nothing, the backward plan keeps every index bit pending
+  bool dense_input = false;
 };
 
 // Tile geometry for a given tile size.

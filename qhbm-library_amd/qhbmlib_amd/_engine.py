@@ -44,6 +44,8 @@ ABI_SYMBOLS = (
     "qhbm_kernel_time_ms", "qhbm_traffic_model", "qhbm_flop_model", "qhbm_op_census", "qhbm_clock_probe", "qhbm_plan_builds",
     "qhbm_table_expectation", "qhbm_table_expectation_retain", "qhbm_table_expectation_vjp",
     "qhbm_table_expectation_vjp_retained",
+    "qhbm_expectation_from_states", "qhbm_expectation_vjp_from_states", "qhbm_statevector_from_states",
+    "qhbm_describe_schedule_from_states",
 )
 
 
@@ -129,6 +131,10 @@ def load_library():
     lib.qhbm_table_expectation_retain.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     lib.qhbm_table_expectation_vjp.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.qhbm_table_expectation_vjp_retained.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.qhbm_expectation_from_states.argtypes = [vp, vp, i32, vp, vp, vp]
+    lib.qhbm_expectation_vjp_from_states.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.qhbm_statevector_from_states.argtypes = [vp, vp, i32, vp, vp, vp]
+    lib.qhbm_describe_schedule_from_states.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t]
   except AttributeError:  # an older library given through QHBM_ENGINE_LIB (A/B runs): the probe is optional there
     pass
   _lib = lib
@@ -640,6 +646,66 @@ class Engine:
           self._lib.qhbm_statevector(self._h, bits.data_ptr(), bits.shape[0],
                                      params.data_ptr(), out.data_ptr(),
                                      self._stream()))
+    return out
+
+  # ---- circuits that start from caller-supplied states (include/qhbm_engine.h) ----
+  def describe_schedule_from_states(self):
+    """The dense-start plans the from-states calls run (works without a device)."""
+    buf = ctypes.create_string_buffer(1 << 16)
+    self._check(self._lib.qhbm_describe_schedule_from_states(self._h, buf, len(buf)))
+    return buf.value.decode()
+
+  def _prep_states(self, states, params):
+    if self.device is None:
+      raise EngineError("planning-only engine: no device, no CPU fallback")
+    states = torch.as_tensor(states)
+    if not states.is_complex():
+      raise ValueError("states must be a complex tensor of shape [batch, 2^n]")
+    if states.dim() != 2 or states.shape[1] != (1 << self.n_qubits):
+      raise ValueError(f"states must have shape [batch, {1 << self.n_qubits}], got {tuple(states.shape)}")
+    states = states.to(device=self.device, dtype=torch.complex64).contiguous()
+    if states.data_ptr() % 16:  # (a view at an odd offset: the import loads 16-byte words)
+      states = states.clone()
+    params = torch.as_tensor(params).to(device=self.device, dtype=torch.float32).contiguous()
+    if params.numel() != self.n_params:
+      raise ValueError(f"expected {self.n_params} parameters")
+    return states, params
+
+  def expectation_from_states(self, states, params):
+    """Values [batch, n_ops] of <phi_u| C^dagger O_k C |phi_u> for states [batch, 2^n] complex64 in the layout of
+    `statevector`; not divided by the norm, the input is never written."""
+    states, params = self._prep_states(states, params)
+    out = torch.empty((states.shape[0], self.n_ops), dtype=torch.float32, device=self.device)
+    self.retained = None
+    with torch.cuda.device(self.device):
+      self._check(self._lib.qhbm_expectation_from_states(self._h, states.data_ptr(), states.shape[0], params.data_ptr(),
+                                                         out.data_ptr(), self._stream()))
+    return out
+
+  def expectation_vjp_from_states(self, states, params, upstream):
+    """(vals [batch, n_ops], grad [n_params]) by the adjoint method; the gradient mask applies as in
+    `expectation_vjp`, and `state_gradients` then serves this call's rows."""
+    states, params = self._prep_states(states, params)
+    upstream = torch.as_tensor(upstream).to(device=self.device, dtype=torch.float32).contiguous()
+    if tuple(upstream.shape) != (states.shape[0], self.n_ops):
+      raise ValueError("upstream must have shape [batch, n_ops]")
+    vals = torch.empty((states.shape[0], self.n_ops), dtype=torch.float32, device=self.device)
+    grad = torch.zeros((self.n_params,), dtype=torch.float32, device=self.device)
+    self.retained = None
+    with torch.cuda.device(self.device):
+      self._check(self._lib.qhbm_expectation_vjp_from_states(
+          self._h, states.data_ptr(), states.shape[0], params.data_ptr(), upstream.data_ptr(), vals.data_ptr(),
+          grad.data_ptr(), self._stream()))
+    return vals, grad
+
+  def statevector_from_states(self, states, params):
+    """C(params)|phi_u>, complex64 [batch, 2^n], global phase as `statevector`."""
+    states, params = self._prep_states(states, params)
+    out = torch.empty((states.shape[0], 1 << self.n_qubits), dtype=torch.complex64, device=self.device)
+    self.retained = None
+    with torch.cuda.device(self.device):
+      self._check(self._lib.qhbm_statevector_from_states(self._h, states.data_ptr(), states.shape[0], params.data_ptr(),
+                                                         out.data_ptr(), self._stream()))
     return out
 
   def sample(self, bits, params, n_shots, seed=0, shift_gate=-1, shift=0.0):

@@ -89,6 +89,26 @@ class _ExpectationFunction(torch.autograd.Function):
     return grad.to(symbol_values.device), None, None, None, None, None, None, None
 
 
+class _StatesExpectationFunction(torch.autograd.Function):
+  """values[M, T] = <phi_m| C^dagger O_t C |phi_m> for caller-supplied states (qhbm_expectation_from_states);
+  backward = the adjoint VJP from the same states (qhbm_expectation_vjp_from_states).  No gradient reaches `states`."""
+
+  @staticmethod
+  def forward(ctx, symbol_values, engine, states, grad_mask=None):
+    ctx.engine, ctx.states = engine, states
+    ctx.grad_mask = None if grad_mask is None or all(grad_mask) else tuple(bool(f) for f in grad_mask)
+    ctx.save_for_backward(symbol_values)
+    return engine.expectation_from_states(states, symbol_values.detach())
+
+  @staticmethod
+  def backward(ctx, upstream):
+    (symbol_values,) = ctx.saved_tensors
+    eng = ctx.engine
+    eng.set_gradient_mask(ctx.grad_mask)  # (a no-op unless another call on this engine set another one)
+    _, grad = eng.expectation_vjp_from_states(ctx.states, symbol_values.detach(), upstream.contiguous())
+    return grad.to(symbol_values.device), None, None, None
+
+
 class _TableExpectationFunction(torch.autograd.Function):
   """values[U, 1] = <x_u| C^dagger diag(table) C |x_u> (qhbm_table_expectation); backward = the table VJP: lambda =
   upstream * table * psi, the adjoint sweep, and d/d table[y] = sum_u upstream_u |psi_u[y]|^2 -- autograd carries the
@@ -419,6 +439,51 @@ class AnalyticQuantumInference(QuantumInference):
         grad_mask = None
       parts.append(_ExpectationFunction.apply(values, eng, bits, self.gradient_method, group, self.ordered_reduction,
                                               grad_mask, self.shard_weights))
+    expectations = parts[0] if len(parts) == 1 else torch.cat(parts, 1)
+    return post_process(expectations)
+
+
+  def expectation_from_states(self, states: torch.Tensor, observables: Observables):
+    """[M, n_ops] of <phi_m| C^dagger O_j C |phi_m> for quantum DATA: `states` is [M, 2^n] complex64 (complex128 is
+    cast) in the row order of `qnn_utils.unitary` -- amplitude index = the bitstring read big-endian over the total
+    circuit's qubits, what `qhbm_statevector` writes.  The values are not divided by the states' norms.
+
+    `observables` as in `expectation`: a list of PauliSums, or a Hamiltonian with a Pauli-form energy (U^dagger is
+    appended, the shards are measured, `operator_expectation` is applied).  Differentiable with respect to the
+    variables of this inference's circuit and of the Hamiltonian's circuit and energy (adjoint VJP in the engine),
+    not with respect to `states`."""
+    states = torch.as_tensor(states)
+    if states.requires_grad:
+      raise ValueError("expectation_from_states is not differentiable with respect to `states`: pass states.detach()")
+    if self._group() is not None:
+      raise ValueError("expectation_from_states is not sharded yet: use an inference without a process_group")
+    if isinstance(observables, hamiltonian.Hamiltonian):
+      if not isinstance(observables.energy, energy.PauliMixin):
+        raise TypeError("General Hamiltonians not accepted.  "
+                        "Please use `SampledQuantumInference` instead.")
+      total_circuit = self.circuit + observables.circuit_dagger
+      ops = observables.operator_shards
+      post_process = lambda y: observables.energy.operator_expectation(y).unsqueeze(-1)
+    else:
+      total_circuit = self.circuit
+      ops = list(observables)
+      post_process = lambda x: x
+    qubits = total_circuit.qubits
+    if not states.is_complex() or states.dim() != 2 or states.shape[1] != (1 << len(qubits)):
+      raise ValueError(f"states must be a complex tensor of shape [M, {1 << len(qubits)}] "
+                       f"({len(qubits)} qubits), got {states.dtype} {tuple(states.shape)}")
+    values, flags = total_circuit.symbol_values_and_flags()
+    symbol_names = total_circuit.symbol_names
+    grad_mask = flags if values.requires_grad and len(flags) == len(symbol_names) else None
+    values = values.to(torch.float32)
+    flat_gates = total_circuit.pqc.flat_gates(qubits, list(symbol_names))
+    parts = []
+    for lo in range(0, max(len(ops), 1), self.MAX_OPS_PER_CALL):
+      masks = [ir.as_pauli_sum(op).masks(qubits) for op in ops[lo:lo + self.MAX_OPS_PER_CALL]]
+      eng = self._engine_for(len(qubits), flat_gates, len(symbol_names), masks)
+      if not parts:  # (one copy on the engine's device serves every slice)
+        states = states.detach().to(device=eng.device, dtype=torch.complex64).contiguous()
+      parts.append(_StatesExpectationFunction.apply(values, eng, states, grad_mask))
     expectations = parts[0] if len(parts) == 1 else torch.cat(parts, 1)
     return post_process(expectations)
 
