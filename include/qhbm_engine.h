@@ -478,10 +478,18 @@ enum {
   QHBM_CENSUS_CPH_WAVE_ON,       /* predicate = thread bit that is uniform over the wave, on */
   QHBM_CENSUS_CPH_LANE,          /* predicate varies inside the wave */
   QHBM_CENSUS_CPH_OFF,           /* predicate evaluated, off in the whole wave */
-  QHBM_CENSUS_REDUCE8,           /* adjoint: eight-wide wave reductions of gradient partials */
+  QHBM_CENSUS_REDUCE8,           /* adjoint: eight-wide wave reductions of gradient partials: sets that have a value */
+  QHBM_CENSUS_LEVEL1,            /* adjoint: level-1 adds of those reductions, issued where a partial is made: one per
+                                    header bit of a micro-op with a partial, ten per FULL record */
   QHBM_CENSUS_COLUMNS
 };
 int qhbm_op_census(qhbm_engine* h, int adjoint, int max_passes, double* out, int* n_passes);
+/* The row stride of qhbm_op_census IN THE LIBRARY (its QHBM_CENSUS_COLUMNS).  Columns are appended within an ABI
+ * version (QHBM_CENSUS_LEVEL1 was; libraries without this entry point write 15 columns), so a caller that may meet a
+ * library built from another header sizes `out` as max_passes * qhbm_census_columns() and strides its rows by it
+ * (qhbmlib_amd/_engine.py op_census does); a buffer sized by an older header's QHBM_CENSUS_COLUMNS is too small for
+ * this library. */
+int qhbm_census_columns(void);
 
 /* Plan searches this engine has run so far: forward plans (rebuilt when the circuit, the observables or a planning
  * option changes) and backward plans (also per gradient mask; a mask the engine has seen before is served from its

@@ -2545,11 +2545,16 @@ void pass_census(const Plan& plan, const Pass& p, double tiles_per_state, double
         else if (wmask >> (pred & 0xffu) & 1u) { out[QHBM_CENSUS_CPH_WAVE_ON] += 0.5 * alive; out[QHBM_CENSUS_CPH_OFF] += 0.5 * alive; }
         else out[QHBM_CENSUS_CPH_LANE] += alive;
       }
-      if (adj) {  // eight-wide reductions (instance_adj): CPH group; PH2 group (per-term or FULL with pair terms); X + PH1 group
+      if (adj) {  // eight-wide reductions, counted as instance_adj tests them: one per SET that has a value -- the set's
+        // levels 2 and 3 and quad stages (kernels.hip add_slots8).  CPH set; PH2 set (per-term, or FULL with pair terms);
+        // X + PH1 set (X gates that own a slot: bits 12..15, not every X).  Level 1 is QHBM_CENSUS_LEVEL1; the
+        // lane-bit-5 stage and the store of the X + PH1 and PH2 sets run once in EVERY instance (QHBM_CENSUS_INSTANCES),
+        // the CPH set's with its count here.
         if (h1 & 0xffu) out[QHBM_CENSUS_REDUCE8] += alive;
         if (full && ((h0 >> 24) & 0x3fu)) out[QHBM_CENSUS_REDUCE8] += alive;
         if ((h0 >> 16) & 0x3fu) out[QHBM_CENSUS_REDUCE8] += alive;
-        if ((h0 & 0xf0fu) || (full && ((h0 >> 4) & 0xfu))) out[QHBM_CENSUS_REDUCE8] += alive;
+        if (((h0 >> 8) & 0xffu) || (full && ((h0 >> 4) & 0xfu))) out[QHBM_CENSUS_REDUCE8] += alive;
+        out[QHBM_CENSUS_LEVEL1] += alive * level1_adds(rec);
       }
     }
     ++round_i;
@@ -2611,6 +2616,8 @@ extern "C" int qhbm_plan_builds(qhbm_engine* h, int64_t* forward_plans, int64_t*
   if (backward_plans) *backward_plans = h->adj_plans_built;
   return 0;
 }
+
+extern "C" int qhbm_census_columns(void) { return QHBM_CENSUS_COLUMNS; }
 
 extern "C" int qhbm_op_census(qhbm_engine* h, int adjoint, int max_passes, double* out, int* n_passes) {
   if (!h || !out || !n_passes) return 1;

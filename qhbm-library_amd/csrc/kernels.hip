@@ -706,86 +706,95 @@ __device__ __forceinline__ void add_slot(float* cells, int tid, uint32_t slot, f
   if ((tid & 63) == 0) cells[slot * NW + (uint32_t(tid) >> 6)] = v;
 }
 
-// Gradient partials of the EIGHT slots of record slot group G8 (program.h slot_lane8), reduced over the wave together
-// WITHOUT selects.  Value v = (v0, v1, v2) ends up in the lanes whose bits (2, 3, 4) spell v (`present`: a wave-uniform
-// bit per value that exists -- the instance's own micro-op masks; used by the A/B builds with presence tests only):
+// Gradient partials of the EIGHT slots of a record slot group (program.h slot_lane8), reduced over the wave together
+// WITHOUT selects.  Value v = (v0, v1, v2) ends up in the lanes whose bits (2, 3, 4) spell v:
 //   level 1  lane bit 2 (adjacent banks of four lanes): value 2k adds its partner bank's share under bank_mask 0x5
-//            (row_shl:4), value 2k + 1 under 0xa (row_shr:4) into the SAME register -- one DPP add per value;
+//            (row_shl:4), value 2k + 1 under 0xa (row_shr:4) into the SAME accumulator t_k -- one DPP add per value,
+//            issued WHERE THE VALUE IS MADE (add_slot_l1, inside the header-bit test that already surrounds the code that
+//            makes it): a value that does not exist costs nothing, and no branch is added.  The accumulators start as
+//            any_float(): the banks of a value that does not exist stay undefined and reach no stored lane;
 //   level 2  lane bit 3: pair (2k, 2k + 1) with pair (2k + 2, 2k + 3) under bank masks 0x3 / 0xc (row_shl:8 / row_shr:8)
-//            -- one DPP add per pair;
+//            -- one DPP add per pair, in place;
 //   level 3  v_permlane16_swap + add: values 0..3 stay in even rows, 4..7 in odd rows (summed over the row pair);
-//   then the sums nobody selects on: two quad butterflies (lane bits 0, 1) and v_permlane32_swap + add (lane bit 5).
+//   then the sums nobody selects on: two quad butterflies (lane bits 0, 1) -- add_slots8 -- and v_permlane32_swap + add
+//   (lane bit 5): store_slots8 for a set alone, store_slots8x2 for the X + PH1 and the PH2 set of an instance together.
 // Round 4's butterfly paid two v_cndmask_b32 (4.2 cycles each on gfx950, as much as a packed FMA:
-// scripts/experiments/micro/valu_cycles.hip) per DPP add and all eight inputs whether they existed or not: 12 selects +
-// 8 DPP + 2 swaps = 105 cycles per call; here 12 DPP adds + a 31-cycle tail = 81, and no zeroed inputs: an input that
-// does not exist holds whatever its register held, and reaches no stored sum.  One asm statement: the DPP hazards (a VGPR
-// written by the previous VALU instruction needs two wait states before a DPP read) are spelled out.
+// scripts/experiments/micro/valu_cycles.hip) per DPP add and all eight inputs whether they existed or not; round 5's paid
+// eight level-1 adds per call whether the values existed or not (presence tests around them -- a scalar bit test + branch
+// per value or pair -- were measured and LOSE: a taken branch costs a wave more than the 4.2-cycle DPP add it skips,
+// profiles/r05_ab_runs.txt).  The DPP hazards (a VGPR written by the previous VALU instruction needs two wait states
+// before a DPP read) are spelled out in every statement.
 // The lanes whose slot-vector word `sv` IS the slot of the value they hold then store into their wave's cells (see
 // add_slot).  (`sv` holds slots LOCAL to the pass; the chain-rule scale of the slot class is folded into slot_factor.)
 template <int CTRL>
 __device__ __forceinline__ float dpp_get(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
 }
-template <int G8, int NW>
-__device__ __forceinline__ void add_slots8(float* cells, int lane, uint32_t wave, uint32_t sv, uint32_t present, float g0,
-                                           float g1, float g2, float g3, float g4, float g5, float g6, float g7) {
-  float t0, t1, t2, t3, u0, u1, w, x;
-// Presence tests (a scalar bit test + branch around the DPP add of a value or pair that does not exist) were measured
-// and LOSE: a taken branch costs a wave more than the 4.2-cycle DPP add it skips (adjoint 230.9 / 229.7 / 228.5 ms with a
-// test per value and pair / per pair / none, profiles/r05_ab_runs.txt).  0 = none (shipped); 1, 2: A/B builds.
-#ifndef QHBM_RED_TESTS
-#define QHBM_RED_TESTS 0
-#endif
-#if QHBM_RED_TESTS >= 2
-#define QHBM_L1(BIT_, T_, G_, DIR_, BANKS_)                                                        \
-  "s_bitcmp1_b32 %[m], " #BIT_ "\n\t"                                                              \
-  "s_cbranch_scc0 .Lred%=_a" #BIT_ "\n\t"                                                          \
-  "v_add_f32_dpp %[" #T_ "], %[" #G_ "], %[" #G_ "] " DIR_ ":4 row_mask:0xf bank_mask:" BANKS_ "\n" \
-  ".Lred%=_a" #BIT_ ":\n\t"
-#else
-#define QHBM_L1(BIT_, T_, G_, DIR_, BANKS_)                                                        \
-  "v_add_f32_dpp %[" #T_ "], %[" #G_ "], %[" #G_ "] " DIR_ ":4 row_mask:0xf bank_mask:" BANKS_ "\n\t"
-#endif
-#if QHBM_RED_TESTS >= 1
-#define QHBM_L2(MASK_, TAG_, U_, T_, DIR_, BANKS_)                                                 \
-  "s_and_b32 %[sc], %[m], " MASK_ "\n\t"                                                          \
-  "s_cbranch_scc0 .Lred%=_b" #TAG_ "\n\t"                                                         \
-  "v_add_f32_dpp %[" #U_ "], %[" #T_ "], %[" #T_ "] " DIR_ ":8 row_mask:0xf bank_mask:" BANKS_ "\n" \
-  ".Lred%=_b" #TAG_ ":\n\t"
-#else
-#define QHBM_L2(MASK_, TAG_, U_, T_, DIR_, BANKS_)                                                 \
-  "v_add_f32_dpp %[" #U_ "], %[" #T_ "], %[" #T_ "] " DIR_ ":8 row_mask:0xf bank_mask:" BANKS_ "\n\t"
-#endif
-  uint32_t sc;
+// Level 1 of value V of a set: into the banks of accumulator t = t_{V / 2} that V owns.
+template <int V>
+__device__ __forceinline__ void add_slot_l1(float& t, float g) {
+  if constexpr ((V & 1) == 0)
+    asm volatile("s_nop 1\n\tv_add_f32_dpp %[t], %[g], %[g] row_shl:4 row_mask:0xf bank_mask:0x5" : [t] "+v"(t) : [g] "v"(g));
+  else
+    asm volatile("s_nop 1\n\tv_add_f32_dpp %[t], %[g], %[g] row_shr:4 row_mask:0xf bank_mask:0xa" : [t] "+v"(t) : [g] "v"(g));
+}
+// Levels 2 and 3 and the quad butterflies of one set: every lane then holds, summed over its HALF of the wave, the
+// value that its bits (2, 3, 4) spell.
+__device__ __forceinline__ float add_slots8(float t0, float t1, float t2, float t3) {
   asm volatile(
       "s_nop 1\n\t"
-      QHBM_L1(0, t0, g0, "row_shl", "0x5") QHBM_L1(2, t1, g2, "row_shl", "0x5") QHBM_L1(4, t2, g4, "row_shl", "0x5")
-      QHBM_L1(6, t3, g6, "row_shl", "0x5") QHBM_L1(1, t0, g1, "row_shr", "0xa") QHBM_L1(3, t1, g3, "row_shr", "0xa")
-      QHBM_L1(5, t2, g5, "row_shr", "0xa") QHBM_L1(7, t3, g7, "row_shr", "0xa")
+      "v_add_f32_dpp %[t0], %[t0], %[t0] row_shl:8 row_mask:0xf bank_mask:0x3\n\t"
+      "v_add_f32_dpp %[t2], %[t2], %[t2] row_shl:8 row_mask:0xf bank_mask:0x3\n\t"
+      "v_add_f32_dpp %[t0], %[t1], %[t1] row_shr:8 row_mask:0xf bank_mask:0xc\n\t"
+      "v_add_f32_dpp %[t2], %[t3], %[t3] row_shr:8 row_mask:0xf bank_mask:0xc\n\t"
       "s_nop 1\n\t"
-      QHBM_L2("0x03", 0, u0, t0, "row_shl", "0x3") QHBM_L2("0x30", 2, u1, t2, "row_shl", "0x3")
-      QHBM_L2("0x0c", 1, u0, t1, "row_shr", "0xc") QHBM_L2("0xc0", 3, u1, t3, "row_shr", "0xc")
+      "v_permlane16_swap_b32 %[t0], %[t2]\n\t"
       "s_nop 1\n\t"
-      "v_permlane16_swap_b32 %[u0], %[u1]\n\t"
+      "v_add_f32 %[t0], %[t0], %[t2]\n\t"
       "s_nop 1\n\t"
-      "v_add_f32 %[w], %[u0], %[u1]\n\t"
+      "v_add_f32_dpp %[t0], %[t0], %[t0] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
       "s_nop 1\n\t"
-      "v_add_f32_dpp %[w], %[w], %[w] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_add_f32_dpp %[w], %[w], %[w] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %[t0], %[t0], %[t0] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
+      : [t0] "+v"(t0), [t2] "+v"(t2)
+      : [t1] "v"(t1), [t3] "v"(t3));
+  return t0;
+}
+// Lane bit 5 of ONE set (slot group G8), then the store.
+template <int G8, int NW>
+__device__ __forceinline__ void store_slots8(float* cells, int lane, uint32_t wave, uint32_t sv, float w) {
+  float x;
+  asm volatile(
       "v_mov_b32 %[x], %[w]\n\t"
       "s_nop 1\n\t"
       "v_permlane32_swap_b32 %[w], %[x]\n\t"
       "s_nop 1\n\t"
       "v_add_f32 %[w], %[w], %[x]"
-      : [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [u0] "=&v"(u0), [u1] "=&v"(u1), [w] "=&v"(w),
-        [x] "=&v"(x), [sc] "=&s"(sc)
-      : [m] "s"(present), [g0] "v"(g0), [g1] "v"(g1), [g2] "v"(g2), [g3] "v"(g3), [g4] "v"(g4), [g5] "v"(g5), [g6] "v"(g6),
-        [g7] "v"(g7)
-      : "scc");
-#undef QHBM_L1
-#undef QHBM_L2
+      : [w] "+v"(w), [x] "=&v"(x));
   if ((lane & 3) == (G8 & 3) && (lane >> 5) == (G8 >> 2) && sv != 0xffffffffu) cells[sv * NW + wave] = w;
+}
+// Lane bit 5 of the X + PH1 set (`wa`, slot group 0) and of the PH2 set (`wb`, group 1) with ONE swap of the two registers
+// against each other: lanes 0..31 then hold (wa low half) + (wa high half), lanes 32..63 (wb low) + (wb high) -- the sums
+// the sets' own swaps formed, operand for operand.  The upper lanes hold the PH2 slots in `sv` (slot_vector_lane), so one
+// store serves both; a set that the instance does not have is an undefined register and has no slot.
+template <int NW>
+__device__ __forceinline__ void store_slots8x2(float* cells, int lane, uint32_t wave, uint32_t sv, float wa, float wb) {
+  asm volatile(
+      "s_nop 1\n\t"
+      "v_permlane32_swap_b32 %[wa], %[wb]\n\t"
+      "s_nop 1\n\t"
+      "v_add_f32 %[wa], %[wa], %[wb]"
+      : [wa] "+v"(wa), [wb] "+v"(wb));
+  if ((lane & 3) == 0 && sv != 0xffffffffu) cells[sv * NW + wave] = wa;
+}
+// The word of an adjoint record's slot vector that a lane loads: its own in lanes 0..31 (all four slot groups), and in
+// lanes 32..63 the word of slot group 1 that belongs to the value the lane holds after store_slots8x2's swap (group 0's
+// word with lane bit 0 set; words 32..63 of the vector are unused).
+// (-DQHBM_RED_SHARED=0: every set with a lane-bit-5 stage and a store of its own, for A/B measurements.)
+#ifndef QHBM_RED_SHARED
+#define QHBM_RED_SHARED 1
+#endif
+__device__ __forceinline__ int slot_vector_lane(int lane) {
+  return QHBM_RED_SHARED && lane >= 32 ? ((lane & 31) ^ 1) : lane;
 }
 
 // A float nobody has written: an input of the eight-wide reduction whose slot does not exist.  The butterfly never adds
@@ -886,6 +895,23 @@ __device__ __forceinline__ void full_partials(const v2f (&p)[16], const v2f (&l)
   g2[3] = d9;   // B4: (0, 3)
   g2[4] = d10;  // A5: (1, 3)
   g2[5] = d12;  // A6: (2, 3)
+}
+
+// Level 1 (add_slot_l1) of the ten partials of a FULL instance in one statement: PH1 J is value 4 + J of the X + PH1
+// set (accumulators ta2, ta3), PH2 pair pi value pi of the PH2 set (tb0..tb2).
+__device__ __forceinline__ void full_l1(float& ta2, float& ta3, float& tb0, float& tb1, float& tb2, const float (&g1)[4],
+                                        const float (&g2)[6]) {
+#define QHBM_L1(T_, G_, DIR_, BANKS_) "v_add_f32_dpp %[" #T_ "], %[" #G_ "], %[" #G_ "] " DIR_ ":4 row_mask:0xf bank_mask:" BANKS_ "\n\t"
+  asm volatile(
+      "s_nop 1\n\t"
+      QHBM_L1(ta2, a0, "row_shl", "0x5") QHBM_L1(ta3, a2, "row_shl", "0x5") QHBM_L1(tb0, b0, "row_shl", "0x5")
+      QHBM_L1(tb1, b2, "row_shl", "0x5") QHBM_L1(tb2, b4, "row_shl", "0x5") QHBM_L1(ta2, a1, "row_shr", "0xa")
+      QHBM_L1(ta3, a3, "row_shr", "0xa") QHBM_L1(tb0, b1, "row_shr", "0xa") QHBM_L1(tb1, b3, "row_shr", "0xa")
+      "v_add_f32_dpp %[tb2], %[b5], %[b5] row_shr:4 row_mask:0xf bank_mask:0xa"
+      : [ta2] "+v"(ta2), [ta3] "+v"(ta3), [tb0] "+v"(tb0), [tb1] "+v"(tb1), [tb2] "+v"(tb2)
+      : [a0] "v"(g1[0]), [a1] "v"(g1[1]), [a2] "v"(g1[2]), [a3] "v"(g1[3]), [b0] "v"(g2[0]), [b1] "v"(g2[1]), [b2] "v"(g2[2]),
+        [b3] "v"(g2[3]), [b4] "v"(g2[4]), [b5] "v"(g2[5]));
+#undef QHBM_L1
 }
 
 // Controlled phase: register bit J AND (a thread bit | a tile bit).  One code path for both
@@ -1440,23 +1466,30 @@ __device__ __forceinline__ void instance_adj(const uint32_t (&cur)[1], const uin
   const RecBase rb{recs + rec_off};
   const uint32_t h0 = rec_word<0>(cur, rb), h1 = rec_word<1>(cur, rb);
   const uint32_t x2 = rb.p[L.x2_mask()];  // X gates in two-shear form (0 in instances without a FULL table)
+  // Level 1 of every reduction stands where its value is made (add_slot_l1), the rest once per set that has a value.
   // ---- CPH (slot group 2) ----
   if (h1 & 0xffu) {
-    float g[8] = {any_float(), any_float(), any_float(), any_float(), any_float(), any_float(), any_float(), any_float()};
+    float t[4] = {any_float(), any_float(), any_float(), any_float()};
+    // (a micro-op that the whole wave skips still contributes its zero: its lane is stored by assignment)
     QHBM_FOR_RB(R,
       if ((h1 >> (2 * J)) & 1u)
-        g[2 * J] = cph_adj<R, J>(p, l, rec_cs<L.cph(2 * J)>(cur, rb), rec_word<L.pred(2 * J)>(cur, rb), TLX);
+        add_slot_l1<2 * J>(t[J], cph_adj<R, J>(p, l, rec_cs<L.cph(2 * J)>(cur, rb), rec_word<L.pred(2 * J)>(cur, rb), TLX));
       if ((h1 >> (2 * J + 1)) & 1u)
-        g[2 * J + 1] = cph_adj<R, J>(p, l, rec_cs<L.cph(2 * J + 1)>(cur, rb), rec_word<L.pred(2 * J + 1)>(cur, rb), TLX);)
-    add_slots8<2, NW>(cells, lane, wave, sv[0], h1 & 0xffu, g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7]);
+        add_slot_l1<2 * J + 1>(t[J], cph_adj<R, J>(p, l, rec_cs<L.cph(2 * J + 1)>(cur, rb), rec_word<L.pred(2 * J + 1)>(cur, rb), TLX));)
+    store_slots8<2, NW>(cells, lane, wave, sv[0], add_slots8(t[0], t[1], t[2], t[3]));
   }
-  float g1[4] = {any_float(), any_float(), any_float(), any_float()};  // PH1 partials: reduced together with the X partials (slot group 0)
+  // Accumulators of the X + PH1 set (slot group 0: ta[0], ta[1] the X values, ta[2], ta[3] PH1) and of the PH2 set (group 1:
+  // six values, tb[3] stays undefined); `wb`: the PH2 set after its quad stages, held until the X + PH1 set has caught up.
+  float ta[4] = {any_float(), any_float(), any_float(), any_float()};
+  float tb[4] = {any_float(), any_float(), any_float(), any_float()};
+  float wb = any_float();
   if (h1 & kFullDiagFlag) {
     // ---- all PH1/PH2 terms at once: the per-term gradients are sums of Im(conj(lam) psi) over
     // the term's index set (full_partials), then ONE conj-table multiply ----
-    float g[6];
+    float g1[4], g[6];
     full_partials(p, l, g1, g);
-    if ((h0 >> 24) & 0x3fu) add_slots8<1, NW>(cells, lane, wave, sv[0], (h0 >> 24) & 0x3fu, g[0], g[1], g[2], g[3], g[4], g[5], any_float(), any_float());
+    full_l1(ta[2], ta[3], tb[0], tb[1], tb[2], g1, g);
+    if ((h0 >> 24) & 0x3fu) wb = add_slots8(tb[0], tb[1], tb[2], tb[3]);
     if (x2) {  // (the partials above are taken on the exact pair: the scaling of the two-shear X gates comes after them)
       const float e0 = __uint_as_float(rb.p[L.full0()]);
       scale_full0(p[0], e0);
@@ -1467,29 +1500,27 @@ __device__ __forceinline__ void instance_adj(const uint32_t (&cur)[1], const uin
   }
   // ---- PH2 (slot group 1) ----
   if ((h0 >> 16) & 0x3fu) {
-    float g[6] = {any_float(), any_float(), any_float(), any_float(), any_float(), any_float()};
     QHBM_FOR_PAIR(R,
       if ((h0 >> (16 + pair_index(JA, JB))) & 1u) {
         const v2f cs = rec_cs<L.ph2(pair_index(JA, JB))>(cur, rb);
-        g[pair_index(JA, JB)] = sum_w2<R, JA, JB>(p, l);
+        add_slot_l1<pair_index(JA, JB)>(tb[pair_index(JA, JB) >> 1], sum_w2<R, JA, JB>(p, l));
         apply_ph2<R, JA, JB>(p, cs);
         apply_ph2<R, JA, JB>(l, cs);
       })
-    add_slots8<1, NW>(cells, lane, wave, sv[0], (h0 >> 16) & 0x3fu, g[0], g[1], g[2], g[3], g[4], g[5], any_float(), any_float());
+    wb = add_slots8(tb[0], tb[1], tb[2], tb[3]);
   }
   // ---- PH1 ----
   if ((h0 >> 8) & 0xfu) {
     QHBM_FOR_RB(R,
       if ((h0 >> (8 + J)) & 1u) {
         const v2f cs = rec_cs<L.ph1(J)>(cur, rb);
-        g1[J] = sum_w1<R, J>(p, l);
+        add_slot_l1<4 + J>(ta[2 + (J >> 1)], sum_w1<R, J>(p, l));
         apply_ph1<R, J>(p, cs);
         apply_ph1<R, J>(l, cs);
       })
   }
   // ---- one-qubit gates: X (slot group 0, with the PH1 partials), Y and dense (slot group 3) ----
   {
-    float g[4] = {any_float(), any_float(), any_float(), any_float()};
     if (h0 & 0xfu) {
       // While a two-shear gate of the instance is pending, the table has scaled the pair by the diagonal factors of ALL
       // of them, and an inner product taken now would be wrong by those factors squared.  X_J commutes with every X
@@ -1498,26 +1529,37 @@ __device__ __forceinline__ void instance_adj(const uint32_t (&cur)[1], const uin
       QHBM_FOR_RB(R,
         if ((h0 >> J) & 1u) {
           const v2f cs = rec_cs<L.x(J)>(cur, rb);  // (U^dagger's shear coefficients: negated at preparation)
-          if (!x2 && ((h0 >> (12 + J)) & 1u)) g[J] = im_lam_x_psi<R, J>(p, l);  // (the X gates that own a gradient slot: a header bit, not a v_readlane of the slot vector)
+          if (!x2 && ((h0 >> (12 + J)) & 1u)) add_slot_l1<J>(ta[J >> 1], im_lam_x_psi<R, J>(p, l));  // (the X gates that own a gradient slot: a header bit, not a v_readlane of the slot vector)
           apply_x2<R, J>(p, cs);
           apply_x2<R, J>(l, cs);
           if (!((x2 >> J) & 1u)) { apply_x3<R, J>(p, cs); apply_x3<R, J>(l, cs); }
         })
       if (x2 && ((h0 >> 12) & 0xfu)) {
-        QHBM_FOR_RB(R, if ((h0 >> (12 + J)) & 1u) g[J] = im_lam_x_psi<R, J>(p, l);)
+        QHBM_FOR_RB(R, if ((h0 >> (12 + J)) & 1u) add_slot_l1<J>(ta[J >> 1], im_lam_x_psi<R, J>(p, l));)
       }
     }
     // the values that exist: X gates that own a slot (word 0 bits 12..15), PH1 terms (per-term: bits 8..11, FULL: 4..7)
     const uint32_t present = ((h0 >> 12) & 0xfu) | ((((h0 >> 8) | (h0 >> 4)) & 0xfu) << 4);
-    if (present) add_slots8<0, NW>(cells, lane, wave, sv[0], present, g[0], g[1], g[2], g[3], g1[0], g1[1], g1[2], g1[3]);
+#if QHBM_RED_SHARED
+    // (the shared stage runs in every instance -- a test around it would be a new branch; a set the instance does not
+    // have is an undefined register there, and its lanes have no slot)
+    float wa = any_float();
+    if (present) wa = add_slots8(ta[0], ta[1], ta[2], ta[3]);
+    store_slots8x2<NW>(cells, lane, wave, sv[0], wa, wb);
+#else
+    if ((h0 >> 16) & 0x3f3fu) store_slots8<1, NW>(cells, lane, wave, sv[0], wb);
+    if (present) store_slots8<0, NW>(cells, lane, wave, sv[0], add_slots8(ta[0], ta[1], ta[2], ta[3]));
+#endif
   }
   if constexpr (GEN) {
   if ((h1 >> 16) & 0xf0fu) {
-    float gy[4] = {0.f, 0.f, 0.f, 0.f}, gd[4] = {0.f, 0.f, 0.f, 0.f};
+    float gy[4] = {0.f, 0.f, 0.f, 0.f}, gd[4] = {0.f, 0.f, 0.f, 0.f};  // (a gate without a slot: a zero nobody stores)
+    float t[4] = {any_float(), any_float(), any_float(), any_float()};
     QHBM_FOR_RB(R,
       if ((h1 >> (16 + J)) & 1u) {
         const v2f cs = rec_cs<L.y(J)>(cur, rb);
         if (rec_word<L.slot_y(J) - S0>(sv) != 0xffffffffu) gy[J] = im_lam_y_psi<R, J>(p, l);
+        add_slot_l1<J>(t[J >> 1], gy[J]);
         apply_y<R, J>(p, cs);
         apply_y<R, J>(l, cs);
       })
@@ -1530,9 +1572,10 @@ __device__ __forceinline__ void instance_adj(const uint32_t (&cur)[1], const uin
           if (rec_word<L.slot_dense(J) - S0>(sv) != 0xffffffffu) gd[J] = im_lam_g1_psi<R, J>(p, l, gen);
           apply_mat1<R, J>(p, rec_cs<16 * J>(dv), rec_cs<16 * J + 2>(dv), rec_cs<16 * J + 4>(dv), rec_cs<16 * J + 6>(dv));
           apply_mat1<R, J>(l, rec_cs<16 * J>(dv), rec_cs<16 * J + 2>(dv), rec_cs<16 * J + 4>(dv), rec_cs<16 * J + 6>(dv));
+          add_slot_l1<4 + J>(t[2 + (J >> 1)], gd[J]);
         })
     }
-    add_slots8<3, NW>(cells, lane, wave, sv[0], (h1 >> 16) & 0xf0fu ? (((h1 >> 16) & 0xfu) | (((h1 >> 24) & 0xfu) << 4)) : 0u, gy[0], gy[1], gy[2], gy[3], gd[0], gd[1], gd[2], gd[3]);
+    store_slots8<3, NW>(cells, lane, wave, sv[0], add_slots8(t[0], t[1], t[2], t[3]));
   }
   }
 }
@@ -1632,6 +1675,7 @@ __global__ __launch_bounds__(1 << (K - 4), adjx_min_waves(K)) void pass_adjx_ker
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const uint32_t wave = uni(uint32_t(tid) >> 6);
+  const int slane = slot_vector_lane(lane);  // the word of a record's slot vector that this lane holds
   const uint32_t* recs = reinterpret_cast<const uint32_t*>(coef);
   const uint32_t s_local = blockIdx.x >> a.n_free;
   [[maybe_unused]] const unsigned long long tk0 = QHBM_TICK();  // (QHBM_ADJ_TIMING builds only: 0 otherwise)
@@ -1661,7 +1705,7 @@ __global__ __launch_bounds__(1 << (K - 4), adjx_min_waves(K)) void pass_adjx_ker
   uint32_t cur[1], nxt[1], sv[1], svn[1];
   uint32_t rec_off = uni(prog[2]);
   rec_load<1>(recs, rec_off, lane, cur);
-  rec_load<1>(recs, rec_off + L.slot0(), lane, sv);
+  rec_load<1>(recs, rec_off + L.slot0(), slane, sv);
   const uint32_t* tlt = tables + a.tl_off + uint32_t(tid);
   uint32_t DB[R], T, TL = tlt[uni(prog[3])];
   TileRegs rp, rl;
@@ -1693,11 +1737,11 @@ __global__ __launch_bounds__(1 << (K - 4), adjx_min_waves(K)) void pass_adjx_ker
     if (dead) {
       rec_off += n_inst * L.words();
       rec_load<1>(recs, rec_off, lane, cur);
-      rec_load<1>(recs, rec_off + L.slot0(), lane, sv);
+      rec_load<1>(recs, rec_off + L.slot0(), slane, sv);
     } else {
       for (uint32_t inst = 0; inst < n_inst; ++inst) {
         rec_load<1>(recs, rec_off + L.words(), lane, nxt);  // prefetch (the buffer is padded)
-        rec_load<1>(recs, rec_off + L.words() + L.slot0(), lane, svn);
+        rec_load<1>(recs, rec_off + L.words() + L.slot0(), slane, svn);
         instance_adj<R, NW, false>(cur, sv, recs, rec_off, lane, wave, p, l, TL | tile_hi, cells);
         rec_off += L.words();
         cur[0] = nxt[0];
@@ -1717,7 +1761,7 @@ __global__ __launch_bounds__(1 << (K - 4), adjx_min_waves(K)) void pass_adjx_ker
     if (next_off != rec_off) {  // records of consecutive rounds are consecutive: normally already prefetched
       rec_off = next_off;
       rec_load<1>(recs, rec_off, lane, cur);
-      rec_load<1>(recs, rec_off + L.slot0(), lane, sv);
+      rec_load<1>(recs, rec_off + L.slot0(), slane, sv);
     }
     round_store0<R>(T, DB, p);
     if (sync) __syncthreads();
@@ -1797,6 +1841,7 @@ __global__ __launch_bounds__(1 << (K - 4), adj_min_waves(K)) void pass_adj_kerne
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const uint32_t wave = uni(uint32_t(tid) >> 6);
+  const int slane = slot_vector_lane(lane);  // the word of a record's slot vector that this lane holds
   const uint32_t* recs = reinterpret_cast<const uint32_t*>(coef);
   const uint32_t s_local = blockIdx.x >> a.n_free;
   // tail of the sweep: the tiles on which psi is identically zero are not launched (launched_tile; these plans
@@ -1834,7 +1879,7 @@ __global__ __launch_bounds__(1 << (K - 4), adj_min_waves(K)) void pass_adj_kerne
       constexpr RecordLayout L(R, true);
       if (rec_off != carried_off) {  // else: prefetched by the previous round's last instance
         rec_load<1>(recs, rec_off, lane, cur);
-        rec_load<1>(recs, rec_off + L.slot0(), lane, sv);
+        rec_load<1>(recs, rec_off + L.slot0(), slane, sv);
       }
       uint32_t DB[R], T;
       const uint32_t TL = tables[a.tl_off + uni(prog[pc + 3]) + uint32_t(tid)];
@@ -1844,7 +1889,7 @@ __global__ __launch_bounds__(1 << (K - 4), adj_min_waves(K)) void pass_adj_kerne
       round_load<R>(tl, T, DB, l);
       for (uint32_t inst = 0; inst < n_inst; ++inst) {
         rec_load<1>(recs, rec_off + L.words(), lane, nxt);  // prefetch (the buffer is padded)
-        rec_load<1>(recs, rec_off + L.words() + L.slot0(), lane, svn);
+        rec_load<1>(recs, rec_off + L.words() + L.slot0(), slane, svn);
         instance_adj<R, NW, GEN>(cur, sv, recs, rec_off, lane, wave, p, l, TL | tile_hi, cells);
         rec_off += L.words();
         cur[0] = nxt[0];

@@ -141,6 +141,8 @@ struct RecordLayout {
   // value v of slot group g8 ends up in the lanes with bits (2, 3, 4) = v and bits (0, 1, 5) = g8, and
   // the slot-vector word of that lane IS the slot.  Groups: 0 = X[4] + PH1[4], 1 = PH2[6],
   // 2 = CPH[8], 3 = Y[4] + DENSE[4].
+  // (Groups 0 and 1 share their last stage: group 1's sums end up in lanes 32..63, which load group 1's words of the
+  // vector -- kernels.hip slot_vector_lane; the layout is as written here.)
   constexpr int slot_lane8(int g8, int v) const {
     return slot0() + ((g8 & 3) | ((v & 3) << 2) | ((v >> 2) << 4) | ((g8 >> 2) << 5));
   }
@@ -156,6 +158,14 @@ struct RecordLayout {
   constexpr int words() const { return 64 * vecs(); }
 };
 constexpr uint32_t kFullDiagFlag = 1u << 31;
+// Level-1 adds of the gradient reductions that one wave executes for an adjoint record (kernels.hip add_slot_l1): one per
+// header bit of a micro-op that makes a partial -- X gates that own a slot, per-term PH1 / PH2, CPH (a micro-op that is off
+// in the whole wave still contributes its zero), Y, dense -- and ten per FULL record, whose partials all come from one
+// statement whether their terms exist or not.
+inline int level1_adds(const uint32_t* rec) {
+  const uint32_t h0 = rec[0], h1 = rec[1];
+  return __builtin_popcount((h0 >> 8) & 0x3fffu) + __builtin_popcount(h1 & 0x0f0f00ffu) + ((h1 & kFullDiagFlag) ? 10 : 0);
+}
 
 // Lowered operation kinds produced by the host.
 enum LoweredType : int { LOW_SKIP = 0, LOW_DIAG = 1, LOW_MAT1 = 2, LOW_MAT2 = 3 };

@@ -1521,7 +1521,7 @@ std::string describe_plan(const Plan& p) {
         groups += ((h0 >> 16) & 0x3fu) != 0;
       }
     }
-    if (p.adjoint) {  // how full the eight-wide gradient reductions are (kernels.hip add_slots8)
+    if (p.adjoint) {  // how full the eight-wide gradient reductions are (kernels.hip add_slot_l1 / add_slots8)
       int hist[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
       for (uint32_t off : p.record_offsets)
         for (int g8 = 0; g8 < 4; ++g8) {
@@ -1540,6 +1540,22 @@ std::string describe_plan(const Plan& p) {
         }
       os << "; by group (X+PH1 | PH2 | CPH | Y+dense) low-half only / high-half only / both:";
       for (int g8 = 0; g8 < 4; ++g8) os << " " << half[g8][0] << "/" << half[g8][1] << "/" << half[g8][2];
+      os << "\n";
+      // where the slots sit: per group the records with a slot at value position 0..7, and the records by the sets they
+      // reduce (bit 0: X + PH1, bit 1: PH2, bit 2: CPH, bit 3: Y + dense) -- what a test of the reductions must cover
+      int at[4][8] = {}, sets[16] = {};
+      for (uint32_t off : p.record_offsets) {
+        int m = 0;
+        for (int g8 = 0; g8 < 4; ++g8)
+          for (int v = 0; v < 8; ++v)
+            if (p.coef_init[off + L.slot_lane8(g8, v)] != 0xffffffffu) { ++at[g8][v]; m |= 1 << g8; }
+        ++sets[m];
+      }
+      os << "  slots at value position 0..7, by group:";
+      for (int g8 = 0; g8 < 4; ++g8)
+        for (int v = 0; v < 8; ++v) os << (v ? "/" : " ") << at[g8][v];
+      os << "; records by sets reduced 0..15:";
+      for (int m = 0; m < 16; ++m) os << (m ? "/" : " ") << sets[m];
       os << "\n";
     }
     os << "  census: instances=" << n_inst << " (FULL " << n_full << ") X=" << x << " PH1=" << ph1 << " PH2=" << ph2
@@ -1580,6 +1596,15 @@ std::string describe_plan(const Plan& p) {
       }
     }
     if (p.adjoint) {
+      // level-1 adds of the gradient reductions that a wave running every record of the pass once executes (kernels.hip
+      // add_slot_l1: one per header bit of a micro-op with a partial, ten per FULL record)
+      const RecordLayout L(p.R, true);
+      size_t l1 = 0;
+      for (size_t r = 0; r < q.round_words.size(); ++r) {
+        const uint32_t w0 = q.prog[q.round_words[r]], n_inst = (w0 & ~kRoundNoBarrier) >> 8, first = q.prog[q.round_words[r] + 2];
+        for (uint32_t i = 0; i < n_inst; ++i) l1 += size_t(level1_adds(&p.coef_init[first + size_t(i) * size_t(L.words())]));
+      }
+      os << " level1_adds=" << l1;
       os << " dead=";
       for (size_t r = 0; r < q.round_words.size(); ++r) os << (r ? "," : "") << std::hex << q.prog[q.round_words[r] + 4] << std::dec;
     }

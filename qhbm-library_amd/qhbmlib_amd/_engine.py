@@ -41,7 +41,7 @@ ABI_SYMBOLS = (
     "qhbm_expectation_jacobian", "qhbm_statevector", "qhbm_sample", "qhbm_sample_counts", "qhbm_program_vjps", "qhbm_parity_energy", "qhbm_parity_energy_vjp",
     "qhbm_gwg_sample", "qhbm_walsh_hadamard", "qhbm_parity_table", "qhbm_parity_table_vjp",
     "qhbm_num_passes", "qhbm_describe_schedule",
-    "qhbm_kernel_time_ms", "qhbm_traffic_model", "qhbm_flop_model", "qhbm_op_census", "qhbm_clock_probe", "qhbm_plan_builds",
+    "qhbm_kernel_time_ms", "qhbm_traffic_model", "qhbm_flop_model", "qhbm_op_census", "qhbm_census_columns", "qhbm_clock_probe", "qhbm_plan_builds",
     "qhbm_table_expectation", "qhbm_table_expectation_retain", "qhbm_table_expectation_vjp",
     "qhbm_table_expectation_vjp_retained",
     "qhbm_expectation_from_states", "qhbm_expectation_vjp_from_states", "qhbm_statevector_from_states",
@@ -482,18 +482,22 @@ class Engine:
     return {"ghz": g.value, "cycles_per_pk_fma": c.value, "tflops": t.value}
 
   CENSUS_COLUMNS = ("tiles", "rounds", "rounds_barrier", "rounds_no_barrier", "instances", "x", "x_no_slot", "full",
-                    "ph1", "ph2", "cph_tile_on", "cph_wave_on", "cph_lane", "cph_off", "reduce8")
+                    "ph1", "ph2", "cph_tile_on", "cph_wave_on", "cph_lane", "cph_off", "reduce8", "level1")
 
   def op_census(self, adjoint=True, max_passes=64):
     """Executed micro-ops per pass in wave-executions per state (include/qhbm_engine.h qhbm_op_census):
     a list of dicts, one per pass of the forward or backward schedule."""
     import numpy as np  # pylint: disable=import-outside-toplevel
-    ncol = len(self.CENSUS_COLUMNS)
+    try:  # the library's own row stride; one from before the entry point writes 15 columns (A/B runs: QHBM_ENGINE_LIB)
+      ncol = int(self._lib.qhbm_census_columns())
+    except AttributeError:
+      ncol = 15
     out = np.zeros((max_passes, ncol), np.float64)
     n = ctypes.c_int()
     self._check(self._lib.qhbm_op_census(self._h, int(bool(adjoint)), max_passes,
                                          out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(n)))
-    return [dict(zip(self.CENSUS_COLUMNS, out[i])) for i in range(min(n.value, max_passes))]
+    names = self.CENSUS_COLUMNS  # (a column the library does not have yet reads 0)
+    return [{name: (out[i, c] if c < ncol else 0.0) for c, name in enumerate(names)} for i in range(min(n.value, max_passes))]
 
   # ---- hot path --------------------------------------------------------------
   def _prep(self, bits, params):

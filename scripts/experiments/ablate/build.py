@@ -35,14 +35,33 @@ def in_instance(text, old, new, count=-1):
   return text[:a] + body.replace(old, new, count) + text[b:]
 
 
+def _reduction_pieces(text, l1, full_l1, quads, store, store2):
+  """Puts a statement in front of the body of each piece of the eight-wide gradient reductions."""
+  for head, first in (
+      ("__device__ __forceinline__ void add_slot_l1(float& t, float g) {\n", l1),
+      ("                                        const float (&g2)[6]) {\n", full_l1),
+      ("__device__ __forceinline__ float add_slots8(float t0, float t1, float t2, float t3) {\n", quads),
+      ("__device__ __forceinline__ void store_slots8(float* cells, int lane, uint32_t wave, uint32_t sv, float w) {\n", store),
+      ("__device__ __forceinline__ void store_slots8x2(float* cells, int lane, uint32_t wave, uint32_t sv, float wa, float wb) {\n", store2)):
+    assert text.count(head) == 1, head
+    text = text.replace(head, head + first, 1)
+  return text
+
+
 VARIANTS = {
     "base": lambda t: t,
-    "no_reduce": lambda t: once(t, "  float t0, t1, t2, t3, u0, u1, w, x;\n",
-                                "  if (sv == 0x12345u) return;\n  if (true) return;\n  float t0, t1, t2, t3, u0, u1, w, x;\n"),
+    # the gradient reductions compiled out at every piece: level 1 where a value is made (add_slot_l1, full_l1), the
+    # set's levels 2, 3 and quad stages (add_slots8), the lane-bit-5 stages and stores (store_slots8, store_slots8x2)
+    "no_reduce": lambda t: _reduction_pieces(t, "  if (true) return;\n", "  if (true) return;\n", "  if (true) return t0;\n",
+                                             "  if (true) return;\n", "  if (true) return;\n"),
     # the reductions' cross-lane part compiled out: the partial sums stay alive (an empty asm consumes them), one of
-    # them is stored -- what is removed is add_slots8's DPP adds, swaps and tail
-    "no_butterfly": lambda t: once(t, "  float t0, t1, t2, t3, u0, u1, w, x;\n",
-                                   "  if (lane >= 0) { asm volatile(\"\" :: \"v\"(g0), \"v\"(g1), \"v\"(g2), \"v\"(g3), \"v\"(g4), \"v\"(g5), \"v\"(g6), \"v\"(g7), \"s\"(present)); if ((lane & 3) == (G8 & 3) && (lane >> 5) == (G8 >> 2) && sv != 0xffffffffu) cells[sv * NW + wave] = g0; return; }\n  float t0, t1, t2, t3, u0, u1, w, x;\n"),
+    # them is stored -- what is removed is the DPP adds, swaps and tails
+    "no_butterfly": lambda t: _reduction_pieces(
+        t, "  if (true) { asm volatile(\"\" : \"+v\"(t) : \"v\"(g)); return; }\n",
+        "  if (true) { asm volatile(\"\" : \"+v\"(ta2), \"+v\"(ta3), \"+v\"(tb0), \"+v\"(tb1), \"+v\"(tb2) : \"v\"(g1[0]), \"v\"(g1[1]), \"v\"(g1[2]), \"v\"(g1[3]), \"v\"(g2[0]), \"v\"(g2[1]), \"v\"(g2[2]), \"v\"(g2[3]), \"v\"(g2[4]), \"v\"(g2[5])); return; }\n",
+        "  if (true) { asm volatile(\"\" : \"+v\"(t0) : \"v\"(t1), \"v\"(t2), \"v\"(t3)); return t0; }\n",
+        "  if (lane >= 0) { if ((lane & 3) == (G8 & 3) && (lane >> 5) == (G8 >> 2) && sv != 0xffffffffu) cells[sv * NW + wave] = w; return; }\n",
+        "  if (lane >= 0) { asm volatile(\"\" : \"+v\"(wa) : \"v\"(wb)); if ((lane & 3) == 0 && sv != 0xffffffffu) cells[sv * NW + wave] = wa; return; }\n"),
     # record coefficients as compile-time constants (only the two header words are loaded): what the
     # scalar-load latency of the record fields costs
     "const_coefs": lambda t: once(t, "  if constexpr (QHBM_SCALAR_RECORDS) return rb.p[W];", "  if constexpr (W >= 2) return 0x3f19999au; else if constexpr (QHBM_SCALAR_RECORDS) return rb.p[W];"),
@@ -80,14 +99,14 @@ __global__ __launch_bounds__(1 << (K - 4), adjx_min_waves(K)) void pass_adjx_ker
         "    const ThreadOff o = thread_offsets<ROWS>(t, tid);\n    round_store0<R>(T, DB, p);\n    __syncthreads();\n    __builtin_amdgcn_sched_barrier(0);\n    store_tile<K, NT, ROWS>(xt, sp, t, o, tid);\n    __builtin_amdgcn_sched_barrier(0);\n    __syncthreads();\n    round_store0<R>(T, DB, l);\n    __syncthreads();\n    __builtin_amdgcn_sched_barrier(0);\n    store_tile<K, NT, ROWS>(xt, sl, t, o, tid);\n",
         "    regs_to_global<K, NT>(p, sp, t, tid);\n    regs_to_global<K, NT>(l, sl, t, tid);\n    __syncthreads();\n"),
     # (both places the inner product may stand: before the shears, or after them all when a two-shear gate is pending)
-    "no_x_inner": lambda t: in_instance(in_instance(t, "g[J] = im_lam_x_psi<R, J>(p, l);  //", "g[J] = p[0].x;  //"),
-                                        "g[J] = im_lam_x_psi<R, J>(p, l);)", "g[J] = p[0].x;)"),
+    "no_x_inner": lambda t: in_instance(in_instance(t, "add_slot_l1<J>(ta[J >> 1], im_lam_x_psi<R, J>(p, l));  //", "add_slot_l1<J>(ta[J >> 1], p[0].x);  //"),
+                                        "add_slot_l1<J>(ta[J >> 1], im_lam_x_psi<R, J>(p, l));)", "add_slot_l1<J>(ta[J >> 1], p[0].x);)"),
     "no_x_on_lambda": lambda t: in_instance(in_instance(t, "          apply_x2<R, J>(l, cs);\n", ""), " apply_x3<R, J>(l, cs); }", " }"),
     "no_x_at_all": lambda t: in_instance(in_instance(in_instance(in_instance(in_instance(
         t, "          apply_x2<R, J>(l, cs);\n", ""), "          apply_x2<R, J>(p, cs);\n", ""),
         "          if (!((x2 >> J) & 1u)) { apply_x3<R, J>(p, cs); apply_x3<R, J>(l, cs); }\n", ""),
-        "g[J] = im_lam_x_psi<R, J>(p, l);  //", "g[J] = p[0].x + cs.x;  //"),
-        "g[J] = im_lam_x_psi<R, J>(p, l);)", "g[J] = p[0].x;)"),
+        "add_slot_l1<J>(ta[J >> 1], im_lam_x_psi<R, J>(p, l));  //", "add_slot_l1<J>(ta[J >> 1], p[0].x + cs.x);  //"),
+        "add_slot_l1<J>(ta[J >> 1], im_lam_x_psi<R, J>(p, l));)", "add_slot_l1<J>(ta[J >> 1], p[0].x);)"),
     "no_full": lambda t: in_instance(t, "  if (h1 & kFullDiagFlag) {", "  if ((h1 & kFullDiagFlag) && lane == 77) {"),
     "no_cph": lambda t: in_instance(t, "  if (h1 & 0xffu) {", "  if ((h1 & 0xffu) && lane == 77) {", 1),
     "no_ph1_ph2": lambda t: in_instance(in_instance(t, "  if ((h0 >> 16) & 0x3fu) {", "  if (((h0 >> 16) & 0x3fu) && lane == 77) {"),
@@ -208,9 +227,8 @@ VARIANTS.update({
 VARIANTS.update({
     # round 5: the paired forward kernel at FIVE waves per SIMD (its LDS -- one 32-KiB exchange tile -- admits five
     # workgroups per CU; 96 registers instead of 111: the compiler spills 16 in the tile prologue)
-    # round 5: the reductions with presence tests -- a scalar test + branch per pair / per value and pair (shipped: none)
-    "red_tests_pairs": lambda t: once(t, "#define QHBM_RED_TESTS 0\n", "#define QHBM_RED_TESTS 1\n"),
-    "red_tests_values": lambda t: once(t, "#define QHBM_RED_TESTS 0\n", "#define QHBM_RED_TESTS 2\n"),
+    # part 2 of the producing-site reductions compiled out: every set with a lane-bit-5 stage and a store of its own
+    "red_own_tails": lambda t: once(t, "#define QHBM_RED_SHARED 1\n", "#define QHBM_RED_SHARED 0\n"),
     "fwd2_five_waves": lambda t: once(t,
         "template <int K>\n__global__ __launch_bounds__(1 << (K - 4), adjx_min_waves(K)) void pass_fwd2_kernel(",
         "constexpr int fwd2_min_waves(int K) { return clampi(wg_per_cu(8 << K) * (1 << (K - 4)) / 256, 1, 5); }\n"

@@ -79,7 +79,8 @@ def main():
       ("FULL tables + their ten partials", "no_full", None, c["full"], "60 (2 x 15 x 2) + 31 scalar mul/fma + 27 scalar adds"),
       ("PH1 / PH2 phases + their sums", "no_ph1_ph2", None, c["ph1"] + c["ph2"], "PH1 8 + 32, PH2 4 + 16"),
       ("boundary phases (CPH) + their reduction", "no_cph", None, c["cph_tile_on"] + c["cph_wave_on"] + c["cph_lane"], "8 + 32 per execution with the predicate on"),
-      ("cross-lane reductions (add_slots8)", "no_butterfly", None, c["reduce8"], "0 (values + pairs DPP adds + 7)"),
+      # (level 1 at the producing sites -- c["level1"] adds in all -- then per set levels 2, 3, the quad stages and a tail)
+      ("cross-lane reductions (add_slots8)", "no_butterfly", None, c["reduce8"], f"0 ({c['level1'] / max(c['reduce8'], 1):.1f} level-1 adds + 12 per set, 2 + store per instance)"),
       ("LDS exchange between rounds", "no_exchange", None, c["rounds"], "0 (64 DS ops + 60 v_xor)"),
   ]
   seen_valu = seen_cyc = 0.0
