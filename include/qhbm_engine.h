@@ -299,6 +299,47 @@ int qhbm_statevector_from_states(qhbm_engine* h, const void* d_states, int U, co
                                  void* d_out_states, void* stream);
 int qhbm_describe_schedule_from_states(qhbm_engine* h, char* buf, size_t buf_len);
 
+/* ---- Evolving caller-supplied states: matrix-free thermal targets ----
+ * Added WITHIN ABI version 5: purely additive, QHBM_ABI_VERSION stays 5.
+ *
+ * H = sum_k weights[k] O_k over the INSTALLED observables (qhbm_set_observables); `weights` is a host array of n_ops
+ * doubles, NULL = all ones.  R = sum_k |w_k| sum_j |c_kj| >= ||H||.  e^{-tau H} phi and e^{-i tau H} phi are Chebyshev sums
+ * in H / R built from repeated launches of the lambda = O psi kernels on device-resident states:
+ *   imaginary time  e^{-d H} = e^{d R} [a_0 T_0 + 2 sum_k (-1)^k a_k T_k(H / R)],  a_k = e^{-x} I_k(x),  x = d R
+ *   real time       e^{-i d H} = J_0(x) T_0 + 2 sum_k (-i)^k J_k(x) T_k(H / R)
+ * tau is split into m = ceil(|tau| R / s) equal steps (engine option "evolve_step_argument" s, default 4, so x <= 4); the
+ * coefficients come from Miller's backward recurrence in float64 on the host and the sum is cut where the discarded
+ * tail 2 sum |a_k| falls below 2^-30.  In imaginary time the state is renormalised after every step and
+ * log ||.|| is accumulated per state in float64 on the device; the factor e^{d R} enters that log norm only.  m and the
+ * number of terms depend on (tau, R, mode) alone: nothing is read back, the call is asynchronous on `stream`.
+ *
+ * State layout, alignment and the rule that the states must not lie inside the workspace: as for
+ * qhbm_expectation_from_states.  The circuit may be empty (it is not applied).  Four state buffers per chunk element
+ * are cut from workspace_budget_mb / chunk_states.  Results do not depend on the chunking, nor on which other states
+ * share the call (no floating-point atomics).  Like every compute call these drop retained states and VJP rows.
+ * Refused, each with a message: no observables installed; U <= 0; tau not finite, or tau < 0 in mode 0; d_log_norms
+ * given in mode 1; states inside the workspace.  R = 0 is the identity: the states are unchanged and the log norms are
+ * log ||phi_u||.
+ *
+ *   qhbm_apply_observables   d_out_states[u] = H phi_u of the states as given (d_out_states must not overlap d_states)
+ *   qhbm_evolve_states       in place.  mode 0: phi_u <- e^{-tau H} phi_u / ||e^{-tau H} phi_u|| (zeros for a state of norm
+ *                            0), d_log_norms [U] (device, float64, may be NULL) = log ||e^{-tau H} phi_u|| of the input AS
+ *                            GIVEN (-inf for norm 0).  mode 1: phi_u <- e^{-i tau H} phi_u, the norm as given, any sign of
+ *                            tau; d_log_norms must be NULL.
+ *   qhbm_describe_evolution  "R=... steps=... terms_per_step=... applications=..." of such a call; needs no device
+ *   qhbm_random_states       d_states [U, 2^n_qubits] complex64 = random-sign states: for state u = first_state + row and
+ *                            the group g = j >> 6 of 64 amplitudes, one Philox4x32-10 call with key (seed low, seed
+ *                            high) and counter {g low, g high, u, 0x54505153}; amplitude j takes bits 2 (j & 63) (sign
+ *                            of the real part) and 2 (j & 63) + 1 (imaginary part) of the 128 output bits, word index
+ *                            first, least significant bit first; each part has magnitude float(2^{-(n + 1) / 2}), so
+ *                            ||r|| = 1 and E[|r><r|] = I / 2^n.  No engine: the current device. */
+int qhbm_apply_observables(qhbm_engine* h, const void* d_states, int U, const double* weights, void* d_out_states,
+                           void* stream);
+int qhbm_evolve_states(qhbm_engine* h, void* d_states, int U, const double* weights, double tau, int mode,
+                       double* d_log_norms, void* stream);
+int qhbm_describe_evolution(qhbm_engine* h, const double* weights, double tau, int mode, char* buf, size_t len);
+int qhbm_random_states(void* d_states, int U, int n_qubits, uint64_t seed, uint64_t first_state, void* stream);
+
 /* Computational-basis samples of the final states (tfq.layers.Sample as used at
  * qhbmlib/inference/qnn.py:169,177-181,286-291):
  *   d_out_samples [U, n_shots, n_qubits] int8 (device); shot j of state u is drawn from

@@ -223,6 +223,11 @@ struct qhbm_engine {
   DevBuf<double> import_parts, import_norm2;  // import_states.hip: scratch, ||phi_u||^2 [U]
   DevBuf<float> import_up;                    // upstream rows times ||phi_u||^2
   DevBuf<int8_t> import_bits;                 // zeros: the bitstrings the pass kernels are handed (no pass reads them)
+  // Chebyshev evolution of caller states (qhbm_evolve_states, qhbm_apply_observables; thermal.hip)
+  int opt_evolve_step = 4;                    // bound on the argument x = delta R of one step ("evolve_step_argument")
+  std::vector<double> evo_host_wr;            // w_k / R (or w_k) of the call in flight: the source of an asynchronous copy
+  DevBuf<double> evo_wr, evo_scale, evo_parts, evo_log_norm;  // [n_ops], [chunk], norm partials, [U] when the caller wants none
+  DevBuf<float> evo_up1, evo_up2;             // [chunk, n_ops] upstream rows: (w_k / R) * scale of the state, 2 w_k / R
 };
 
 namespace {
@@ -263,7 +268,9 @@ size_t own_bytes(const qhbm_engine* h) {
            const PlanSet& o = h->dense;
            size_t b = plan_bytes(o.fwd) + plan_bytes(o.adj) + buf_bytes(o.global_terms) + buf_bytes(o.param_slot_begin) +
                       buf_bytes(o.param_slots) + buf_bytes(o.slot_factor) + buf_bytes(o.shift_phases) + buf_bytes(h->import_parts) +
-                      buf_bytes(h->import_norm2) + buf_bytes(h->import_up) + buf_bytes(h->import_bits);
+                      buf_bytes(h->import_norm2) + buf_bytes(h->import_up) + buf_bytes(h->import_bits) + buf_bytes(h->evo_wr) +
+                      buf_bytes(h->evo_scale) + buf_bytes(h->evo_parts) + buf_bytes(h->evo_log_norm) + buf_bytes(h->evo_up1) +
+                      buf_bytes(h->evo_up2);
            for (const auto& kv : o.adj_cache) b += plan_bytes(*kv.second);
            return b;
          }();
@@ -1105,7 +1112,8 @@ int ensure_state_buffers(qhbm_engine* h, uint32_t cs, bool with_lam) {
 }
 
 int run_observable_chunk(qhbm_engine* h, uint32_t s0, uint32_t c, const float* d_upstream, bool value_mode,
-                         hipStream_t stream, bool store_lambda = true, bool multi_values = false);
+                         hipStream_t stream, bool store_lambda = true, bool multi_values = false,
+                         const float2* src = nullptr, float2* dst = nullptr);
 int run_values_chunk(qhbm_engine* h, uint32_t row0, uint32_t c, hipStream_t stream);
 
 int forward(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, float* d_out,
@@ -1142,13 +1150,17 @@ bool observable_xcd_states(const qhbm_engine* h) {
 // <psi|O|psi> goes to the fixed-point value accumulators -- the forward sweep measured nothing.
 // multi_values (gather_multi_mode): the gather kernel with a value accumulator per observable -- the weighted lambda (if
 // stored) and every <psi|O_t|psi> from ONE launch.
+// src / dst (default: psi / lam): the c states read and the c states written, at the workspace's pitch -- the Chebyshev
+// recurrence of evolve_states rotates its buffers through them.
 int run_observable_chunk(qhbm_engine* h, uint32_t s0, uint32_t c, const float* d_upstream, bool value_mode,
-                         hipStream_t stream, bool store_lambda, bool multi_values) {
+                         hipStream_t stream, bool store_lambda, bool multi_values, const float2* src, float2* dst) {
   const uint32_t n_eff = uint32_t(h->fwd.plan.n_eff);
+  if (!src) src = h->psi.p;
+  if (!dst) dst = h->lam.p;
   if (multi_values) {
     HIPCHK(h->value_part.reserve(observable_value_parts(n_eff, c) * size_t(h->model.n_ops)));
     hipEvent_t* ev = timer_begin(h, 2, stream);
-    HIPCHK(launch_apply_observable(h->psi.p, store_lambda ? h->lam.p : nullptr, n_eff, c, h->terms.p,
+    HIPCHK(launch_apply_observable(src, store_lambda ? dst : nullptr, n_eff, c, h->terms.p,
                                    h->n_gather_terms, h->obs_groups.p, h->n_obs_groups,
                                    store_lambda ? d_upstream : nullptr, uint32_t(h->model.n_ops), s0, h->op_scale.p,
                                    h->vals64.p, h->value_part.p, observable_xcd_states(h), stream, true));
@@ -1160,7 +1172,7 @@ int run_observable_chunk(qhbm_engine* h, uint32_t s0, uint32_t c, const float* d
   hipEvent_t* ev = timer_begin(h, 2, stream);
   if (block_kernel(h)) {
     const int mode = !value_mode ? OBS_LAMBDA : (store_lambda ? OBS_LAMBDA_VALUE : OBS_VALUES);
-    HIPCHK(launch_observable_blocks(mode, obs_block_shape(h), h->psi.p, store_lambda ? h->lam.p : nullptr, n_eff, c, h->obs_bterms.p,
+    HIPCHK(launch_observable_blocks(mode, obs_block_shape(h), src, store_lambda ? dst : nullptr, n_eff, c, h->obs_bterms.p,
                                     h->obs_bgroups.p, h->n_obs_bgroups, d_upstream, uint32_t(h->model.n_ops), s0,
                                     h->op_scale.p, value_mode ? h->vals64.p : nullptr, h->value_part.p,
                                     observable_xcd_states(h), stream));
@@ -1168,7 +1180,7 @@ int run_observable_chunk(qhbm_engine* h, uint32_t s0, uint32_t c, const float* d
     ObsFarLaunch far[3];
     for (int f = 0; f < h->n_far; ++f)
       far[f] = ObsFarLaunch{h->far[f].terms.p, h->far[f].n_terms, h->far[f].groups.p, h->far[f].n_groups, h->far[f].far_hi};
-    HIPCHK(launch_apply_observable(h->psi.p, store_lambda ? h->lam.p : nullptr, n_eff, c, h->terms.p,
+    HIPCHK(launch_apply_observable(src, store_lambda ? dst : nullptr, n_eff, c, h->terms.p,
                                    h->n_gather_terms, h->obs_groups.p, h->n_obs_groups, d_upstream,
                                    uint32_t(h->model.n_ops), s0, h->op_scale.p, value_mode ? h->vals64.p : nullptr,
                                    h->value_part.p, observable_xcd_states(h), stream, false, far, h->n_far));
@@ -1670,6 +1682,10 @@ int qhbm_set_option(qhbm_engine* h, const char* name, int64_t value) {
   else if (k == "values_from_observable") h->opt_values_from_obs = int(value);
   else if (k == "cph_wave_bits") { h->opt_cph_wave_bits = int(value); invalidate_plans(h); }
   else if (k == "chunk_states") h->opt_chunk = value;
+  else if (k == "evolve_step_argument") {
+    if (value < 1 || value > 64) return fail(h, "evolve_step_argument: 1 .. 64");
+    h->opt_evolve_step = int(value);
+  }
   else if (k == "workspace_budget_mb") h->opt_budget_mb = std::max<int64_t>(0, value);  // 0 = default
   else if (k == "profile_events") h->opt_profile = int(value);
   else return fail(h, "unknown option '" + k + "'");
@@ -1935,6 +1951,238 @@ int qhbm_describe_schedule_from_states(qhbm_engine* h, char* buf, size_t buf_len
   std::snprintf(line, sizeof(line), "adjoint time model: %.2f us per state\n", 1e6 * adjoint_plan_seconds(h->adj.plan, h->model));
   s += line;
   std::snprintf(buf, buf_len, "%s", s.c_str());
+  return 0;
+}
+
+// ---- Chebyshev evolution of caller-supplied states (include/qhbm_engine.h): e^{-tau H} and e^{-i tau H}
+// for H = sum_k w_k O_k over the installed observables, from repeated launches of the lambda = O psi kernels ----
+}  // extern "C"
+
+namespace {
+
+// What (weights, tau, mode) and the installed observables fix: nothing of it is read from the device.
+struct EvolvePlan {
+  double R = 0.0;  // sum_k |w_k| sum_j |c_kj| >= ||H||
+  int steps = 0;   // m = ceil(|tau| R / evolve_step_argument)
+  int terms = 0;   // K: H-applications of one step
+  double x = 0.0;  // |tau| R / m
+  std::vector<double> re, im;  // c_0 .. c_K of a step: sum_k c_k T_k(H / R)
+};
+
+// f_k proportional to I_k(x) (mode 0) or J_k(x) (mode 1), k = 0 .. N, by Miller's backward recurrence; normalised with
+// I_0 + 2 sum I_k = e^x (so the result is e^{-x} I_k) or J_0 + 2 sum J_2k = 1.
+std::vector<double> bessel_sequence(double x, int mode) {
+  const int N = 2 * int(std::ceil(x)) + 64;
+  std::vector<double> f(size_t(N) + 2, 0.0);
+  f[size_t(N)] = 1.0;
+  for (int k = N; k >= 1; --k) {
+    const double up = mode == 0 ? f[size_t(k) + 1] : -f[size_t(k) + 1];
+    f[size_t(k) - 1] = (2.0 * double(k) / x) * f[size_t(k)] + up;
+    if (std::fabs(f[size_t(k) - 1]) > 1e250)
+      for (int j = k - 1; j <= N; ++j) f[size_t(j)] *= 1e-250;
+  }
+  double norm = f[0];
+  for (int k = 1; k <= N; ++k)
+    if (mode == 0 || k % 2 == 0) norm += 2.0 * f[size_t(k)];
+  for (double& v : f) v /= norm;
+  f.pop_back();
+  return f;
+}
+
+int make_evolve_plan(qhbm_engine* h, const double* weights, double tau, int mode, EvolvePlan* out) {
+  if (h->model.n_ops <= 0) return fail(h, "qhbm_set_observables has not been called");
+  if (mode != 0 && mode != 1) return fail(h, "mode must be 0 (imaginary time) or 1 (real time)");
+  if (!std::isfinite(tau)) return fail(h, "tau is not finite");
+  if (mode == 0 && tau < 0.0) return fail(h, "tau < 0 in imaginary time (mode 0)");
+  std::vector<double> op_sum(size_t(h->model.n_ops), 0.0);
+  for (const PauliTerm& t : h->model.terms) op_sum[size_t(t.op)] += std::fabs(double(t.coeff));
+  EvolvePlan p;
+  for (int k = 0; k < h->model.n_ops; ++k) {
+    const double w = weights ? weights[k] : 1.0;
+    if (!std::isfinite(w)) return fail(h, "a weight is not finite");
+    p.R += std::fabs(w) * op_sum[size_t(k)];
+  }
+  const double arg = std::fabs(tau) * p.R;
+  if (!std::isfinite(arg) || arg > 1e9) return fail(h, "|tau| R is too large");
+  p.steps = int(std::ceil(arg / double(h->opt_evolve_step)));
+  if (p.steps > 0) {
+    p.x = arg / double(p.steps);
+    const std::vector<double> a = bessel_sequence(p.x, mode);
+    // cut where the discarded tail 2 sum |a_k| falls below 2^-30 (at least one term)
+    double tail = 0.0;
+    int K = int(a.size()) - 1;
+    while (K > 1 && tail + 2.0 * std::fabs(a[size_t(K)]) < std::ldexp(1.0, -30)) tail += 2.0 * std::fabs(a[size_t(K--)]);
+    p.terms = K;
+    const double sgn = tau >= 0.0 ? 1.0 : -1.0;
+    for (int k = 0; k <= K; ++k) {
+      const double v = (k ? 2.0 : 1.0) * a[size_t(k)];
+      if (mode == 0) {
+        p.re.push_back(k % 2 ? -v : v);
+        p.im.push_back(0.0);
+      } else {  // (-i sgn)^k
+        static const double cr[4] = {1.0, 0.0, -1.0, 0.0}, ci[4] = {0.0, -1.0, 0.0, 1.0};
+        p.re.push_back(cr[k % 4] * v);
+        p.im.push_back(ci[k % 4] * sgn * v);
+      }
+    }
+  }
+  *out = std::move(p);
+  return 0;
+}
+
+int check_evolve_states(qhbm_engine* h, const void* d_states, int U, const char* what) {
+  if (U <= 0) return fail(h, "U must be positive");
+  if (!h->have_circuit) return fail(h, "qhbm_set_circuit has not been called");
+  if (h->model.n_ops <= 0) return fail(h, "qhbm_set_observables has not been called");
+  if (!d_states) return fail(h, std::string(what) + " is NULL");
+  if (reinterpret_cast<uintptr_t>(d_states) & 15u) return fail(h, std::string(what) + " must be 16-byte aligned");
+  if (aliases_workspace(h, d_states, size_t(U) * (size_t(8) << h->model.n)))
+    return fail(h, std::string(what) + " lies inside the engine's workspace");
+  return 0;
+}
+
+// w_k * factor (weights NULL: ones) to the device, in stream order; the host copy lives in the engine
+int upload_evolve_weights(qhbm_engine* h, const double* weights, double factor, hipStream_t s) {
+  const size_t n_ops = size_t(h->model.n_ops);
+  h->evo_host_wr.resize(n_ops);
+  for (size_t k = 0; k < n_ops; ++k) h->evo_host_wr[k] = (weights ? weights[k] : 1.0) * factor;
+  HIPCHK(h->evo_wr.reserve(n_ops));
+  HIPCHK(hipMemcpyAsync(h->evo_wr.p, h->evo_host_wr.data(), n_ops * sizeof(double), hipMemcpyHostToDevice, s));
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qhbm_describe_evolution(qhbm_engine* h, const double* weights, double tau, int mode, char* buf, size_t buf_len) {
+  if (!h || !buf || !buf_len) return 1;
+  EvolvePlan p;
+  if (int rc = make_evolve_plan(h, weights, tau, mode, &p)) return rc;
+  std::snprintf(buf, buf_len, "R=%.17g steps=%d terms_per_step=%d applications=%d", p.R, p.steps, p.terms, p.steps * p.terms);
+  return 0;
+}
+
+int qhbm_apply_observables(qhbm_engine* h, const void* d_states, int U, const double* weights, void* d_out_states,
+                           void* stream) {
+  if (!h) return 1;
+  if (int rc = need_device(h)) return rc;
+  if (int rc = check_evolve_states(h, d_states, U, "d_states")) return rc;
+  if (int rc = check_evolve_states(h, d_out_states, U, "d_out_states")) return rc;
+  const size_t row = size_t(8) << h->model.n;
+  {
+    const char *a = static_cast<const char*>(d_states), *b = static_cast<const char*>(d_out_states);
+    if (a < b + size_t(U) * row && b < a + size_t(U) * row) return fail(h, "d_out_states overlaps d_states");
+  }
+  if (weights)
+    for (int k = 0; k < h->model.n_ops; ++k)
+      if (!std::isfinite(weights[k])) return fail(h, "a weight is not finite");
+  DenseScope scope(h);
+  if (int rc = upload_model(h)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  h->retained_U = 0;
+  h->state_grad_U = 0;
+  const uint32_t n = uint32_t(h->model.n), n_eff = uint32_t(h->fwd.plan.n_eff), n_ops = uint32_t(h->model.n_ops);
+  if (int rc = upload_evolve_weights(h, weights, 1.0, s)) return rc;
+  const uint32_t cs = adjoint_chunk_states(h, U);
+  HIPCHK(h->evo_up1.reserve(size_t(cs) * n_ops));
+  if (n != n_eff)
+    if (int rc = ensure_state_buffers(h, cs, true)) return rc;
+  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += cs) {
+    const uint32_t c = std::min<uint32_t>(cs, uint32_t(U) - s0);
+    const float2* in = reinterpret_cast<const float2*>(static_cast<const char*>(d_states) + size_t(s0) * row);
+    float2* out = reinterpret_cast<float2*>(static_cast<char*>(d_out_states) + size_t(s0) * row);
+    HIPCHK(launch_evolve_init(c, nullptr, nullptr, nullptr, h->evo_wr.p, n_ops, h->evo_up1.p, nullptr, s));
+    if (n == n_eff) {  // the caller's pitch is the workspace's: the observable kernel reads and writes the caller's rows
+      if (int rc = run_observable_chunk(h, 0, c, h->evo_up1.p, false, s, true, false, in, out)) return rc;
+    } else {
+      HIPCHK(launch_scale_copy_states(in, n, h->psi.p, n_eff, n, c, nullptr, nullptr, s));
+      if (int rc = run_observable_chunk(h, 0, c, h->evo_up1.p, false, s)) return rc;
+      HIPCHK(launch_scale_copy_states(h->lam.p, n_eff, out, n, n, c, nullptr, nullptr, s));
+    }
+  }
+  return 0;
+}
+
+int qhbm_evolve_states(qhbm_engine* h, void* d_states, int U, const double* weights, double tau, int mode,
+                       double* d_log_norms, void* stream) {
+  if (!h) return 1;
+  if (int rc = need_device(h)) return rc;
+  if (int rc = check_evolve_states(h, d_states, U, "d_states")) return rc;
+  EvolvePlan ep;
+  if (int rc = make_evolve_plan(h, weights, tau, mode, &ep)) return rc;
+  if (mode == 1 && d_log_norms) return fail(h, "d_log_norms must be NULL in real time (mode 1)");
+  DenseScope scope(h);
+  if (int rc = upload_model(h)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  h->retained_U = 0;
+  h->state_grad_U = 0;
+  const uint32_t n = uint32_t(h->model.n), n_eff = uint32_t(h->fwd.plan.n_eff), n_ops = uint32_t(h->model.n_ops);
+  const size_t row = size_t(8) << n, pitch = size_t(1) << n_eff;
+  // R = 0 (H = 0), and no step in real time: the identity -- the states are not written
+  const bool identity = ep.R == 0.0 || (ep.steps == 0 && mode == 1);
+  if (identity && !d_log_norms) return 0;
+  // four state buffers per chunk element: t_{k-1}, t_k in psi, w and the sum in lam
+  uint32_t cs = chunk_states(h, U);
+  if (h->opt_chunk <= 0)
+    cs = uint32_t(std::min<size_t>(std::min<size_t>(size_t(U), 65535), std::max<size_t>(1, budget_bytes(h) / (4 * state_bytes(h)))));
+  if (int rc = ensure_state_buffers(h, 2 * cs, true)) return rc;
+  if (aliases_workspace(h, d_states, size_t(U) * row)) return fail(h, "d_states lies inside the engine's workspace");
+  if (int rc = upload_evolve_weights(h, weights, ep.R > 0.0 ? 1.0 / ep.R : 0.0, s)) return rc;
+  HIPCHK(h->import_norm2.reserve(size_t(U)));
+  HIPCHK(h->import_parts.reserve(import_norm_parts_count(n, cs)));
+  HIPCHK(h->evo_scale.reserve(cs));
+  HIPCHK(h->evo_parts.reserve(cheb_norm_parts_count(n_eff, cs)));
+  HIPCHK(h->evo_up1.reserve(size_t(cs) * n_ops));
+  HIPCHK(h->evo_up2.reserve(size_t(cs) * n_ops));
+  double* log_norm = d_log_norms;
+  if (mode == 0 && !log_norm) {
+    HIPCHK(h->evo_log_norm.reserve(size_t(U)));
+    log_norm = h->evo_log_norm.p;
+  }
+  auto c32 = [&](int k) { return make_float2(float(ep.re[size_t(k)]), float(ep.im[size_t(k)])); };
+  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += cs) {
+    const uint32_t c = std::min<uint32_t>(cs, uint32_t(U) - s0);
+    float2 *A = h->psi.p, *B = h->psi.p + size_t(cs) * pitch, *W = h->lam.p, *ACC = h->lam.p + size_t(cs) * pitch;
+    float2* rows = reinterpret_cast<float2*>(static_cast<char*>(d_states) + size_t(s0) * row);
+    // the sum starts as phi / ||phi|| (zeros for norm 0); ||phi||^2 stays on the device
+    HIPCHK(launch_import_states(static_cast<const float2*>(d_states), n, n_eff, c, s0, ACC, h->import_parts.p, h->import_norm2.p, s));
+    HIPCHK(launch_evolve_init(c, h->import_norm2.p + s0, mode == 0 ? log_norm + s0 : nullptr, h->evo_scale.p, h->evo_wr.p, n_ops,
+                              h->evo_up1.p, h->evo_up2.p, s));
+    if (identity) continue;
+    for (int step = 0; step < ep.steps; ++step) {
+      for (int k = 1; k <= ep.terms; ++k) {
+        const bool first = k == 1, with_norm = mode == 0 && k == ep.terms;
+        // w = (1 / R) H (sum * scale) for the first term (the rescale rides on the upstream row), (2 / R) H t_k after it
+        if (int rc = run_observable_chunk(h, 0, c, first ? h->evo_up1.p : h->evo_up2.p, false, s, true, false, first ? ACC : B, W))
+          return rc;
+        hipEvent_t* ev = timer_begin(h, 0, s);  // (profile_events: the recurrence's sweeps count as forward launches)
+        HIPCHK(launch_cheb_step(first, with_norm, W, A, ACC, n_eff, c, c32(0), c32(k), h->evo_scale.p, h->evo_parts.p, s));
+        timer_end(ev, s);
+        if (first) std::swap(B, W);  // t_1 was written as w
+        else std::swap(A, B);        // t_{k+1} replaced t_{k-1}
+      }
+      // e^{delta R} never touches an amplitude: it enters the log norm as + x
+      if (mode == 0)
+        HIPCHK(launch_finish_step(h->evo_parts.p, n_eff, c, ep.x, log_norm + s0, h->evo_scale.p, h->evo_wr.p, n_ops, h->evo_up1.p, s));
+    }
+    // imaginary time: the sum over its norm; real time: back to the norm of the state as given
+    HIPCHK(launch_scale_copy_states(ACC, n_eff, rows, n, n, c, mode == 0 ? h->evo_scale.p : nullptr,
+                                    mode == 1 ? h->import_norm2.p + s0 : nullptr, s));
+  }
+  return 0;
+}
+
+int qhbm_random_states(void* d_states, int U, int n_qubits, uint64_t seed, uint64_t first_state, void* stream) {
+  if (U < 0) return fail(nullptr, "negative batch size");
+  if (n_qubits < 1 || n_qubits > 34) return fail(nullptr, "n_qubits must be in [1, 34]");
+  if (U == 0) return 0;
+  if (!d_states) return fail(nullptr, "d_states is NULL");
+  if (reinterpret_cast<uintptr_t>(d_states) & 15u) return fail(nullptr, "d_states must be 16-byte aligned");
+  if (first_state + uint64_t(U) > (uint64_t(1) << 32)) return fail(nullptr, "first_state + U exceeds 2^32");
+  hipError_t e = launch_random_states(static_cast<float2*>(d_states), uint32_t(U), uint32_t(n_qubits), seed, uint32_t(first_state),
+                                      static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, std::string("qhbm_random_states: ") + hipGetErrorString(e));
   return 0;
 }
 

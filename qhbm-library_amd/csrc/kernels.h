@@ -259,4 +259,29 @@ hipError_t launch_scale_by_norm2(const float* in, float* out, uint32_t rows, uin
 // st[r, :] *= sqrt(norm2[r]) for `rows` (<= 65535) states of 2^n amplitudes
 hipError_t launch_scale_state_rows(float2* st, uint32_t rows, uint32_t n, const double* norm2, hipStream_t stream);
 
+// ---- Chebyshev evolution of caller-supplied states (thermal.hip) ----
+// Doubles of scratch (`parts`) the norm of a chunk of c states at a pitch of 2^n_eff amplitudes needs.
+size_t cheb_norm_parts_count(uint32_t n_eff, uint32_t c);
+// One term of the recurrence over the chunk's c states (w, tprev, acc: [c, 2^n_eff], distinct buffers):
+//   first:      tprev = t_0 = acc * scale[i], acc = c0 t_0 + coef w            (w = t_1)
+//   otherwise:  tprev = t_{k+1} = w - tprev,  acc += coef t_{k+1}
+// with_norm: parts[i, .] = per-workgroup sums of |acc|^2 (fp64) for launch_finish_step.
+hipError_t launch_cheb_step(bool first, bool with_norm, const float2* w, float2* tprev, float2* acc, uint32_t n_eff, uint32_t c,
+                            float2 c0, float2 coef, const double* scale, double* parts, hipStream_t stream);
+// Per state i < c: norm = sqrt(sum of its parts, in index order), log_norm[i] += log(norm) + x, scale[i] = 1 / norm (0 for
+// norm 0), up1[i, k] = float(wr[k] * scale[i]) for k < n_ops.
+hipError_t launch_finish_step(const double* parts, uint32_t n_eff, uint32_t c, double x, double* log_norm, double* scale,
+                              const double* wr, uint32_t n_ops, float* up1, hipStream_t stream);
+// scale[i] = 1, log_norm[i] = log(norm2[i]) / 2, up1[i, k] = float(wr[k]), up2[i, k] = float(2 wr[k]); scale, log_norm
+// (with norm2), up1 and up2 may each be NULL.
+hipError_t launch_evolve_init(uint32_t c, const double* norm2, double* log_norm, double* scale, const double* wr, uint32_t n_ops,
+                              float* up1, float* up2, hipStream_t stream);
+// dst row r (2^n_dst amplitudes) = src row r (2^n_src amplitudes), its first 2^n_copy amplitudes times
+// scale[r] * sqrt(norm2[r]) (either may be NULL: 1; both NULL: a plain copy), zeros behind them.
+hipError_t launch_scale_copy_states(const float2* src, uint32_t n_src, float2* dst, uint32_t n_dst, uint32_t n_copy, uint32_t c,
+                                    const double* scale, const double* norm2, hipStream_t stream);
+// Random-sign states (include/qhbm_engine.h qhbm_random_states): out [n_states, 2^n]
+hipError_t launch_random_states(float2* out, uint32_t n_states, uint32_t n, uint64_t seed, uint32_t first_state,
+                                hipStream_t stream);
+
 }  // namespace qhbm

@@ -46,6 +46,7 @@ ABI_SYMBOLS = (
     "qhbm_table_expectation_vjp_retained",
     "qhbm_expectation_from_states", "qhbm_expectation_vjp_from_states", "qhbm_statevector_from_states",
     "qhbm_describe_schedule_from_states",
+    "qhbm_apply_observables", "qhbm_evolve_states", "qhbm_describe_evolution", "qhbm_random_states",
 )
 
 
@@ -135,6 +136,10 @@ def load_library():
     lib.qhbm_expectation_vjp_from_states.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     lib.qhbm_statevector_from_states.argtypes = [vp, vp, i32, vp, vp, vp]
     lib.qhbm_describe_schedule_from_states.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t]
+    lib.qhbm_apply_observables.argtypes = [vp, vp, i32, vp, vp, vp]
+    lib.qhbm_evolve_states.argtypes = [vp, vp, i32, vp, ctypes.c_double, i32, vp, vp]
+    lib.qhbm_describe_evolution.argtypes = [vp, vp, ctypes.c_double, i32, ctypes.c_char_p, ctypes.c_size_t]
+    lib.qhbm_random_states.argtypes = [vp, i32, i32, ctypes.c_uint64, ctypes.c_uint64, vp]
   except AttributeError:  # an older library given through QHBM_ENGINE_LIB (A/B runs): the probe is optional there
     pass
   _lib = lib
@@ -311,6 +316,21 @@ def gwg_sample(states, n_bits, masks, thetas, seed, step0, n_steps, write_sample
         out.data_ptr() if out is not None else None, acc.data_ptr() if acc is not None else None,
         ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
   return out, acc
+
+
+def random_states(num_states, n_qubits, seed, first_state=0, device=None):
+  """complex64 [num_states, 2^n_qubits] random-sign states of norm 1 with E[|r><r|] = I / 2^n, written by the engine's
+  `random_states_kernel` from Philox4x32-10 (include/qhbm_engine.h qhbm_random_states): row m is state
+  `first_state` + m of `seed`, whatever the batch it is drawn in."""
+  if not torch.cuda.is_available():
+    raise EngineError("random_states needs a GPU: the engine has no CPU fallback")
+  device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+  out = torch.empty((int(num_states), 1 << int(n_qubits)), dtype=torch.complex64, device=device)
+  with torch.cuda.device(device):
+    _check_global(load_library().qhbm_random_states(out.data_ptr(), int(num_states), int(n_qubits),
+                                                    int(seed) & (2**64 - 1), int(first_state),
+                                                    torch.cuda.current_stream().cuda_stream))
+  return out
 
 
 class Engine:
@@ -711,6 +731,55 @@ class Engine:
       self._check(self._lib.qhbm_statevector_from_states(self._h, states.data_ptr(), states.shape[0], params.data_ptr(),
                                                          out.data_ptr(), self._stream()))
     return out
+
+  # ---- evolving caller-supplied states under H = sum_k w_k O_k of the installed observables ----
+  def _weights(self, weights):
+    if weights is None:
+      return None
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+    if w.shape != (self.n_ops,):
+      raise ValueError(f"{w.shape[0]} weights for {self.n_ops} observables")
+    return w
+
+  def describe_evolution(self, tau, mode=0, weights=None):
+    """{"R", "steps", "terms_per_step", "applications"} of `evolve_states(..., tau, mode, weights)`; needs no device."""
+    w = self._weights(weights)
+    buf = ctypes.create_string_buffer(256)
+    self._check(self._lib.qhbm_describe_evolution(self._h, None if w is None else w.ctypes.data, float(tau), int(mode),
+                                                  buf, len(buf)))
+    fields = dict(item.split("=") for item in buf.value.decode().split())
+    return {k: float(v) if k == "R" else int(v) for k, v in fields.items()}
+
+  def apply_observables(self, states, weights=None):
+    """H phi_u for states [batch, 2^n] complex64, H = sum_k weights[k] O_k (default: all ones); a new tensor."""
+    states, _ = self._prep_states(states, np.zeros(self.n_params, np.float32))
+    w = self._weights(weights)
+    out = torch.empty_like(states)
+    self.retained = None
+    with torch.cuda.device(self.device):
+      self._check(self._lib.qhbm_apply_observables(self._h, states.data_ptr(), states.shape[0],
+                                                   None if w is None else w.ctypes.data, out.data_ptr(), self._stream()))
+    return out
+
+  def evolve_states(self, states, tau, mode=0, weights=None, in_place=False):
+    """mode 0: (e^{-tau H} phi_u normalised, float64 [batch] log ||e^{-tau H} phi_u|| of the states as given);
+    mode 1: (e^{-i tau H} phi_u, None).  The input is copied unless `in_place` (then it must be a contiguous, 16-byte
+    aligned complex64 tensor on the engine's device, and is overwritten)."""
+    given = states
+    states, _ = self._prep_states(states, np.zeros(self.n_params, np.float32))
+    if in_place:
+      if states.data_ptr() != torch.as_tensor(given).data_ptr():
+        raise ValueError("in_place needs a contiguous, 16-byte aligned complex64 tensor on the engine's device")
+    elif torch.is_tensor(given) and states.data_ptr() == given.data_ptr():
+      states = states.clone()
+    w = self._weights(weights)
+    log_norms = torch.empty((states.shape[0],), dtype=torch.float64, device=self.device) if int(mode) == 0 else None
+    self.retained = None
+    with torch.cuda.device(self.device):
+      self._check(self._lib.qhbm_evolve_states(self._h, states.data_ptr(), states.shape[0],
+                                               None if w is None else w.ctypes.data, float(tau), int(mode),
+                                               None if log_norms is None else log_norms.data_ptr(), self._stream()))
+    return states, log_norms
 
   def sample(self, bits, params, n_shots, seed=0, shift_gate=-1, shift=0.0):
     """int8 [batch, n_shots, n_qubits]: computational-basis samples of C(params)|x_u>;

@@ -70,6 +70,14 @@ class StateVectorData(QuantumData):
     states = evecs[:, keep].transpose(0, 1).to(torch.complex128)
     return cls(states, evals[keep], qubits)
 
+  @classmethod
+  def thermal(cls, operators, beta, **kwargs):
+    """The thermal state of H = sum_k operators[k] at inverse temperature `beta` as quantum data, without a dense
+    matrix: thermal pure quantum states from the engine's imaginary-time evolution
+    (`inference.thermal_ensemble(operators, beta, **kwargs).data()`; `start="basis"` is exact up to 14 qubits)."""
+    from qhbmlib_amd.inference import thermal  # pylint: disable=import-outside-toplevel
+    return thermal.thermal_ensemble(operators, beta, **kwargs).data()
+
   def _inference_for(self, qubits):
     # (imported here: qhbmlib_amd.inference imports the losses, which take QuantumData)
     from qhbmlib_amd.inference import qnn  # pylint: disable=import-outside-toplevel

@@ -12,9 +12,12 @@ from qhbmlib_amd.inference.qmhl_loss import qmhl
 from qhbmlib_amd.inference.qnn import (AnalyticQuantumInference, QuantumInference,
                                        SampledQuantumInference)
 from qhbmlib_amd.inference.qnn_utils import unitary
+from qhbmlib_amd.inference.thermal import (ThermalEnsemble, imaginary_time_evolution, real_time_evolution,
+                                           thermal_ensemble)
 from qhbmlib_amd.inference.vqt_loss import vqt
 
 __all__ = ["AnalyticEnergyInference", "AnalyticQuantumInference", "BernoulliEnergyInference", "CapturedLoss",
            "EnergyInference", "EnergyInferenceBase", "GibbsWithGradientsInference", "QHBM", "QuantumInference",
-           "SampledQuantumInference", "density_matrix",
-           "fidelity", "information_matrix", "natural_gradient", "probabilities", "qmhl", "unitary", "vqt"]
+           "SampledQuantumInference", "ThermalEnsemble", "density_matrix",
+           "fidelity", "imaginary_time_evolution", "information_matrix", "natural_gradient", "probabilities", "qmhl",
+           "real_time_evolution", "thermal_ensemble", "unitary", "vqt"]
