@@ -340,6 +340,39 @@ int qhbm_evolve_states(qhbm_engine* h, void* d_states, int U, const double* weig
 int qhbm_describe_evolution(qhbm_engine* h, const double* weights, double tau, int mode, char* buf, size_t len);
 int qhbm_random_states(void* d_states, int U, int n_qubits, uint64_t seed, uint64_t first_state, void* stream);
 
+/* ---- Krylov spaces of caller-supplied states: ground states, spectra, whole beta ladders ----
+ * Added WITHIN ABI version 5: purely additive, QHBM_ABI_VERSION stays 5.
+ *
+ * H, `weights` and R as for qhbm_evolve_states.  Per start state phi the Lanczos recurrence, j = 0 .. m - 1:
+ *   v_0 = phi / ||phi||;  w = H v_j;  per round c_i = <v_i, w> for i in [lo, j] (float64 sums), then
+ *   w <- w - sum_i c_i v_i, i ascending, c_i rounded to complex64;  alpha_j = sum over rounds of Re c_j;
+ *   beta_j = ||w|| (float64);  v_{j+1} = w / beta_j.
+ * reorth = 1: lo = 0 and two rounds (full reorthogonalisation, classical Gram-Schmidt twice); reorth = 0: lo = max(0, j - 1)
+ * and one round (local).  beta_j <= 2^-16 R: the space is exhausted -- length = j + 1, beta_j = 0, every later alpha and
+ * beta is 0 and every later basis row is exact zeros; otherwise length = m.  beta_{m-1} is stored although v_m is not
+ * (residuals need it).  A start state of norm 0 has length 0 and an all-zero basis.  T = tridiag(alpha[:length],
+ * beta[:length - 1]) then holds what the space knows of H: V e^{-tau T} e_1 ||phi|| ~ e^{-tau H} phi for every tau at once.
+ *
+ *   qhbm_krylov_basis     d_basis [m, U, 2^n] complex64, STEP-MAJOR and caller-owned (row j of consecutive states is
+ *                         contiguous); d_alpha, d_beta [U, m] float64; d_lengths [U] int32; all on the device.  Asynchronous
+ *                         on `stream`, nothing is read back: the breakdown decision lives on the device.  Two state buffers
+ *                         per chunk element are cut from workspace_budget_mb / chunk_states; results do not depend on the
+ *                         chunking nor on which other states share the call (no floating-point atomics).  Refused, each with
+ *                         a message: m outside [1, 1024]; reorth not 0 or 1; U <= 0; no observables installed; a NULL or
+ *                         misaligned pointer (states 16 bytes); the basis or the start states inside the workspace; the
+ *                         basis overlapping the start states.
+ *   qhbm_krylov_combine   d_out_states[u, s] = sum_j d_coef[u, s, j] d_basis[j, u], j ascending in fp32; d_coef [U, S, m]
+ *                         complex64, d_out_states [U, S, 2^n_qubits].  No engine: the current device.  Refused: S < 1, m
+ *                         outside [1, 1024], U <= 0, a NULL or misaligned pointer.
+ *   qhbm_describe_krylov  "basis_bytes=... workspace_bytes=... applications=... chunk_states=... krylov_bytes_per_state=..."
+ *                         of such a call: the bytes the project / subtract / normalise kernels and the import move per
+ *                         state by the model of DESIGN.md 6h; needs no device */
+int qhbm_krylov_basis(qhbm_engine* h, const void* d_start_states, int U, const double* weights, int m, int reorth,
+                      void* d_basis, double* d_alpha, double* d_beta, int32_t* d_lengths, void* stream);
+int qhbm_krylov_combine(const void* d_basis, int m, int U, int n_qubits, const void* d_coef, int S, void* d_out_states,
+                        void* stream);
+int qhbm_describe_krylov(qhbm_engine* h, int U, int m, int reorth, char* buf, size_t len);
+
 /* Computational-basis samples of the final states (tfq.layers.Sample as used at
  * qhbmlib/inference/qnn.py:169,177-181,286-291):
  *   d_out_samples [U, n_shots, n_qubits] int8 (device); shot j of state u is drawn from

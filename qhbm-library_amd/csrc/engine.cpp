@@ -228,6 +228,10 @@ struct qhbm_engine {
   std::vector<double> evo_host_wr;            // w_k / R (or w_k) of the call in flight: the source of an asynchronous copy
   DevBuf<double> evo_wr, evo_scale, evo_parts, evo_log_norm;  // [n_ops], [chunk], norm partials, [U] when the caller wants none
   DevBuf<float> evo_up1, evo_up2;             // [chunk, n_ops] upstream rows: (w_k / R) * scale of the state, 2 w_k / R
+  // Lanczos bases of caller states (qhbm_krylov_basis; krylov.hip): per-workgroup partials of a block of inner products and
+  // of ||w||^2, the round's coefficients [chunk, m] complex64
+  DevBuf<double> kry_parts, kry_norm_parts;
+  DevBuf<float2> kry_coef;
 };
 
 namespace {
@@ -270,7 +274,7 @@ size_t own_bytes(const qhbm_engine* h) {
                       buf_bytes(o.param_slots) + buf_bytes(o.slot_factor) + buf_bytes(o.shift_phases) + buf_bytes(h->import_parts) +
                       buf_bytes(h->import_norm2) + buf_bytes(h->import_up) + buf_bytes(h->import_bits) + buf_bytes(h->evo_wr) +
                       buf_bytes(h->evo_scale) + buf_bytes(h->evo_parts) + buf_bytes(h->evo_log_norm) + buf_bytes(h->evo_up1) +
-                      buf_bytes(h->evo_up2);
+                      buf_bytes(h->evo_up2) + buf_bytes(h->kry_parts) + buf_bytes(h->kry_norm_parts) + buf_bytes(h->kry_coef);
            for (const auto& kv : o.adj_cache) b += plan_bytes(*kv.second);
            return b;
          }();
@@ -1989,19 +1993,26 @@ std::vector<double> bessel_sequence(double x, int mode) {
   return f;
 }
 
+// R = sum_k |w_k| sum_j |c_kj| over the installed observables (weights NULL: ones); refuses a weight that is not finite
+int weighted_radius(qhbm_engine* h, const double* weights, double* R) {
+  std::vector<double> op_sum(size_t(h->model.n_ops), 0.0);
+  for (const PauliTerm& t : h->model.terms) op_sum[size_t(t.op)] += std::fabs(double(t.coeff));
+  *R = 0.0;
+  for (int k = 0; k < h->model.n_ops; ++k) {
+    const double w = weights ? weights[k] : 1.0;
+    if (!std::isfinite(w)) return fail(h, "a weight is not finite");
+    *R += std::fabs(w) * op_sum[size_t(k)];
+  }
+  return 0;
+}
+
 int make_evolve_plan(qhbm_engine* h, const double* weights, double tau, int mode, EvolvePlan* out) {
   if (h->model.n_ops <= 0) return fail(h, "qhbm_set_observables has not been called");
   if (mode != 0 && mode != 1) return fail(h, "mode must be 0 (imaginary time) or 1 (real time)");
   if (!std::isfinite(tau)) return fail(h, "tau is not finite");
   if (mode == 0 && tau < 0.0) return fail(h, "tau < 0 in imaginary time (mode 0)");
-  std::vector<double> op_sum(size_t(h->model.n_ops), 0.0);
-  for (const PauliTerm& t : h->model.terms) op_sum[size_t(t.op)] += std::fabs(double(t.coeff));
   EvolvePlan p;
-  for (int k = 0; k < h->model.n_ops; ++k) {
-    const double w = weights ? weights[k] : 1.0;
-    if (!std::isfinite(w)) return fail(h, "a weight is not finite");
-    p.R += std::fabs(w) * op_sum[size_t(k)];
-  }
+  if (int rc = weighted_radius(h, weights, &p.R)) return rc;
   const double arg = std::fabs(tau) * p.R;
   if (!std::isfinite(arg) || arg > 1e9) return fail(h, "|tau| R is too large");
   p.steps = int(std::ceil(arg / double(h->opt_evolve_step)));
@@ -2170,6 +2181,158 @@ int qhbm_evolve_states(qhbm_engine* h, void* d_states, int U, const double* weig
     HIPCHK(launch_scale_copy_states(ACC, n_eff, rows, n, n, c, mode == 0 ? h->evo_scale.p : nullptr,
                                     mode == 1 ? h->import_norm2.p + s0 : nullptr, s));
   }
+  return 0;
+}
+
+// ---- Lanczos bases of caller-supplied states (include/qhbm_engine.h; krylov.hip) ----
+}  // extern "C"
+
+namespace {
+
+constexpr int kKrylovMaxSteps = 1024;
+constexpr int kKrylovBlock = 8;  // basis rows per project / subtract sweep (krylov.hip kKryBlock)
+
+int check_krylov_shape(qhbm_engine* h, int U, int m, int reorth) {
+  if (U <= 0) return fail(h, "U must be positive");
+  if (m < 1 || m > kKrylovMaxSteps) return fail(h, "m must be in [1, 1024]");
+  if (reorth != 0 && reorth != 1) return fail(h, "reorth must be 0 (local) or 1 (full)");
+  if (!h->have_circuit) return fail(h, "qhbm_set_circuit has not been called");
+  if (h->model.n_ops <= 0) return fail(h, "qhbm_set_observables has not been called");
+  return 0;
+}
+
+// Sweeps of one state's words by the project / subtract / normalise kernels of a whole basis, in units of one state
+// (8 * 2^n bytes): per round and block of nb rows, project reads w and nb rows, subtract reads w and nb rows and writes w;
+// the normalised write reads w and writes a row; the import reads the start state twice and writes row 0.
+double krylov_state_sweeps(int m, int reorth) {
+  double sweeps = 3.0;
+  for (int j = 0; j < m; ++j) {
+    const int lo = reorth ? 0 : std::max(0, j - 1), rows = j - lo + 1, blocks = (rows + kKrylovBlock - 1) / kKrylovBlock;
+    sweeps += double(reorth ? 2 : 1) * double(3 * blocks + 2 * rows) + (j + 1 < m ? 2.0 : 0.0);
+  }
+  return sweeps;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qhbm_describe_krylov(qhbm_engine* h, int U, int m, int reorth, char* buf, size_t buf_len) {
+  if (!h || !buf || !buf_len) return 1;
+  if (int rc = check_krylov_shape(h, U, m, reorth)) return rc;
+  DenseScope scope(h);
+  if (int rc = build_plans(h)) return rc;
+  const double state = double(size_t(8) << h->model.n);
+  const uint32_t cs = adjoint_chunk_states(h, U);
+  std::snprintf(buf, buf_len, "basis_bytes=%.17g workspace_bytes=%.17g applications=%d chunk_states=%u krylov_bytes_per_state=%.17g",
+                double(m) * double(U) * state, 2.0 * double(cs) * double(state_bytes(h)), m, cs, krylov_state_sweeps(m, reorth) * state);
+  return 0;
+}
+
+int qhbm_krylov_basis(qhbm_engine* h, const void* d_start_states, int U, const double* weights, int m, int reorth,
+                      void* d_basis, double* d_alpha, double* d_beta, int32_t* d_lengths, void* stream) {
+  if (!h) return 1;
+  if (int rc = need_device(h)) return rc;
+  if (int rc = check_krylov_shape(h, U, m, reorth)) return rc;
+  if (int rc = check_evolve_states(h, d_start_states, U, "d_start_states")) return rc;
+  if (!d_basis) return fail(h, "d_basis is NULL");
+  if (reinterpret_cast<uintptr_t>(d_basis) & 15u) return fail(h, "d_basis must be 16-byte aligned");
+  if (!d_alpha || !d_beta || !d_lengths) return fail(h, "d_alpha / d_beta / d_lengths is NULL");
+  if ((reinterpret_cast<uintptr_t>(d_alpha) | reinterpret_cast<uintptr_t>(d_beta)) & 7u)
+    return fail(h, "d_alpha / d_beta must be 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_lengths) & 3u) return fail(h, "d_lengths must be 4-byte aligned");
+  const uint32_t n = uint32_t(h->model.n);
+  const size_t row = size_t(8) << n, basis_bytes = size_t(m) * size_t(U) * row;
+  {
+    const char *a = static_cast<const char*>(d_start_states), *b = static_cast<const char*>(d_basis);
+    if (a < b + basis_bytes && b < a + size_t(U) * row) return fail(h, "d_basis overlaps d_start_states");
+  }
+  double R = 0.0;
+  if (int rc = weighted_radius(h, weights, &R)) return rc;
+  DenseScope scope(h);
+  if (int rc = upload_model(h)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  h->retained_U = 0;
+  h->state_grad_U = 0;
+  const uint32_t n_eff = uint32_t(h->fwd.plan.n_eff), n_ops = uint32_t(h->model.n_ops);
+  const uint32_t cs = adjoint_chunk_states(h, U);
+  if (int rc = ensure_state_buffers(h, cs, true)) return rc;
+  if (aliases_workspace(h, d_start_states, size_t(U) * row)) return fail(h, "d_start_states lies inside the engine's workspace");
+  if (aliases_workspace(h, d_basis, basis_bytes)) return fail(h, "d_basis lies inside the engine's workspace");
+  if (int rc = upload_evolve_weights(h, weights, 1.0, s)) return rc;
+  HIPCHK(h->import_norm2.reserve(size_t(U)));
+  HIPCHK(h->import_parts.reserve(import_norm_parts_count(n, cs)));
+  HIPCHK(h->evo_scale.reserve(cs));
+  HIPCHK(h->evo_up1.reserve(size_t(cs) * n_ops));
+  HIPCHK(h->kry_parts.reserve(krylov_coef_parts_count(n, cs)));
+  HIPCHK(h->kry_norm_parts.reserve(krylov_norm_parts_count(n, cs)));
+  HIPCHK(h->kry_coef.reserve(size_t(cs) * size_t(m)));
+  HIPCHK(launch_zero_fill(d_alpha, size_t(U) * size_t(m) * sizeof(double), s));
+  const double threshold = std::ldexp(R, -16);
+  const size_t amps = size_t(1) << n, stride = size_t(U) * amps;  // amplitudes from one basis row to the next
+  float2* basis = static_cast<float2*>(d_basis);
+  float2* W = h->lam.p;
+  const int rounds = reorth ? 2 : 1;
+  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += cs) {
+    const uint32_t c = std::min<uint32_t>(cs, uint32_t(U) - s0);
+    // v_0 = phi / ||phi|| straight into row 0 at the caller's pitch (zeros for norm 0); ||phi||^2 stays on the device
+    hipEvent_t* iev = timer_begin(h, 0, s);  // (profile_events: the import and the Krylov kernels count as forward launches)
+    HIPCHK(launch_import_states(static_cast<const float2*>(d_start_states), n, n, c, s0, basis + size_t(s0) * amps, h->import_parts.p,
+                                h->import_norm2.p, s));
+    timer_end(iev, s);
+    HIPCHK(launch_krylov_init(c, h->import_norm2.p + s0, m, d_lengths + s0, h->evo_scale.p, s));
+    HIPCHK(launch_evolve_init(c, nullptr, nullptr, nullptr, h->evo_wr.p, n_ops, h->evo_up1.p, nullptr, s));
+    for (int j = 0; j < m; ++j) {
+      const float2* vj = basis + size_t(j) * stride + size_t(s0) * amps;
+      // w = H v_j: row j of the chunk is contiguous, so at n = n_eff the observable kernel reads the basis itself
+      if (n == n_eff) {
+        if (int rc = run_observable_chunk(h, 0, c, h->evo_up1.p, false, s, true, false, vj, W)) return rc;
+      } else {
+        HIPCHK(launch_scale_copy_states(vj, n, h->psi.p, n_eff, n, c, nullptr, nullptr, s));
+        if (int rc = run_observable_chunk(h, 0, c, h->evo_up1.p, false, s)) return rc;
+      }
+      hipEvent_t* ev = timer_begin(h, 0, s);
+      const int lo = reorth ? 0 : std::max(0, j - 1), rows = j - lo + 1;
+      for (int round = 0; round < rounds; ++round) {
+        // classical Gram-Schmidt: every c_i of the round from the same w, then the subtractions, i ascending
+        for (int b0 = 0; b0 < rows; b0 += kKrylovBlock) {
+          const int nb = std::min(kKrylovBlock, rows - b0), i0 = lo + b0;
+          HIPCHK(launch_krylov_project(W, n_eff, basis + size_t(i0) * stride + size_t(s0) * amps, stride, n, c, uint32_t(nb),
+                                       h->kry_parts.p, h->kry_coef.p, uint32_t(m), uint32_t(b0), j >= i0 && j < i0 + nb ? j - i0 : -1,
+                                       d_alpha + size_t(s0) * size_t(m) + size_t(j), uint64_t(m), s));
+        }
+        for (int b0 = 0; b0 < rows; b0 += kKrylovBlock) {
+          const int nb = std::min(kKrylovBlock, rows - b0), i0 = lo + b0;
+          const bool last = round + 1 == rounds && b0 + nb == rows;
+          HIPCHK(launch_krylov_subtract(W, n_eff, basis + size_t(i0) * stride + size_t(s0) * amps, stride, n, c, uint32_t(nb),
+                                        h->kry_coef.p + b0, uint32_t(m), last ? h->kry_norm_parts.p : nullptr, s));
+        }
+      }
+      HIPCHK(launch_krylov_norm(h->kry_norm_parts.p, n, c, threshold, j, d_beta + size_t(s0) * size_t(m), uint64_t(m), d_lengths + s0,
+                                h->evo_scale.p, s));
+      // v_{j+1} = w / beta_j (scale 0 after a breakdown: zeros)
+      if (j + 1 < m)
+        HIPCHK(launch_scale_copy_states(W, n_eff, basis + size_t(j + 1) * stride + size_t(s0) * amps, n, n, c, h->evo_scale.p, nullptr, s));
+      timer_end(ev, s);
+    }
+  }
+  return 0;
+}
+
+int qhbm_krylov_combine(const void* d_basis, int m, int U, int n_qubits, const void* d_coef, int S, void* d_out_states,
+                        void* stream) {
+  if (m < 1 || m > kKrylovMaxSteps) return fail(nullptr, "m must be in [1, 1024]");
+  if (U <= 0) return fail(nullptr, "U must be positive");
+  if (S < 1) return fail(nullptr, "S must be at least 1");
+  if (n_qubits < 1 || n_qubits > 34) return fail(nullptr, "n_qubits must be in [1, 34]");
+  if (!d_basis || !d_coef || !d_out_states) return fail(nullptr, "d_basis / d_coef / d_out_states is NULL");
+  if ((reinterpret_cast<uintptr_t>(d_basis) | reinterpret_cast<uintptr_t>(d_out_states)) & 15u)
+    return fail(nullptr, "d_basis / d_out_states must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_coef) & 7u) return fail(nullptr, "d_coef must be 8-byte aligned");
+  hipError_t e = launch_krylov_combine(static_cast<const float2*>(d_basis), uint32_t(m), uint32_t(U), uint32_t(n_qubits),
+                                       static_cast<const float2*>(d_coef), uint32_t(S), static_cast<float2*>(d_out_states),
+                                       static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, std::string("qhbm_krylov_combine: ") + hipGetErrorString(e));
   return 0;
 }
 

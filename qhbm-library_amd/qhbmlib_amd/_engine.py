@@ -47,6 +47,7 @@ ABI_SYMBOLS = (
     "qhbm_expectation_from_states", "qhbm_expectation_vjp_from_states", "qhbm_statevector_from_states",
     "qhbm_describe_schedule_from_states",
     "qhbm_apply_observables", "qhbm_evolve_states", "qhbm_describe_evolution", "qhbm_random_states",
+    "qhbm_krylov_basis", "qhbm_krylov_combine", "qhbm_describe_krylov",
 )
 
 
@@ -140,6 +141,9 @@ def load_library():
     lib.qhbm_evolve_states.argtypes = [vp, vp, i32, vp, ctypes.c_double, i32, vp, vp]
     lib.qhbm_describe_evolution.argtypes = [vp, vp, ctypes.c_double, i32, ctypes.c_char_p, ctypes.c_size_t]
     lib.qhbm_random_states.argtypes = [vp, i32, i32, ctypes.c_uint64, ctypes.c_uint64, vp]
+    lib.qhbm_krylov_basis.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]
+    lib.qhbm_krylov_combine.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp]
+    lib.qhbm_describe_krylov.argtypes = [vp, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
   except AttributeError:  # an older library given through QHBM_ENGINE_LIB (A/B runs): the probe is optional there
     pass
   _lib = lib
@@ -330,6 +334,26 @@ def random_states(num_states, n_qubits, seed, first_state=0, device=None):
     _check_global(load_library().qhbm_random_states(out.data_ptr(), int(num_states), int(n_qubits),
                                                     int(seed) & (2**64 - 1), int(first_state),
                                                     torch.cuda.current_stream().cuda_stream))
+  return out
+
+
+def krylov_combine(basis, coef):
+  """out[u, s] = sum_j coef[u, s, j] basis[j, u] for a step-major basis [m, U, 2^n] and coefficients [U, S, m], both
+  complex64 on one device: complex64 [U, S, 2^n], every basis word read once per eight outputs (include/qhbm_engine.h
+  qhbm_krylov_combine)."""
+  if not (torch.is_tensor(basis) and basis.is_cuda and basis.dtype == torch.complex64 and basis.dim() == 3 and basis.is_contiguous()):
+    raise EngineError("krylov_combine needs a contiguous complex64 CUDA basis [m, U, 2^n]")
+  m, num, dim = (int(v) for v in basis.shape)
+  n = dim.bit_length() - 1
+  if dim != (1 << n) or n < 1:
+    raise ValueError(f"basis rows have {dim} amplitudes: not a power of two")
+  coef = torch.as_tensor(coef).to(device=basis.device, dtype=torch.complex64).contiguous()
+  if coef.dim() != 3 or coef.shape[0] != num or coef.shape[2] != m:
+    raise ValueError(f"coef must have shape [{num}, S, {m}], got {tuple(coef.shape)}")
+  out = torch.empty((num, int(coef.shape[1]), dim), dtype=torch.complex64, device=basis.device)
+  with torch.cuda.device(basis.device):
+    _check_global(load_library().qhbm_krylov_combine(basis.data_ptr(), m, num, n, coef.data_ptr(), int(coef.shape[1]),
+                                                     out.data_ptr(), torch.cuda.current_stream().cuda_stream))
   return out
 
 
@@ -780,6 +804,35 @@ class Engine:
                                                None if w is None else w.ctypes.data, float(tau), int(mode),
                                                None if log_norms is None else log_norms.data_ptr(), self._stream()))
     return states, log_norms
+
+  def describe_krylov(self, num_states, num_steps, reorthogonalise=True):
+    """{"basis_bytes", "workspace_bytes", "applications", "chunk_states", "krylov_bytes_per_state"} of
+    `krylov_basis` on `num_states` states; needs no device."""
+    buf = ctypes.create_string_buffer(512)
+    self._check(self._lib.qhbm_describe_krylov(self._h, int(num_states), int(num_steps), int(bool(reorthogonalise)), buf, len(buf)))
+    fields = dict(item.split("=") for item in buf.value.decode().split())
+    return {k: int(v) if k in ("applications", "chunk_states") else float(v) for k, v in fields.items()}
+
+  def krylov_basis(self, states, num_steps, weights=None, reorthogonalise=True):
+    """(basis [m, batch, 2^n] complex64 step-major, alpha [batch, m], beta [batch, m] float64, lengths [batch] int32,
+    start norms [batch] float64), all on the device: the Lanczos recurrence of H = sum_k weights[k] O_k from each state
+    (include/qhbm_engine.h qhbm_krylov_basis).  The input is never written."""
+    states, _ = self._prep_states(states, np.zeros(self.n_params, np.float32))
+    w = self._weights(weights)
+    m, num = int(num_steps), states.shape[0]
+    if not 1 <= m <= 1024:
+      raise ValueError("num_steps must be in [1, 1024]")
+    basis = torch.empty((m, num, 1 << self.n_qubits), dtype=torch.complex64, device=self.device)
+    alpha = torch.empty((num, m), dtype=torch.float64, device=self.device)
+    beta = torch.empty((num, m), dtype=torch.float64, device=self.device)
+    lengths = torch.empty((num,), dtype=torch.int32, device=self.device)
+    self.retained = None
+    with torch.cuda.device(self.device):
+      self._check(self._lib.qhbm_krylov_basis(self._h, states.data_ptr(), num, None if w is None else w.ctypes.data, m,
+                                              int(bool(reorthogonalise)), basis.data_ptr(), alpha.data_ptr(), beta.data_ptr(),
+                                              lengths.data_ptr(), self._stream()))
+    norms = torch.linalg.vector_norm(torch.view_as_real(states).flatten(1), dim=1, dtype=torch.float64)
+    return basis, alpha, beta, lengths, norms
 
   def sample(self, bits, params, n_shots, seed=0, shift_gate=-1, shift=0.0):
     """int8 [batch, n_shots, n_qubits]: computational-basis samples of C(params)|x_u>;

@@ -78,6 +78,16 @@ class StateVectorData(QuantumData):
     from qhbmlib_amd.inference import thermal  # pylint: disable=import-outside-toplevel
     return thermal.thermal_ensemble(operators, beta, **kwargs).data()
 
+  @classmethod
+  def ground_state(cls, operators, **kwargs):
+    """The ground state of H = sum_k operators[k] as quantum data (one state, weight 1), without a dense matrix: the
+    lowest Ritz vector of a restarted Krylov space (`inference.ground_state(operators, **kwargs)`)."""
+    from qhbmlib_amd.inference import krylov, thermal  # pylint: disable=import-outside-toplevel
+    ops = thermal._operator_list(operators)  # pylint: disable=protected-access
+    qubits = thermal._qubits_of(ops, kwargs.get("qubits"))  # pylint: disable=protected-access
+    _, state, _, _ = krylov.ground_state(operators, **kwargs)
+    return cls(state.reshape(1, -1), torch.ones(1, dtype=torch.float64), qubits)
+
   def _inference_for(self, qubits):
     # (imported here: qhbmlib_amd.inference imports the losses, which take QuantumData)
     from qhbmlib_amd.inference import qnn  # pylint: disable=import-outside-toplevel

@@ -6,6 +6,8 @@ from qhbmlib_amd.inference.ebm import (AnalyticEnergyInference, BernoulliEnergyI
                                        GibbsWithGradientsInference)
 from qhbmlib_amd.inference.ebm_utils import probabilities
 from qhbmlib_amd.inference.information import information_matrix, natural_gradient
+from qhbmlib_amd.inference.krylov import (KrylovSpace, ThermalSweep, ground_state, krylov_space, spectrum_extremes,
+                                          thermal_sweep)
 from qhbmlib_amd.inference.qhbm import QHBM
 from qhbmlib_amd.inference.qhbm_utils import density_matrix, fidelity
 from qhbmlib_amd.inference.qmhl_loss import qmhl
@@ -17,7 +19,8 @@ from qhbmlib_amd.inference.thermal import (ThermalEnsemble, imaginary_time_evolu
 from qhbmlib_amd.inference.vqt_loss import vqt
 
 __all__ = ["AnalyticEnergyInference", "AnalyticQuantumInference", "BernoulliEnergyInference", "CapturedLoss",
-           "EnergyInference", "EnergyInferenceBase", "GibbsWithGradientsInference", "QHBM", "QuantumInference",
-           "SampledQuantumInference", "ThermalEnsemble", "density_matrix",
-           "fidelity", "imaginary_time_evolution", "information_matrix", "natural_gradient", "probabilities", "qmhl",
-           "real_time_evolution", "thermal_ensemble", "unitary", "vqt"]
+           "EnergyInference", "EnergyInferenceBase", "GibbsWithGradientsInference", "KrylovSpace", "QHBM", "QuantumInference",
+           "SampledQuantumInference", "ThermalEnsemble", "ThermalSweep", "density_matrix",
+           "fidelity", "ground_state", "imaginary_time_evolution", "information_matrix", "krylov_space", "natural_gradient",
+           "probabilities", "qmhl", "real_time_evolution", "spectrum_extremes", "thermal_ensemble", "thermal_sweep", "unitary",
+           "vqt"]
