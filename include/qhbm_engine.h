@@ -373,6 +373,34 @@ int qhbm_krylov_combine(const void* d_basis, int m, int U, int n_qubits, const v
                         void* stream);
 int qhbm_describe_krylov(qhbm_engine* h, int U, int m, int reorth, char* buf, size_t len);
 
+/* ---- The weighted Gram matrix of M states: fidelity, entropy and relative entropy of state-vector data ----
+ * Added WITHIN ABI version 5: purely additive, QHBM_ABI_VERSION stays 5.
+ *
+ *   G[i, j] = sum_x t(x) conj(s_i(x)) s_j(x)
+ * for M states s_i of 2^n_qubits amplitudes and a real table t over the bitstrings.  With a_m = U^dagger phi_m and
+ * sigma = sum_m w_m |phi_m><phi_m|, W = diag(w): tr(rho sigma) = sum_m w_m G_p[m, m]; the fidelity is (sum_i sqrt(lambda_i))^2
+ * over the spectrum of W^1/2 G_p W^1/2; tr sigma, tr sigma^2, S(sigma) come from the spectrum of W^1/2 G_1 W^1/2; the cross
+ * entropy is sum_m w_m G_E[m, m] + log Z.
+ *
+ *   qhbm_weighted_gram       d_states [M, 2^n_qubits] complex64, interleaved, 16-byte aligned; d_table [2^n_qubits] float32,
+ *                            8-byte aligned, indexed like the amplitudes, or NULL for t = 1; d_gram [M, M, 2] float64
+ *                            (re, im), row-major; all on the device.  No engine: the current device.  Asynchronous on
+ *                            `stream`; allocates nothing, synchronises nothing.  d_scratch: qhbm_gram_scratch_bytes bytes,
+ *                            8-byte aligned, which may hold anything (every partial that is read is written first).
+ *                            Order of additions: a product is float x float in float64 (exact), the column operand s_j
+ *                            times t first (exact); a thread adds its words in word order with fused multiply-adds, the 64
+ *                            lanes of a wave meet in a fixed shuffle tree, the waves add in wave order and the slices in
+ *                            slice order in a second kernel; no floating-point atomics.  The slices depend on n_qubits
+ *                            alone, so G[i, j] depends neither on M nor on which other states share the call.  Only
+ *                            j >= i is summed: G[j, i] is written as the conjugate of G[i, j] and Im G[i, i] as 0.
+ *                            Refused, each with a message and before anything is launched: M outside [1, 1024]; n_qubits
+ *                            outside [1, 31]; d_states, d_scratch or d_gram NULL; a misaligned pointer.
+ *   qhbm_gram_scratch_bytes  *out = the bytes of d_scratch such a call needs: 16 M^2 min(2^n_qubits / 2048, 256), at least
+ *                            16 M^2; needs no device.  Refused: M or n_qubits as above, out NULL. */
+int qhbm_gram_scratch_bytes(int M, int n_qubits, size_t* out);
+int qhbm_weighted_gram(const void* d_states, int M, int n_qubits, const float* d_table, void* d_scratch, double* d_gram,
+                       void* stream);
+
 /* Computational-basis samples of the final states (tfq.layers.Sample as used at
  * qhbmlib/inference/qnn.py:169,177-181,286-291):
  *   d_out_samples [U, n_shots, n_qubits] int8 (device); shot j of state u is drawn from

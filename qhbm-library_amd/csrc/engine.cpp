@@ -2336,6 +2336,30 @@ int qhbm_krylov_combine(const void* d_basis, int m, int U, int n_qubits, const v
   return 0;
 }
 
+// ---- the weighted Gram matrix of M states (include/qhbm_engine.h; gram.hip) ----
+int qhbm_gram_scratch_bytes(int M, int n_qubits, size_t* out) {
+  if (!out) return fail(nullptr, "out is NULL");
+  if (M < 1 || M > kKrylovMaxSteps) return fail(nullptr, "M must be in [1, 1024]");
+  if (n_qubits < 1 || n_qubits > 31) return fail(nullptr, "n_qubits must be in [1, 31]");
+  *out = gram_parts_count(uint32_t(n_qubits), uint32_t(M)) * sizeof(double);
+  return 0;
+}
+
+int qhbm_weighted_gram(const void* d_states, int M, int n_qubits, const float* d_table, void* d_scratch, double* d_gram,
+                       void* stream) {
+  if (M < 1 || M > kKrylovMaxSteps) return fail(nullptr, "M must be in [1, 1024]");
+  if (n_qubits < 1 || n_qubits > 31) return fail(nullptr, "n_qubits must be in [1, 31]");
+  if (!d_states || !d_scratch || !d_gram) return fail(nullptr, "d_states / d_scratch / d_gram is NULL");
+  if (reinterpret_cast<uintptr_t>(d_states) & 15u) return fail(nullptr, "d_states must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_table) & 7u) return fail(nullptr, "d_table must be 8-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_scratch) | reinterpret_cast<uintptr_t>(d_gram)) & 7u)
+    return fail(nullptr, "d_scratch / d_gram must be 8-byte aligned");
+  hipError_t e = launch_weighted_gram(static_cast<const float2*>(d_states), uint32_t(M), uint32_t(n_qubits), d_table,
+                                      static_cast<double*>(d_scratch), d_gram, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, std::string("qhbm_weighted_gram: ") + hipGetErrorString(e));
+  return 0;
+}
+
 int qhbm_random_states(void* d_states, int U, int n_qubits, uint64_t seed, uint64_t first_state, void* stream) {
   if (U < 0) return fail(nullptr, "negative batch size");
   if (n_qubits < 1 || n_qubits > 34) return fail(nullptr, "n_qubits must be in [1, 34]");

@@ -307,4 +307,12 @@ hipError_t launch_krylov_norm(const double* norm_parts, uint32_t n, uint32_t c, 
 hipError_t launch_krylov_combine(const float2* basis, uint32_t m, uint32_t U, uint32_t n, const float2* coef, uint32_t S,
                                  float2* out, hipStream_t stream);
 
+// ---- the weighted Gram matrix of M states (gram.hip) ----
+// Doubles of scratch (`parts`) one Gram matrix of M states of n qubits needs.
+size_t gram_parts_count(uint32_t n, uint32_t M);
+// gram[i, j] = sum_x table[x] conj(states[i, x]) states[j, x] (table NULL: 1), complex fp64 in a fixed order, [M, M, 2];
+// states [M, 2^n]; M in [1, 1024], n in [1, 31].  Every partial that is read is written first: `parts` may hold anything.
+hipError_t launch_weighted_gram(const float2* states, uint32_t M, uint32_t n, const float* table, double* parts, double* gram,
+                                hipStream_t stream);
+
 }  // namespace qhbm

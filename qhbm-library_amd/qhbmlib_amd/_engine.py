@@ -48,6 +48,7 @@ ABI_SYMBOLS = (
     "qhbm_describe_schedule_from_states",
     "qhbm_apply_observables", "qhbm_evolve_states", "qhbm_describe_evolution", "qhbm_random_states",
     "qhbm_krylov_basis", "qhbm_krylov_combine", "qhbm_describe_krylov",
+    "qhbm_gram_scratch_bytes", "qhbm_weighted_gram",
 )
 
 
@@ -144,6 +145,8 @@ def load_library():
     lib.qhbm_krylov_basis.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]
     lib.qhbm_krylov_combine.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp]
     lib.qhbm_describe_krylov.argtypes = [vp, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
+    lib.qhbm_gram_scratch_bytes.argtypes = [i32, i32, ctypes.POINTER(ctypes.c_size_t)]
+    lib.qhbm_weighted_gram.argtypes = [vp, i32, i32, vp, vp, vp, vp]
   except AttributeError:  # an older library given through QHBM_ENGINE_LIB (A/B runs): the probe is optional there
     pass
   _lib = lib
@@ -355,6 +358,40 @@ def krylov_combine(basis, coef):
     _check_global(load_library().qhbm_krylov_combine(basis.data_ptr(), m, num, n, coef.data_ptr(), int(coef.shape[1]),
                                                      out.data_ptr(), torch.cuda.current_stream().cuda_stream))
   return out
+
+
+def gram_scratch_bytes(num_states, n_qubits):
+  """Bytes of scratch one `qhbm_weighted_gram` of `num_states` states of `n_qubits` qubits needs (no device needed)."""
+  out = ctypes.c_size_t()
+  _check_global(load_library().qhbm_gram_scratch_bytes(int(num_states), int(n_qubits), ctypes.byref(out)))
+  return int(out.value)
+
+
+def weighted_gram(states, table=None):
+  """G[i, j] = sum_x table[x] conj(states[i, x]) states[j, x] (table None: 1) for M device-resident states [M, 2^n]:
+  complex128 [M, M], summed in float64 in a fixed order, Hermitian bit for bit with an exactly real diagonal
+  (include/qhbm_engine.h qhbm_weighted_gram).  complex128 states and a float64 table are cast to complex64 / float32; the
+  scratch is this call's own."""
+  if not (torch.is_tensor(states) and states.is_cuda and states.dim() == 2 and states.is_complex()):
+    raise EngineError("weighted_gram needs complex CUDA states [M, 2^n]: the engine has no CPU fallback")
+  states = states.to(torch.complex64).contiguous()
+  num, dim = (int(v) for v in states.shape)
+  n = dim.bit_length() - 1
+  if dim != (1 << n) or n < 1:
+    raise ValueError(f"states have {dim} amplitudes: not a power of two, or fewer than two")
+  if table is not None:
+    if not (torch.is_tensor(table) and table.is_cuda and table.device == states.device):
+      raise EngineError("weighted_gram needs the table on the states' device")
+    if tuple(table.shape) != (dim,):
+      raise ValueError(f"table must have shape [{dim}], got {tuple(table.shape)}")
+    table = table.detach().to(torch.float32).contiguous()
+  with torch.cuda.device(states.device):
+    scratch = torch.empty(gram_scratch_bytes(num, n) // 8, dtype=torch.float64, device=states.device)
+    out = torch.empty((num, num, 2), dtype=torch.float64, device=states.device)
+    _check_global(load_library().qhbm_weighted_gram(states.data_ptr(), num, n, None if table is None else table.data_ptr(),
+                                                    scratch.data_ptr(), out.data_ptr(),
+                                                    torch.cuda.current_stream().cuda_stream))
+  return torch.view_as_complex(out)
 
 
 class Engine:

@@ -14,13 +14,14 @@ from qhbmlib_amd.inference.qmhl_loss import qmhl
 from qhbmlib_amd.inference.qnn import (AnalyticQuantumInference, QuantumInference,
                                        SampledQuantumInference)
 from qhbmlib_amd.inference.qnn_utils import unitary
+from qhbmlib_amd.inference.state_metrics import StateMetrics, state_metrics
 from qhbmlib_amd.inference.thermal import (ThermalEnsemble, imaginary_time_evolution, real_time_evolution,
                                            thermal_ensemble)
 from qhbmlib_amd.inference.vqt_loss import vqt
 
 __all__ = ["AnalyticEnergyInference", "AnalyticQuantumInference", "BernoulliEnergyInference", "CapturedLoss",
            "EnergyInference", "EnergyInferenceBase", "GibbsWithGradientsInference", "KrylovSpace", "QHBM", "QuantumInference",
-           "SampledQuantumInference", "ThermalEnsemble", "ThermalSweep", "density_matrix",
+           "SampledQuantumInference", "StateMetrics", "ThermalEnsemble", "ThermalSweep", "density_matrix",
            "fidelity", "ground_state", "imaginary_time_evolution", "information_matrix", "krylov_space", "natural_gradient",
-           "probabilities", "qmhl", "real_time_evolution", "spectrum_extremes", "thermal_ensemble", "thermal_sweep", "unitary",
+           "probabilities", "qmhl", "real_time_evolution", "spectrum_extremes", "state_metrics", "thermal_ensemble", "thermal_sweep", "unitary",
            "vqt"]
