@@ -401,6 +401,37 @@ int qhbm_gram_scratch_bytes(int M, int n_qubits, size_t* out);
 int qhbm_weighted_gram(const void* d_states, int M, int n_qubits, const float* d_table, void* d_scratch, double* d_gram,
                        void* stream);
 
+/* ---- Reduced density matrices: the partial trace of a state ensemble ----
+ * Added WITHIN ABI version 5: purely additive, QHBM_ABI_VERSION stays 5.
+ *
+ *   rho_A[a, a'] = sum_m w_m sum_b phi_m(a, b) conj(phi_m(a', b))
+ * for M states phi_m of 2^n_qubits amplitudes and a subset A of k kept qubits.  keep_mask is in QUBIT space (bit q set <=>
+ * qubit q is kept; qubit 0 is the most significant bit of an amplitude index); row index a is the kept qubits' bits read
+ * big-endian in ascending qubit order, b the same for the other qubits.
+ *
+ *   qhbm_reduced_density     d_states [M, 2^n_qubits] complex64, interleaved, 16-byte aligned; d_weights [M] float64, or
+ *                            NULL for all ones; d_rho [2^k, 2^k, 2] float64 (re, im), row-major; all on the device.  No
+ *                            engine: the current device.  Asynchronous on `stream`; allocates nothing, synchronises
+ *                            nothing.  d_scratch: qhbm_reduced_density_scratch_bytes bytes, 8-byte aligned, which may hold
+ *                            anything (every partial that is read is written first).  k = n_qubits is allowed: the
+ *                            environment is empty and rho = sum_m w_m |phi_m><phi_m|.
+ *                            Order of additions: a product is float x float in float64 (exact); the column operand
+ *                            phi_m(a', b) is multiplied by w_m first (one rounding per amplitude); a thread adds its
+ *                            environment values in ascending (m, b) order with fused multiply-adds, the threads that
+ *                            share an output meet in a fixed shuffle tree, then in wave order, and the slices add in
+ *                            slice order in a second kernel; no floating-point atomics.  The grid depends on
+ *                            (n_qubits, keep_mask, M) alone: two calls give the same bits.  Only a' >= a is summed:
+ *                            rho[a', a] is written as the conjugate of rho[a, a'] and Im rho[a, a] as 0.
+ *                            Refused, each with a message and before anything is launched: M outside [1, 65536];
+ *                            n_qubits outside [1, 31]; a keep_mask bit at or above n_qubits; k outside
+ *                            [1, min(n_qubits, 10)]; d_states, d_scratch or d_rho NULL; a misaligned pointer.
+ *   qhbm_reduced_density_scratch_bytes  *out = the bytes of d_scratch such a call needs (csrc/rdm_index.h rdm_plan: 16
+ *                            bytes per tile entry, upper-triangle tile and slice); needs no device.  Refused: the shape
+ *                            as above, out NULL. */
+int qhbm_reduced_density_scratch_bytes(int M, int n_qubits, uint64_t keep_mask, size_t* out);
+int qhbm_reduced_density(const void* d_states, int M, int n_qubits, uint64_t keep_mask, const double* d_weights,
+                         void* d_scratch, double* d_rho, void* stream);
+
 /* Computational-basis samples of the final states (tfq.layers.Sample as used at
  * qhbmlib/inference/qnn.py:169,177-181,286-291):
  *   d_out_samples [U, n_shots, n_qubits] int8 (device); shot j of state u is drawn from

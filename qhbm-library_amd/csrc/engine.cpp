@@ -18,6 +18,7 @@
 #include "kernels.h"
 #include "plan_args.h"
 #include "program.h"
+#include "rdm_index.h"
 #include "schedule.h"
 
 using namespace qhbm;
@@ -2357,6 +2358,37 @@ int qhbm_weighted_gram(const void* d_states, int M, int n_qubits, const float* d
   hipError_t e = launch_weighted_gram(static_cast<const float2*>(d_states), uint32_t(M), uint32_t(n_qubits), d_table,
                                       static_cast<double*>(d_scratch), d_gram, static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return fail(nullptr, std::string("qhbm_weighted_gram: ") + hipGetErrorString(e));
+  return 0;
+}
+
+// ---- the reduced density matrix of M states (include/qhbm_engine.h; reduced.hip, rdm_index.h) ----
+static int check_reduced_shape(int M, int n_qubits, uint64_t keep_mask) {
+  if (M < 1 || M > kRdmMaxStates) return fail(nullptr, "M must be in [1, 65536]");
+  switch (rdm_check(n_qubits, keep_mask)) {
+    case 0: return 0;
+    case 1: return fail(nullptr, "n_qubits must be in [1, 31]");
+    case 2: return fail(nullptr, "keep_mask has a bit at or above n_qubits");
+    default: return fail(nullptr, "keep_mask must keep between 1 and min(n_qubits, 10) qubits");
+  }
+}
+
+int qhbm_reduced_density_scratch_bytes(int M, int n_qubits, uint64_t keep_mask, size_t* out) {
+  if (!out) return fail(nullptr, "out is NULL");
+  if (int rc = check_reduced_shape(M, n_qubits, keep_mask)) return rc;
+  *out = rdm_plan(n_qubits, keep_mask, M).scratch_bytes;
+  return 0;
+}
+
+int qhbm_reduced_density(const void* d_states, int M, int n_qubits, uint64_t keep_mask, const double* d_weights,
+                         void* d_scratch, double* d_rho, void* stream) {
+  if (int rc = check_reduced_shape(M, n_qubits, keep_mask)) return rc;
+  if (!d_states || !d_scratch || !d_rho) return fail(nullptr, "d_states / d_scratch / d_rho is NULL");
+  if (reinterpret_cast<uintptr_t>(d_states) & 15u) return fail(nullptr, "d_states must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_weights) | reinterpret_cast<uintptr_t>(d_scratch) | reinterpret_cast<uintptr_t>(d_rho)) & 7u)
+    return fail(nullptr, "d_weights / d_scratch / d_rho must be 8-byte aligned");
+  hipError_t e = launch_reduced_density(static_cast<const float2*>(d_states), uint32_t(M), uint32_t(n_qubits), keep_mask,
+                                        d_weights, static_cast<double*>(d_scratch), d_rho, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, std::string("qhbm_reduced_density: ") + hipGetErrorString(e));
   return 0;
 }
 

@@ -315,4 +315,11 @@ size_t gram_parts_count(uint32_t n, uint32_t M);
 hipError_t launch_weighted_gram(const float2* states, uint32_t M, uint32_t n, const float* table, double* parts, double* gram,
                                 hipStream_t stream);
 
+// ---- the reduced density matrix of M states (reduced.hip; the plan is rdm_index.h's) ----
+// rho[a, a'] = sum_m weights[m] sum_b phi_m(a, b) conj(phi_m(a', b)) (weights NULL: 1), complex fp64 in a fixed order,
+// [2^k, 2^k, 2]; states [M, 2^n]; keep_mask in qubit space, k = popcount in [1, min(n, 10)], n in [1, 31], M in [1, 65536].
+// `parts`: rdm_plan(n, keep_mask, M).scratch_bytes bytes, which may hold anything.
+hipError_t launch_reduced_density(const float2* states, uint32_t M, uint32_t n, uint64_t keep_mask, const double* weights,
+                                  double* parts, double* rho, hipStream_t stream);
+
 }  // namespace qhbm

@@ -28,6 +28,7 @@
 #include "kernels.h"
 #include "program.h"
 #include "x_shear.h"
+#include "rdm_index.h"
 
 namespace qhbm {
 
@@ -3307,6 +3308,7 @@ hipError_t launch_parity_energy_vjp(const int8_t* bits, int64_t n_rows, int n, c
 #include "thermal.hip"
 #include "krylov.hip"
 #include "gram.hip"
+#include "reduced.hip"
 
 size_t observable_value_parts(uint32_t n, uint32_t n_states) { return size_t(n_states) * ((1u << n) / (256u * obs_amps_per_thread(n))); }
 

@@ -49,6 +49,7 @@ ABI_SYMBOLS = (
     "qhbm_apply_observables", "qhbm_evolve_states", "qhbm_describe_evolution", "qhbm_random_states",
     "qhbm_krylov_basis", "qhbm_krylov_combine", "qhbm_describe_krylov",
     "qhbm_gram_scratch_bytes", "qhbm_weighted_gram",
+    "qhbm_reduced_density_scratch_bytes", "qhbm_reduced_density",
 )
 
 
@@ -147,6 +148,8 @@ def load_library():
     lib.qhbm_describe_krylov.argtypes = [vp, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
     lib.qhbm_gram_scratch_bytes.argtypes = [i32, i32, ctypes.POINTER(ctypes.c_size_t)]
     lib.qhbm_weighted_gram.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    lib.qhbm_reduced_density_scratch_bytes.argtypes = [i32, i32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_size_t)]
+    lib.qhbm_reduced_density.argtypes = [vp, i32, i32, ctypes.c_uint64, vp, vp, vp, vp]
   except AttributeError:  # an older library given through QHBM_ENGINE_LIB (A/B runs): the probe is optional there
     pass
   _lib = lib
@@ -391,6 +394,48 @@ def weighted_gram(states, table=None):
     _check_global(load_library().qhbm_weighted_gram(states.data_ptr(), num, n, None if table is None else table.data_ptr(),
                                                     scratch.data_ptr(), out.data_ptr(),
                                                     torch.cuda.current_stream().cuda_stream))
+  return torch.view_as_complex(out)
+
+
+def reduced_density_scratch_bytes(num_states, n_qubits, keep_mask):
+  """Bytes of scratch one `qhbm_reduced_density` of `num_states` states of `n_qubits` qubits onto the qubits of
+  `keep_mask` (bit q set: qubit q is kept) needs (no device needed)."""
+  out = ctypes.c_size_t()
+  _check_global(load_library().qhbm_reduced_density_scratch_bytes(int(num_states), int(n_qubits), int(keep_mask),
+                                                                  ctypes.byref(out)))
+  return int(out.value)
+
+
+def reduced_density(states, keep_mask, weights=None):
+  """rho_A[a, a'] = sum_m weights[m] sum_b states[m, (a, b)] conj(states[m, (a', b)]) (weights None: 1) for M
+  device-resident states [M, 2^n] and the kept qubits of `keep_mask` (bit q set: qubit q, the q-th most significant bit of an
+  amplitude index, is kept; a reads them big-endian in ascending order): complex128 [2^k, 2^k], summed in float64 in a
+  fixed order, Hermitian bit for bit with an exactly real diagonal (include/qhbm_engine.h qhbm_reduced_density).
+  complex128 states are cast to complex64 and the weights to float64; the scratch is this call's own.  Not differentiable."""
+  if not (torch.is_tensor(states) and states.is_cuda and states.dim() == 2 and states.is_complex()):
+    raise EngineError("reduced_density needs complex CUDA states [M, 2^n]: the engine has no CPU fallback")
+  states = states.detach().to(torch.complex64).contiguous()
+  if states.data_ptr() % 16:  # (a view at an odd offset: the gather loads 16-byte words)
+    states = states.clone()
+  num, dim = (int(v) for v in states.shape)
+  n = dim.bit_length() - 1
+  if dim != (1 << n) or n < 1:
+    raise ValueError(f"states have {dim} amplitudes: not a power of two, or fewer than two")
+  keep_mask = int(keep_mask)
+  if keep_mask < 0 or keep_mask >= 1 << 64:
+    raise ValueError(f"keep_mask {keep_mask} is not a 64-bit mask")
+  if weights is not None:
+    weights = torch.as_tensor(weights).detach().to(device=states.device, dtype=torch.float64).contiguous()
+    if tuple(weights.shape) != (num,):
+      raise ValueError(f"weights must have shape [{num}], got {tuple(weights.shape)}")
+  with torch.cuda.device(states.device):
+    scratch = torch.empty(reduced_density_scratch_bytes(num, n, keep_mask) // 8, dtype=torch.float64, device=states.device)
+    dim_a = 1 << bin(keep_mask).count("1")
+    out = torch.empty((dim_a, dim_a, 2), dtype=torch.float64, device=states.device)
+    _check_global(load_library().qhbm_reduced_density(states.data_ptr(), num, n, keep_mask,
+                                                      None if weights is None else weights.data_ptr(),
+                                                      scratch.data_ptr(), out.data_ptr(),
+                                                      torch.cuda.current_stream().cuda_stream))
   return torch.view_as_complex(out)
 
 

@@ -134,6 +134,17 @@ class StateVectorData(QuantumData):
     """D(sigma || rho) = tr sigma (log sigma - log rho) against the QHBM `model`, as a float."""
     return self.metrics(model, **kwargs).relative_entropy
 
+  def reduced(self, qubits, rtol=1e-10):
+    """The quantum data of subsystem A = `qubits` (qubit objects of this data or integer positions in its sorted qubit
+    list): the eigen-ensemble of rho_A = tr_B sigma, summed on the GPU without moving the states
+    (`inference.reduced_density_matrix`), as `from_density_matrix(rho_A, rtol, qubits=kept)`.  Not
+    differentiable."""
+    from qhbmlib_amd.inference import reduced  # pylint: disable=import-outside-toplevel
+    positions = reduced._positions(qubits, self.qubits, self.num_qubits)  # pylint: disable=protected-access
+    kept = None if self.qubits is None else [self.qubits[p] for p in positions]
+    rho = reduced.reduced_density_matrix(self, positions)
+    return StateVectorData.from_density_matrix(rho.cpu(), rtol, qubits=kept)
+
   def entropy(self):
     """S(sigma) = -tr sigma log sigma of the data as given, as a float (no model needed)."""
     from qhbmlib_amd.inference.state_metrics import data_entropy  # pylint: disable=import-outside-toplevel
