@@ -1024,14 +1024,23 @@ PassArgs forward_pass_args(const qhbm_engine* h, size_t i, bool keep_state, bool
   return a;
 }
 
+// Do [a, a + a_bytes) and [b, b + b_bytes) meet?
+bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const char *p = static_cast<const char*>(a), *q = static_cast<const char*>(b);
+  return p < q + b_bytes && q < p + a_bytes;
+}
+
 // Does [p, p + bytes) meet the statevector workspace?
 bool aliases_workspace(const qhbm_engine* h, const void* p, size_t bytes) {
-  const char* a = static_cast<const char*>(p);
-  auto meets = [&](const DevBuf<float2>& b) {
-    const char* w = reinterpret_cast<const char*>(b.p);
-    return b.p && a < w + b.n * sizeof(float2) && w < a + bytes;
-  };
+  auto meets = [&](const DevBuf<float2>& b) { return b.p && ranges_overlap(p, bytes, b.p, b.n * sizeof(float2)); };
   return meets(h->psi) || meets(h->lam);
+}
+
+// A pointer argument that must be there and a multiple of `align` bytes (h NULL: an entry point without an engine).
+int check_pointer(qhbm_engine* h, const void* p, size_t align, const char* name) {
+  if (!p) return fail(h, std::string(name) + " is NULL");
+  if (reinterpret_cast<uintptr_t>(p) % align) return fail(h, std::string(name) + " must be " + std::to_string(align) + "-byte aligned");
+  return 0;
 }
 
 // From-states calls: states s0 .. s0 + c of the caller's batch, normalised, into the workspace (import_states.hip);
@@ -1040,7 +1049,7 @@ int import_chunk(qhbm_engine* h, uint32_t s0, uint32_t c, hipStream_t stream) {
   const uint32_t n = uint32_t(h->model.n), n_eff = uint32_t(h->fwd.plan.n_eff);
   if (aliases_workspace(h, h->import_src, size_t(h->import_U) * (size_t(8) << n)))
     return fail(h, "d_states lies inside the engine's workspace");
-  HIPCHK(h->import_parts.reserve(import_norm_parts_count(n, c)));
+  HIPCHK(h->import_parts.reserve(state_norm_parts_count(n, c)));
   hipEvent_t* ev = timer_begin(h, 0, stream);  // (profile_events: the import counts as a launch of the forward sweep)
   HIPCHK(launch_import_states(h->import_src, n, n_eff, c, s0, h->psi.p, h->import_parts.p, h->import_norm2.p, stream));
   timer_end(ev, stream);
@@ -1846,8 +1855,8 @@ int check_states_call(qhbm_engine* h, const void* d_states, int U, bool need_obs
   if (U < 0) return fail(h, "negative batch size");
   if (!h->have_circuit) return fail(h, "qhbm_set_circuit has not been called");
   if (need_observables && h->model.n_ops <= 0) return fail(h, "qhbm_set_observables has not been called");
-  if (U > 0 && !d_states) return fail(h, "d_states is NULL");
-  if (U > 0 && (reinterpret_cast<uintptr_t>(d_states) & 15u)) return fail(h, "d_states must be 16-byte aligned");
+  if (U > 0)
+    if (int rc = check_pointer(h, d_states, 16, "d_states")) return rc;
   if (U > 0 && aliases_workspace(h, d_states, size_t(U) * (size_t(8) << h->model.n)))
     return fail(h, "d_states lies inside the engine's workspace");
   return 0;
@@ -1916,8 +1925,8 @@ int qhbm_expectation_vjp_from_states(qhbm_engine* h, const void* d_states, int U
 int qhbm_statevector_from_states(qhbm_engine* h, const void* d_states, int U, const float* d_params, void* d_out_states,
                                  void* stream) {
   if (int rc = check_states_call(h, d_states, U, false)) return rc;
-  if (U > 0 && !d_out_states) return fail(h, "d_out_states is NULL");
-  if (reinterpret_cast<uintptr_t>(d_out_states) & 15u) return fail(h, "d_out_states must be 16-byte aligned");
+  if (U > 0 || d_out_states)
+    if (int rc = check_pointer(h, d_out_states, 16, "d_out_states")) return rc;
   DenseScope scope(h);
   if (int rc = upload_model(h)) return rc;
   if (U == 0) return 0;
@@ -1929,16 +1938,16 @@ int qhbm_statevector_from_states(qhbm_engine* h, const void* d_states, int U, co
   if (int rc = values_begin(h, U, s)) return rc;  // (by-product values of installed observables stay in the scratch)
   const uint32_t cs = chunk_states(h, U);
   if (int rc = ensure_state_buffers(h, cs, false)) return rc;
-  const size_t row = size_t(8) << h->model.n, pitch = size_t(8) << d.plan.n_eff;
+  const uint32_t n = uint32_t(h->model.n), n_eff = uint32_t(d.plan.n_eff);
   for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += cs) {
     const uint32_t c = std::min<uint32_t>(cs, uint32_t(U) - s0);
     // (a circuit without gates: the imported states are the result.  The plan's one pass would load and store them
     // unchanged; it is skipped -- and with it the by-product values of installed observables, which nobody can read --
     // so that the forward events of such a call time the import alone: scripts/from_states_time.py measures it this way)
     if (int rc = h->model.gates.empty() ? import_chunk(h, s0, c, s) : run_forward_chunk(h, h->import_bits.p, s0, c, true, s)) return rc;
-    char* out = static_cast<char*>(d_out_states) + size_t(s0) * row;
-    HIPCHK(hipMemcpy2DAsync(out, row, h->psi.p, pitch, row, c, hipMemcpyDeviceToDevice, s));
-    HIPCHK(launch_scale_state_rows(reinterpret_cast<float2*>(out), c, uint32_t(h->model.n), h->import_norm2.p + s0, s));
+    // idle padding qubits stay |0>: the first 2^n amplitudes of a row, times ||phi|| -- the state as given, evolved
+    HIPCHK(launch_scale_copy_states(h->psi.p, n_eff, static_cast<float2*>(d_out_states) + (size_t(s0) << n), n, n, c, nullptr,
+                                    h->import_norm2.p + s0, s));
   }
   HIPCHK(h->phase_cs.reserve(2));  // the global phase the kernels leave out, as qhbm_statevector restores it
   HIPCHK(launch_global_phase(d.jobs.p, int(d.plan.jobs.size()), h->shift_phases.p, h->n_shift_phases, d_params,
@@ -2046,8 +2055,7 @@ int check_evolve_states(qhbm_engine* h, const void* d_states, int U, const char*
   if (U <= 0) return fail(h, "U must be positive");
   if (!h->have_circuit) return fail(h, "qhbm_set_circuit has not been called");
   if (h->model.n_ops <= 0) return fail(h, "qhbm_set_observables has not been called");
-  if (!d_states) return fail(h, std::string(what) + " is NULL");
-  if (reinterpret_cast<uintptr_t>(d_states) & 15u) return fail(h, std::string(what) + " must be 16-byte aligned");
+  if (int rc = check_pointer(h, d_states, 16, what)) return rc;
   if (aliases_workspace(h, d_states, size_t(U) * (size_t(8) << h->model.n)))
     return fail(h, std::string(what) + " lies inside the engine's workspace");
   return 0;
@@ -2060,6 +2068,19 @@ int upload_evolve_weights(qhbm_engine* h, const double* weights, double factor, 
   for (size_t k = 0; k < n_ops; ++k) h->evo_host_wr[k] = (weights ? weights[k] : 1.0) * factor;
   HIPCHK(h->evo_wr.reserve(n_ops));
   HIPCHK(hipMemcpyAsync(h->evo_wr.p, h->evo_host_wr.data(), n_ops * sizeof(double), hipMemcpyHostToDevice, s));
+  return 0;
+}
+
+// out = H in for c states under the upstream rows in evo_up1; in, out: rows at the caller's pitch of 2^n amplitudes.
+// n = n_eff: that is the workspace's pitch, and the observable kernel reads and writes the caller's rows.  Otherwise the
+// rows are staged through psi and the result leaves lam for `out` -- unless `out` is lam itself, where it stays, at the
+// workspace's pitch (qhbm_krylov_basis orthogonalises it there).
+int apply_h_chunk(qhbm_engine* h, const float2* in, float2* out, uint32_t c, hipStream_t s) {
+  const uint32_t n = uint32_t(h->model.n), n_eff = uint32_t(h->fwd.plan.n_eff);
+  if (n == n_eff) return run_observable_chunk(h, 0, c, h->evo_up1.p, false, s, true, false, in, out);
+  HIPCHK(launch_scale_copy_states(in, n, h->psi.p, n_eff, n, c, nullptr, nullptr, s));
+  if (int rc = run_observable_chunk(h, 0, c, h->evo_up1.p, false, s)) return rc;
+  if (out != h->lam.p) HIPCHK(launch_scale_copy_states(h->lam.p, n_eff, out, n, n, c, nullptr, nullptr, s));
   return 0;
 }
 
@@ -2082,10 +2103,7 @@ int qhbm_apply_observables(qhbm_engine* h, const void* d_states, int U, const do
   if (int rc = check_evolve_states(h, d_states, U, "d_states")) return rc;
   if (int rc = check_evolve_states(h, d_out_states, U, "d_out_states")) return rc;
   const size_t row = size_t(8) << h->model.n;
-  {
-    const char *a = static_cast<const char*>(d_states), *b = static_cast<const char*>(d_out_states);
-    if (a < b + size_t(U) * row && b < a + size_t(U) * row) return fail(h, "d_out_states overlaps d_states");
-  }
+  if (ranges_overlap(d_states, size_t(U) * row, d_out_states, size_t(U) * row)) return fail(h, "d_out_states overlaps d_states");
   if (weights)
     for (int k = 0; k < h->model.n_ops; ++k)
       if (!std::isfinite(weights[k])) return fail(h, "a weight is not finite");
@@ -2105,13 +2123,7 @@ int qhbm_apply_observables(qhbm_engine* h, const void* d_states, int U, const do
     const float2* in = reinterpret_cast<const float2*>(static_cast<const char*>(d_states) + size_t(s0) * row);
     float2* out = reinterpret_cast<float2*>(static_cast<char*>(d_out_states) + size_t(s0) * row);
     HIPCHK(launch_evolve_init(c, nullptr, nullptr, nullptr, h->evo_wr.p, n_ops, h->evo_up1.p, nullptr, s));
-    if (n == n_eff) {  // the caller's pitch is the workspace's: the observable kernel reads and writes the caller's rows
-      if (int rc = run_observable_chunk(h, 0, c, h->evo_up1.p, false, s, true, false, in, out)) return rc;
-    } else {
-      HIPCHK(launch_scale_copy_states(in, n, h->psi.p, n_eff, n, c, nullptr, nullptr, s));
-      if (int rc = run_observable_chunk(h, 0, c, h->evo_up1.p, false, s)) return rc;
-      HIPCHK(launch_scale_copy_states(h->lam.p, n_eff, out, n, n, c, nullptr, nullptr, s));
-    }
+    if (int rc = apply_h_chunk(h, in, out, c, s)) return rc;
   }
   return 0;
 }
@@ -2142,9 +2154,9 @@ int qhbm_evolve_states(qhbm_engine* h, void* d_states, int U, const double* weig
   if (aliases_workspace(h, d_states, size_t(U) * row)) return fail(h, "d_states lies inside the engine's workspace");
   if (int rc = upload_evolve_weights(h, weights, ep.R > 0.0 ? 1.0 / ep.R : 0.0, s)) return rc;
   HIPCHK(h->import_norm2.reserve(size_t(U)));
-  HIPCHK(h->import_parts.reserve(import_norm_parts_count(n, cs)));
+  HIPCHK(h->import_parts.reserve(state_norm_parts_count(n, cs)));
   HIPCHK(h->evo_scale.reserve(cs));
-  HIPCHK(h->evo_parts.reserve(cheb_norm_parts_count(n_eff, cs)));
+  HIPCHK(h->evo_parts.reserve(state_norm_parts_count(n_eff, cs)));
   HIPCHK(h->evo_up1.reserve(size_t(cs) * n_ops));
   HIPCHK(h->evo_up2.reserve(size_t(cs) * n_ops));
   double* log_norm = d_log_norms;
@@ -2191,7 +2203,6 @@ int qhbm_evolve_states(qhbm_engine* h, void* d_states, int U, const double* weig
 namespace {
 
 constexpr int kKrylovMaxSteps = 1024;
-constexpr int kKrylovBlock = 8;  // basis rows per project / subtract sweep (krylov.hip kKryBlock)
 
 int check_krylov_shape(qhbm_engine* h, int U, int m, int reorth) {
   if (U <= 0) return fail(h, "U must be positive");
@@ -2236,18 +2247,13 @@ int qhbm_krylov_basis(qhbm_engine* h, const void* d_start_states, int U, const d
   if (int rc = need_device(h)) return rc;
   if (int rc = check_krylov_shape(h, U, m, reorth)) return rc;
   if (int rc = check_evolve_states(h, d_start_states, U, "d_start_states")) return rc;
-  if (!d_basis) return fail(h, "d_basis is NULL");
-  if (reinterpret_cast<uintptr_t>(d_basis) & 15u) return fail(h, "d_basis must be 16-byte aligned");
-  if (!d_alpha || !d_beta || !d_lengths) return fail(h, "d_alpha / d_beta / d_lengths is NULL");
-  if ((reinterpret_cast<uintptr_t>(d_alpha) | reinterpret_cast<uintptr_t>(d_beta)) & 7u)
-    return fail(h, "d_alpha / d_beta must be 8-byte aligned");
-  if (reinterpret_cast<uintptr_t>(d_lengths) & 3u) return fail(h, "d_lengths must be 4-byte aligned");
+  if (int rc = check_pointer(h, d_basis, 16, "d_basis")) return rc;
+  if (int rc = check_pointer(h, d_alpha, 8, "d_alpha")) return rc;
+  if (int rc = check_pointer(h, d_beta, 8, "d_beta")) return rc;
+  if (int rc = check_pointer(h, d_lengths, 4, "d_lengths")) return rc;
   const uint32_t n = uint32_t(h->model.n);
   const size_t row = size_t(8) << n, basis_bytes = size_t(m) * size_t(U) * row;
-  {
-    const char *a = static_cast<const char*>(d_start_states), *b = static_cast<const char*>(d_basis);
-    if (a < b + basis_bytes && b < a + size_t(U) * row) return fail(h, "d_basis overlaps d_start_states");
-  }
+  if (ranges_overlap(d_start_states, size_t(U) * row, d_basis, basis_bytes)) return fail(h, "d_basis overlaps d_start_states");
   double R = 0.0;
   if (int rc = weighted_radius(h, weights, &R)) return rc;
   DenseScope scope(h);
@@ -2262,11 +2268,11 @@ int qhbm_krylov_basis(qhbm_engine* h, const void* d_start_states, int U, const d
   if (aliases_workspace(h, d_basis, basis_bytes)) return fail(h, "d_basis lies inside the engine's workspace");
   if (int rc = upload_evolve_weights(h, weights, 1.0, s)) return rc;
   HIPCHK(h->import_norm2.reserve(size_t(U)));
-  HIPCHK(h->import_parts.reserve(import_norm_parts_count(n, cs)));
+  HIPCHK(h->import_parts.reserve(state_norm_parts_count(n, cs)));
   HIPCHK(h->evo_scale.reserve(cs));
   HIPCHK(h->evo_up1.reserve(size_t(cs) * n_ops));
   HIPCHK(h->kry_parts.reserve(krylov_coef_parts_count(n, cs)));
-  HIPCHK(h->kry_norm_parts.reserve(krylov_norm_parts_count(n, cs)));
+  HIPCHK(h->kry_norm_parts.reserve(state_norm_parts_count(n, cs)));
   HIPCHK(h->kry_coef.reserve(size_t(cs) * size_t(m)));
   HIPCHK(launch_zero_fill(d_alpha, size_t(U) * size_t(m) * sizeof(double), s));
   const double threshold = std::ldexp(R, -16);
@@ -2286,12 +2292,7 @@ int qhbm_krylov_basis(qhbm_engine* h, const void* d_start_states, int U, const d
     for (int j = 0; j < m; ++j) {
       const float2* vj = basis + size_t(j) * stride + size_t(s0) * amps;
       // w = H v_j: row j of the chunk is contiguous, so at n = n_eff the observable kernel reads the basis itself
-      if (n == n_eff) {
-        if (int rc = run_observable_chunk(h, 0, c, h->evo_up1.p, false, s, true, false, vj, W)) return rc;
-      } else {
-        HIPCHK(launch_scale_copy_states(vj, n, h->psi.p, n_eff, n, c, nullptr, nullptr, s));
-        if (int rc = run_observable_chunk(h, 0, c, h->evo_up1.p, false, s)) return rc;
-      }
+      if (int rc = apply_h_chunk(h, vj, W, c, s)) return rc;
       hipEvent_t* ev = timer_begin(h, 0, s);
       const int lo = reorth ? 0 : std::max(0, j - 1), rows = j - lo + 1;
       for (int round = 0; round < rounds; ++round) {
@@ -2326,10 +2327,9 @@ int qhbm_krylov_combine(const void* d_basis, int m, int U, int n_qubits, const v
   if (U <= 0) return fail(nullptr, "U must be positive");
   if (S < 1) return fail(nullptr, "S must be at least 1");
   if (n_qubits < 1 || n_qubits > 34) return fail(nullptr, "n_qubits must be in [1, 34]");
-  if (!d_basis || !d_coef || !d_out_states) return fail(nullptr, "d_basis / d_coef / d_out_states is NULL");
-  if ((reinterpret_cast<uintptr_t>(d_basis) | reinterpret_cast<uintptr_t>(d_out_states)) & 15u)
-    return fail(nullptr, "d_basis / d_out_states must be 16-byte aligned");
-  if (reinterpret_cast<uintptr_t>(d_coef) & 7u) return fail(nullptr, "d_coef must be 8-byte aligned");
+  if (int rc = check_pointer(nullptr, d_basis, 16, "d_basis")) return rc;
+  if (int rc = check_pointer(nullptr, d_coef, 8, "d_coef")) return rc;
+  if (int rc = check_pointer(nullptr, d_out_states, 16, "d_out_states")) return rc;
   hipError_t e = launch_krylov_combine(static_cast<const float2*>(d_basis), uint32_t(m), uint32_t(U), uint32_t(n_qubits),
                                        static_cast<const float2*>(d_coef), uint32_t(S), static_cast<float2*>(d_out_states),
                                        static_cast<hipStream_t>(stream));
@@ -2338,23 +2338,27 @@ int qhbm_krylov_combine(const void* d_basis, int m, int U, int n_qubits, const v
 }
 
 // ---- the weighted Gram matrix of M states (include/qhbm_engine.h; gram.hip) ----
+static int check_gram_shape(int M, int n_qubits) {
+  if (M < 1 || M > kGramMaxStates) return fail(nullptr, "M must be in [1, " + std::to_string(kGramMaxStates) + "]");
+  if (n_qubits < 1 || n_qubits > 31) return fail(nullptr, "n_qubits must be in [1, 31]");
+  return 0;
+}
+
 int qhbm_gram_scratch_bytes(int M, int n_qubits, size_t* out) {
   if (!out) return fail(nullptr, "out is NULL");
-  if (M < 1 || M > kKrylovMaxSteps) return fail(nullptr, "M must be in [1, 1024]");
-  if (n_qubits < 1 || n_qubits > 31) return fail(nullptr, "n_qubits must be in [1, 31]");
+  if (int rc = check_gram_shape(M, n_qubits)) return rc;
   *out = gram_parts_count(uint32_t(n_qubits), uint32_t(M)) * sizeof(double);
   return 0;
 }
 
 int qhbm_weighted_gram(const void* d_states, int M, int n_qubits, const float* d_table, void* d_scratch, double* d_gram,
                        void* stream) {
-  if (M < 1 || M > kKrylovMaxSteps) return fail(nullptr, "M must be in [1, 1024]");
-  if (n_qubits < 1 || n_qubits > 31) return fail(nullptr, "n_qubits must be in [1, 31]");
-  if (!d_states || !d_scratch || !d_gram) return fail(nullptr, "d_states / d_scratch / d_gram is NULL");
-  if (reinterpret_cast<uintptr_t>(d_states) & 15u) return fail(nullptr, "d_states must be 16-byte aligned");
-  if (reinterpret_cast<uintptr_t>(d_table) & 7u) return fail(nullptr, "d_table must be 8-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(d_scratch) | reinterpret_cast<uintptr_t>(d_gram)) & 7u)
-    return fail(nullptr, "d_scratch / d_gram must be 8-byte aligned");
+  if (int rc = check_gram_shape(M, n_qubits)) return rc;
+  if (int rc = check_pointer(nullptr, d_states, 16, "d_states")) return rc;
+  if (d_table)
+    if (int rc = check_pointer(nullptr, d_table, 8, "d_table")) return rc;
+  if (int rc = check_pointer(nullptr, d_scratch, 8, "d_scratch")) return rc;
+  if (int rc = check_pointer(nullptr, d_gram, 8, "d_gram")) return rc;
   hipError_t e = launch_weighted_gram(static_cast<const float2*>(d_states), uint32_t(M), uint32_t(n_qubits), d_table,
                                       static_cast<double*>(d_scratch), d_gram, static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return fail(nullptr, std::string("qhbm_weighted_gram: ") + hipGetErrorString(e));
@@ -2382,10 +2386,11 @@ int qhbm_reduced_density_scratch_bytes(int M, int n_qubits, uint64_t keep_mask, 
 int qhbm_reduced_density(const void* d_states, int M, int n_qubits, uint64_t keep_mask, const double* d_weights,
                          void* d_scratch, double* d_rho, void* stream) {
   if (int rc = check_reduced_shape(M, n_qubits, keep_mask)) return rc;
-  if (!d_states || !d_scratch || !d_rho) return fail(nullptr, "d_states / d_scratch / d_rho is NULL");
-  if (reinterpret_cast<uintptr_t>(d_states) & 15u) return fail(nullptr, "d_states must be 16-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(d_weights) | reinterpret_cast<uintptr_t>(d_scratch) | reinterpret_cast<uintptr_t>(d_rho)) & 7u)
-    return fail(nullptr, "d_weights / d_scratch / d_rho must be 8-byte aligned");
+  if (int rc = check_pointer(nullptr, d_states, 16, "d_states")) return rc;
+  if (d_weights)
+    if (int rc = check_pointer(nullptr, d_weights, 8, "d_weights")) return rc;
+  if (int rc = check_pointer(nullptr, d_scratch, 8, "d_scratch")) return rc;
+  if (int rc = check_pointer(nullptr, d_rho, 8, "d_rho")) return rc;
   hipError_t e = launch_reduced_density(static_cast<const float2*>(d_states), uint32_t(M), uint32_t(n_qubits), keep_mask,
                                         d_weights, static_cast<double*>(d_scratch), d_rho, static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return fail(nullptr, std::string("qhbm_reduced_density: ") + hipGetErrorString(e));
@@ -2396,8 +2401,7 @@ int qhbm_random_states(void* d_states, int U, int n_qubits, uint64_t seed, uint6
   if (U < 0) return fail(nullptr, "negative batch size");
   if (n_qubits < 1 || n_qubits > 34) return fail(nullptr, "n_qubits must be in [1, 34]");
   if (U == 0) return 0;
-  if (!d_states) return fail(nullptr, "d_states is NULL");
-  if (reinterpret_cast<uintptr_t>(d_states) & 15u) return fail(nullptr, "d_states must be 16-byte aligned");
+  if (int rc = check_pointer(nullptr, d_states, 16, "d_states")) return rc;
   if (first_state + uint64_t(U) > (uint64_t(1) << 32)) return fail(nullptr, "first_state + U exceeds 2^32");
   hipError_t e = launch_random_states(static_cast<float2*>(d_states), uint32_t(U), uint32_t(n_qubits), seed, uint32_t(first_state),
                                       static_cast<hipStream_t>(stream));

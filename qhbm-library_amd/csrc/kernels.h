@@ -1,4 +1,6 @@
-// kernels.h -- launch entry points of kernels.hip (host side).
+// kernels.h -- launch entry points of the kernel objects (host side): kernels.hip (the pass kernels, with gwg.hip and
+// parity_table.hip), observable.hip (with energy_table.hip) and states.hip (import_states.hip, thermal.hip, krylov.hip,
+// gram.hip, reduced.hip).  A .hip file reaches another one's kernels through these declarations only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -246,8 +248,9 @@ hipError_t launch_energy_table(int mode, const float2* psi, float2* lam, const f
                                double* gpart, double* carry, double* gsum, hipStream_t stream);
 
 // ---- caller-supplied start states (import_states.hip) ----
-// Doubles of scratch (`parts`) the import of a chunk of c states of n qubits needs.
-size_t import_norm_parts_count(uint32_t n, uint32_t c);
+// Doubles of scratch a squared norm of each of c states at a pitch of 2^n amplitudes needs (state_sweep.h: one partial
+// per slice): the `parts` of launch_import_states and launch_cheb_step, the `norm_parts` of launch_krylov_subtract.
+size_t state_norm_parts_count(uint32_t n, uint32_t c);
 // Input states s0 .. s0 + c of `src` ([., 2^n] complex64, read only, 16-byte aligned): norm2[s0 + i] = ||phi||^2 in fp64
 // (fixed order, no atomics), psi element i = phi / ||phi|| at a pitch of 2^n_eff amplitudes, zeros in the padding and
 // for a state of norm 0.  Reads the input twice.
@@ -256,12 +259,12 @@ hipError_t launch_import_states(const float2* src, uint32_t n, uint32_t n_eff, u
 // out[r, k] = in[r, k] * norm2[r] (in == out allowed)
 hipError_t launch_scale_by_norm2(const float* in, float* out, uint32_t rows, uint32_t width, const double* norm2,
                                  hipStream_t stream);
-// st[r, :] *= sqrt(norm2[r]) for `rows` (<= 65535) states of 2^n amplitudes
-hipError_t launch_scale_state_rows(float2* st, uint32_t rows, uint32_t n, const double* norm2, hipStream_t stream);
+// dst row r (2^n_dst amplitudes) = src row r (2^n_src amplitudes), its first 2^n_copy amplitudes times
+// scale[r] * sqrt(norm2[r]) (either may be NULL: 1; both NULL: a plain copy), zeros behind them.
+hipError_t launch_scale_copy_states(const float2* src, uint32_t n_src, float2* dst, uint32_t n_dst, uint32_t n_copy, uint32_t c,
+                                    const double* scale, const double* norm2, hipStream_t stream);
 
 // ---- Chebyshev evolution of caller-supplied states (thermal.hip) ----
-// Doubles of scratch (`parts`) the norm of a chunk of c states at a pitch of 2^n_eff amplitudes needs.
-size_t cheb_norm_parts_count(uint32_t n_eff, uint32_t c);
 // One term of the recurrence over the chunk's c states (w, tprev, acc: [c, 2^n_eff], distinct buffers):
 //   first:      tprev = t_0 = acc * scale[i], acc = c0 t_0 + coef w            (w = t_1)
 //   otherwise:  tprev = t_{k+1} = w - tprev,  acc += coef t_{k+1}
@@ -276,18 +279,14 @@ hipError_t launch_finish_step(const double* parts, uint32_t n_eff, uint32_t c, d
 // (with norm2), up1 and up2 may each be NULL.
 hipError_t launch_evolve_init(uint32_t c, const double* norm2, double* log_norm, double* scale, const double* wr, uint32_t n_ops,
                               float* up1, float* up2, hipStream_t stream);
-// dst row r (2^n_dst amplitudes) = src row r (2^n_src amplitudes), its first 2^n_copy amplitudes times
-// scale[r] * sqrt(norm2[r]) (either may be NULL: 1; both NULL: a plain copy), zeros behind them.
-hipError_t launch_scale_copy_states(const float2* src, uint32_t n_src, float2* dst, uint32_t n_dst, uint32_t n_copy, uint32_t c,
-                                    const double* scale, const double* norm2, hipStream_t stream);
 // Random-sign states (include/qhbm_engine.h qhbm_random_states): out [n_states, 2^n]
 hipError_t launch_random_states(float2* out, uint32_t n_states, uint32_t n, uint64_t seed, uint32_t first_state,
                                 hipStream_t stream);
 
 // ---- Lanczos bases of caller-supplied states and sums over a stored basis (krylov.hip) ----
-// Doubles of scratch one project sweep (`parts`) and one norm (`norm_parts`) of a chunk of c states of n qubits need.
+constexpr int kKrylovBlock = 8;  // basis rows of one project / subtract sweep, outputs of one combine sweep
+// Doubles of scratch one project sweep (`parts`) of a chunk of c states of n qubits needs.
 size_t krylov_coef_parts_count(uint32_t n, uint32_t c);
-size_t krylov_norm_parts_count(uint32_t n, uint32_t c);
 // scale[i] = 1, lengths[i] = m for i < c; a state with norm2[i] = 0: scale 0, length 0.
 hipError_t launch_krylov_init(uint32_t c, const double* norm2, int m, int32_t* lengths, double* scale, hipStream_t stream);
 // c_k = <v_k, w> for the nb <= 8 basis rows at `rows` (row k of the chunk's state i at rows + k row_stride_amps + i 2^n)
@@ -308,10 +307,11 @@ hipError_t launch_krylov_combine(const float2* basis, uint32_t m, uint32_t U, ui
                                  float2* out, hipStream_t stream);
 
 // ---- the weighted Gram matrix of M states (gram.hip) ----
+constexpr int kGramMaxStates = 1024;
 // Doubles of scratch (`parts`) one Gram matrix of M states of n qubits needs.
 size_t gram_parts_count(uint32_t n, uint32_t M);
 // gram[i, j] = sum_x table[x] conj(states[i, x]) states[j, x] (table NULL: 1), complex fp64 in a fixed order, [M, M, 2];
-// states [M, 2^n]; M in [1, 1024], n in [1, 31].  Every partial that is read is written first: `parts` may hold anything.
+// states [M, 2^n]; M in [1, kGramMaxStates], n in [1, 31].  Every partial that is read is written first: `parts` may hold anything.
 hipError_t launch_weighted_gram(const float2* states, uint32_t M, uint32_t n, const float* table, double* parts, double* gram,
                                 hipStream_t stream);
 

@@ -28,7 +28,6 @@
 #include "kernels.h"
 #include "program.h"
 #include "x_shear.h"
-#include "rdm_index.h"
 
 namespace qhbm {
 
@@ -2968,20 +2967,6 @@ __global__ __launch_bounds__(256) void block_scan_kernel(double* __restrict__ bl
   }
 }
 
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = uint64_t(0xD2511F53u) * c[0], p1 = uint64_t(0xCD9E8D57u) * c[2];
-    const uint32_t n0 = uint32_t(p1 >> 32) ^ c[1] ^ k0, n2 = uint32_t(p0 >> 32) ^ c[3] ^ k1;
-    c[1] = uint32_t(p1);
-    c[3] = uint32_t(p0);
-    c[0] = n0;
-    c[2] = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-
 __global__ __launch_bounds__(64) void draw_kernel(const float2* __restrict__ psi, uint32_t n, int n_user,
                                                   const double* __restrict__ block_cum, uint32_t n_shots,
                                                   uint32_t shot0, uint64_t seed, uint32_t state0,
@@ -3305,10 +3290,6 @@ hipError_t launch_parity_energy_vjp(const int8_t* bits, int64_t n_rows, int n, c
 
 #include "gwg.hip"
 #include "parity_table.hip"
-#include "thermal.hip"
-#include "krylov.hip"
-#include "gram.hip"
-#include "reduced.hip"
 
 size_t observable_value_parts(uint32_t n, uint32_t n_states) { return size_t(n_states) * ((1u << n) / (256u * obs_amps_per_thread(n))); }
 

@@ -17,39 +17,36 @@
 //   krylov_init_kernel           scale = 1, length = m (norm 0: scale 0, length 0) from the import's squared norms
 //   krylov_combine_kernel<SB>    out[u, s0 + s] = sum_j coef[u, s0 + s, j] basis[j, u], j ascending, fp32, s < SB <= 8:
 //                                every basis word is read once for SB outputs held in registers        m reads, SB writes
-// v_{j+1} = w * scale is thermal.hip's scale_copy_kernel (1 read, 1 write), which also takes w from the workspace's pitch
-// to the caller's.
+// v_{j+1} = w * scale is import_states.hip's launch_scale_copy_states (1 read, 1 write), which also takes w from the
+// workspace's pitch to the caller's.
 //
-// Shape (thermal.hip's): 16-byte words, blockIdx.y = the state, blockIdx.x = a slice of 1024 words, 256 threads x 4 words,
+// Shape (state_sweep.h): 16-byte words, blockIdx.y = the state, blockIdx.x = a slice of 1024 words, 256 threads x 4 words,
 // the grid a function of n alone.  A thread adds its words in word order, a wave's 64 lanes meet in a fixed shuffle tree,
-// the four waves in wave order, the slices in slice order through th_block_sum: no floating-point atomics, and nothing
+// the four waves in wave order, the slices in slice order through sweep_row_sum(2): no floating-point atomics, and nothing
 // depends on chunk_states or on which other states share the call.
 //
-// (included by kernels.hip inside namespace qhbm, after thermal.hip whose helpers it uses)
+// (a translation unit of its own in the source tree, compiled as part of states.hip; it uses no name of another .hip file)
+#include <algorithm>
 
+#include "kernels.h"
+#include "state_sweep.h"
+
+namespace qhbm {
 namespace {
-
-constexpr uint32_t kKryBlock = 8;  // basis rows of one project / subtract sweep, outputs of one combine sweep
-
-__device__ __forceinline__ double kry_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;  // (lane 0 holds the sum)
-}
 
 // w: the chunk's states at a pitch of w_pitch words; rows: basis row i0 of the chunk's first state, `row_stride` words
 // from one basis row to the next, `words` words per state; part [c, 8, 2, gridDim.x]
 template <uint32_t NB>
-__global__ __launch_bounds__(kThThreads) void krylov_project_kernel(const float4* __restrict__ w, uint64_t w_pitch,
-                                                                    const float4* __restrict__ rows, uint64_t row_stride,
-                                                                    uint64_t words, double* __restrict__ part) {
-  __shared__ double sh[kThThreads / 64][2 * NB];
+__global__ __launch_bounds__(kSweepThreads) void krylov_project_kernel(const float4* __restrict__ w, uint64_t w_pitch,
+                                                                       const float4* __restrict__ rows, uint64_t row_stride,
+                                                                       uint64_t words, double* __restrict__ part) {
+  __shared__ double sh[kSweepThreads / 64][2 * NB];
   const float4* wr = w + uint64_t(blockIdx.y) * w_pitch;
   const float4* vr = rows + uint64_t(blockIdx.y) * words;
   double re[NB], im[NB];
 #pragma unroll
   for (uint32_t k = 0; k < NB; ++k) re[k] = im[k] = 0.0;
-  for (uint64_t i = uint64_t(blockIdx.x) * kThThreads + threadIdx.x; i < words; i += uint64_t(gridDim.x) * kThThreads) {
+  for (uint64_t i = uint64_t(blockIdx.x) * kSweepThreads + threadIdx.x; i < words; i += uint64_t(gridDim.x) * kSweepThreads) {
     const float4 a = wr[i];
 #pragma unroll
     for (uint32_t k = 0; k < NB; ++k) {
@@ -61,7 +58,7 @@ __global__ __launch_bounds__(kThThreads) void krylov_project_kernel(const float4
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
 #pragma unroll
   for (uint32_t k = 0; k < NB; ++k) {
-    const double r = kry_wave_sum(re[k]), s = kry_wave_sum(im[k]);
+    const double r = sweep_wave_sum(re[k]), s = sweep_wave_sum(im[k]);
     if (lane == 0) {
       sh[wave][2 * k] = r;
       sh[wave][2 * k + 1] = s;
@@ -70,74 +67,63 @@ __global__ __launch_bounds__(kThThreads) void krylov_project_kernel(const float4
   __syncthreads();
   if (threadIdx.x < 2 * NB) {
     double total = sh[0][threadIdx.x];
-    for (uint32_t v = 1; v < kThThreads / 64; ++v) total += sh[v][threadIdx.x];
-    part[(uint64_t(blockIdx.y) * 2 * kKryBlock + threadIdx.x) * gridDim.x + blockIdx.x] = total;
+    for (uint32_t v = 1; v < kSweepThreads / 64; ++v) total += sh[v][threadIdx.x];
+    part[(uint64_t(blockIdx.y) * 2 * kKrylovBlock + threadIdx.x) * gridDim.x + blockIdx.x] = total;
   }
 }
 
 // One workgroup per state of the chunk.  coef [c, coef_pitch]: the round's coefficients, row i at i - lo; the block's
 // rows are first .. first + nb.  alpha_at >= 0: the block's row alpha_at is row j -- alpha[state] += Re c_j.
-__global__ __launch_bounds__(kThThreads) void krylov_coef_kernel(const double* __restrict__ part, uint32_t slices, uint32_t nb,
-                                                                 float2* __restrict__ coef, uint32_t coef_pitch, uint32_t first,
-                                                                 int alpha_at, double* __restrict__ alpha, uint64_t alpha_pitch) {
-  __shared__ double sh[kThThreads];
+__global__ __launch_bounds__(kSweepThreads) void krylov_coef_kernel(const double* __restrict__ part, uint32_t slices, uint32_t nb,
+                                                                    float2* __restrict__ coef, uint32_t coef_pitch, uint32_t first,
+                                                                    int alpha_at, double* __restrict__ alpha, uint64_t alpha_pitch) {
+  __shared__ double sh[kSweepThreads];
   for (uint32_t k = 0; k < nb; ++k) {
-    const double* row = part + (uint64_t(blockIdx.x) * 2 * kKryBlock + 2 * k) * slices;
-    double re = 0.0, im = 0.0;
-    for (uint32_t i = threadIdx.x; i < slices; i += kThThreads) {
-      re += row[i];
-      im += row[slices + i];
-    }
-    re = th_block_sum(re, sh);
-    __syncthreads();
-    im = th_block_sum(im, sh);
+    const double2 c = sweep_row_sum2(part + (uint64_t(blockIdx.x) * 2 * kKrylovBlock + 2 * k) * slices, slices, sh);
     __syncthreads();
     if (threadIdx.x == 0) {
-      coef[uint64_t(blockIdx.x) * coef_pitch + first + k] = make_float2(float(re), float(im));
-      if (int(k) == alpha_at) alpha[uint64_t(blockIdx.x) * alpha_pitch] += re;
+      coef[uint64_t(blockIdx.x) * coef_pitch + first + k] = make_float2(float(c.x), float(c.y));
+      if (int(k) == alpha_at) alpha[uint64_t(blockIdx.x) * alpha_pitch] += c.x;
     }
   }
 }
 
 // coef: the state's coefficients of the block's rows (coef_pitch float2 per state); norm_part [c, gridDim.x]
 template <uint32_t NB, bool NORM>
-__global__ __launch_bounds__(kThThreads) void krylov_subtract_kernel(float4* __restrict__ w, uint64_t w_pitch,
-                                                                     const float4* __restrict__ rows, uint64_t row_stride,
-                                                                     uint64_t words, const float2* __restrict__ coef,
-                                                                     uint32_t coef_pitch, double* __restrict__ norm_part) {
-  __shared__ double sh[NORM ? kThThreads : 1];
+__global__ __launch_bounds__(kSweepThreads) void krylov_subtract_kernel(float4* __restrict__ w, uint64_t w_pitch,
+                                                                        const float4* __restrict__ rows, uint64_t row_stride,
+                                                                        uint64_t words, const float2* __restrict__ coef,
+                                                                        uint32_t coef_pitch, double* __restrict__ norm_part) {
+  __shared__ double sh[NORM ? kSweepThreads : 1];
   float4* wr = w + uint64_t(blockIdx.y) * w_pitch;
   const float4* vr = rows + uint64_t(blockIdx.y) * words;
   float2 c[NB];
 #pragma unroll
   for (uint32_t k = 0; k < NB; ++k) c[k] = coef[uint64_t(blockIdx.y) * coef_pitch + k];
   double sum = 0.0;
-  for (uint64_t i = uint64_t(blockIdx.x) * kThThreads + threadIdx.x; i < words; i += uint64_t(gridDim.x) * kThThreads) {
+  for (uint64_t i = uint64_t(blockIdx.x) * kSweepThreads + threadIdx.x; i < words; i += uint64_t(gridDim.x) * kSweepThreads) {
     float4 a = wr[i];
 #pragma unroll
     for (uint32_t k = 0; k < NB; ++k) {
-      const float4 d = th_cmul(c[k], vr[uint64_t(k) * row_stride + i]);
+      const float4 d = sweep_cmul(c[k], vr[uint64_t(k) * row_stride + i]);
       a = make_float4(a.x - d.x, a.y - d.y, a.z - d.z, a.w - d.w);
     }
     wr[i] = a;
-    if (NORM) sum += (double(a.x) * double(a.x) + double(a.y) * double(a.y)) + (double(a.z) * double(a.z) + double(a.w) * double(a.w));
+    if (NORM) sum += word_norm2(a);
   }
   if (NORM) {
-    const double total = th_block_sum(sum, sh);
+    const double total = sweep_block_sum(sum, sh);
     if (threadIdx.x == 0) norm_part[uint64_t(blockIdx.y) * gridDim.x + blockIdx.x] = total;
   }
 }
 
 // One workgroup per state of the chunk; beta, lengths: the chunk's first state, beta at step j of a row of beta_pitch.
-__global__ __launch_bounds__(kThThreads) void krylov_norm_kernel(const double* __restrict__ norm_part, uint32_t slices,
-                                                                 double threshold, int j, double* __restrict__ beta,
-                                                                 uint64_t beta_pitch, int32_t* __restrict__ lengths,
-                                                                 double* __restrict__ scale) {
-  __shared__ double sh[kThThreads];
-  const double* row = norm_part + uint64_t(blockIdx.x) * slices;
-  double acc = 0.0;
-  for (uint32_t i = threadIdx.x; i < slices; i += kThThreads) acc += row[i];
-  const double norm = sqrt(th_block_sum(acc, sh));
+__global__ __launch_bounds__(kSweepThreads) void krylov_norm_kernel(const double* __restrict__ norm_part, uint32_t slices,
+                                                                    double threshold, int j, double* __restrict__ beta,
+                                                                    uint64_t beta_pitch, int32_t* __restrict__ lengths,
+                                                                    double* __restrict__ scale) {
+  __shared__ double sh[kSweepThreads];
+  const double norm = sqrt(sweep_row_sum(norm_part + uint64_t(blockIdx.x) * slices, slices, sh));
   if (threadIdx.x == 0) {
     double b = 0.0, sc = 0.0;
     if (scale[blockIdx.x] != 0.0) {  // (0: exhausted at an earlier step, or a start state of norm 0)
@@ -153,9 +139,9 @@ __global__ __launch_bounds__(kThThreads) void krylov_norm_kernel(const double* _
   }
 }
 
-__global__ __launch_bounds__(kThThreads) void krylov_init_kernel(uint32_t c, const double* __restrict__ norm2, int m,
-                                                                 int32_t* __restrict__ lengths, double* __restrict__ scale) {
-  const uint32_t i = blockIdx.x * kThThreads + threadIdx.x;
+__global__ __launch_bounds__(kSweepThreads) void krylov_init_kernel(uint32_t c, const double* __restrict__ norm2, int m,
+                                                                    int32_t* __restrict__ lengths, double* __restrict__ scale) {
+  const uint32_t i = blockIdx.x * kSweepThreads + threadIdx.x;
   if (i < c) {
     const bool live = norm2[i] > 0.0;
     scale[i] = live ? 1.0 : 0.0;
@@ -166,14 +152,14 @@ __global__ __launch_bounds__(kThThreads) void krylov_init_kernel(uint32_t c, con
 // basis: row 0 of state u0 (blockIdx.y = u - u0), row_stride words between rows; coef: [., S, m] at state u0, output s0;
 // out: [., S, words] at state u0, output s0
 template <uint32_t SB>
-__global__ __launch_bounds__(kThThreads) void krylov_combine_kernel(const float4* __restrict__ basis, uint64_t row_stride,
-                                                                    uint64_t words, uint32_t m, const float2* __restrict__ coef,
-                                                                    uint32_t S, float4* __restrict__ out) {
+__global__ __launch_bounds__(kSweepThreads) void krylov_combine_kernel(const float4* __restrict__ basis, uint64_t row_stride,
+                                                                       uint64_t words, uint32_t m, const float2* __restrict__ coef,
+                                                                       uint32_t S, float4* __restrict__ out) {
   const float4* vr = basis + uint64_t(blockIdx.y) * words;
   const float2* cf = coef + uint64_t(blockIdx.y) * S * m;
   float4* o = out + uint64_t(blockIdx.y) * S * words;
 #pragma unroll 1
-  for (uint64_t i = uint64_t(blockIdx.x) * kThThreads + threadIdx.x; i < words; i += uint64_t(gridDim.x) * kThThreads) {
+  for (uint64_t i = uint64_t(blockIdx.x) * kSweepThreads + threadIdx.x; i < words; i += uint64_t(gridDim.x) * kSweepThreads) {
     float4 acc[SB];
 #pragma unroll
     for (uint32_t s = 0; s < SB; ++s) acc[s] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -182,7 +168,7 @@ __global__ __launch_bounds__(kThThreads) void krylov_combine_kernel(const float4
       const float4 v = vr[uint64_t(j) * row_stride + i];
 #pragma unroll
       for (uint32_t s = 0; s < SB; ++s) {
-        const float4 d = th_cmul(cf[uint64_t(s) * m + j], v);
+        const float4 d = sweep_cmul(cf[uint64_t(s) * m + j], v);
         acc[s] = make_float4(acc[s].x + d.x, acc[s].y + d.y, acc[s].z + d.z, acc[s].w + d.w);
       }
     }
@@ -194,24 +180,24 @@ __global__ __launch_bounds__(kThThreads) void krylov_combine_kernel(const float4
 template <uint32_t NB>
 void kry_launch_project(dim3 grid, hipStream_t stream, const float4* w, uint64_t w_pitch, const float4* rows, uint64_t row_stride,
                         uint64_t words, double* part) {
-  hipLaunchKernelGGL((krylov_project_kernel<NB>), grid, dim3(kThThreads), 0, stream, w, w_pitch, rows, row_stride, words, part);
+  hipLaunchKernelGGL((krylov_project_kernel<NB>), grid, dim3(kSweepThreads), 0, stream, w, w_pitch, rows, row_stride, words, part);
 }
 
 template <uint32_t NB>
 void kry_launch_subtract(bool norm, dim3 grid, hipStream_t stream, float4* w, uint64_t w_pitch, const float4* rows,
                          uint64_t row_stride, uint64_t words, const float2* coef, uint32_t coef_pitch, double* norm_part) {
   if (norm)
-    hipLaunchKernelGGL((krylov_subtract_kernel<NB, true>), grid, dim3(kThThreads), 0, stream, w, w_pitch, rows, row_stride, words,
+    hipLaunchKernelGGL((krylov_subtract_kernel<NB, true>), grid, dim3(kSweepThreads), 0, stream, w, w_pitch, rows, row_stride, words,
                        coef, coef_pitch, norm_part);
   else
-    hipLaunchKernelGGL((krylov_subtract_kernel<NB, false>), grid, dim3(kThThreads), 0, stream, w, w_pitch, rows, row_stride, words,
+    hipLaunchKernelGGL((krylov_subtract_kernel<NB, false>), grid, dim3(kSweepThreads), 0, stream, w, w_pitch, rows, row_stride, words,
                        coef, coef_pitch, norm_part);
 }
 
 template <uint32_t SB>
 void kry_launch_combine(dim3 grid, hipStream_t stream, const float4* basis, uint64_t row_stride, uint64_t words, uint32_t m,
                         const float2* coef, uint32_t S, float4* out) {
-  hipLaunchKernelGGL((krylov_combine_kernel<SB>), grid, dim3(kThThreads), 0, stream, basis, row_stride, words, m, coef, S, out);
+  hipLaunchKernelGGL((krylov_combine_kernel<SB>), grid, dim3(kSweepThreads), 0, stream, basis, row_stride, words, m, coef, S, out);
 }
 
 #define KRY_DISPATCH(count, call) \
@@ -229,12 +215,11 @@ void kry_launch_combine(dim3 grid, hipStream_t stream, const float4* basis, uint
 
 }  // namespace
 
-size_t krylov_coef_parts_count(uint32_t n, uint32_t c) { return size_t(c) * 2 * kKryBlock * th_slices(uint64_t(1) << (n - 1)); }
-size_t krylov_norm_parts_count(uint32_t n, uint32_t c) { return size_t(c) * th_slices(uint64_t(1) << (n - 1)); }
+size_t krylov_coef_parts_count(uint32_t n, uint32_t c) { return size_t(c) * 2 * kKrylovBlock * sweep_slices(uint64_t(1) << (n - 1)); }
 
 hipError_t launch_krylov_init(uint32_t c, const double* norm2, int m, int32_t* lengths, double* scale, hipStream_t stream) {
   if (!c) return hipSuccess;
-  hipLaunchKernelGGL(krylov_init_kernel, dim3((c + kThThreads - 1) / kThThreads), dim3(kThThreads), 0, stream, c, norm2, m, lengths,
+  hipLaunchKernelGGL(krylov_init_kernel, dim3((c + kSweepThreads - 1) / kSweepThreads), dim3(kSweepThreads), 0, stream, c, norm2, m, lengths,
                      scale);
   return hipGetLastError();
 }
@@ -242,24 +227,24 @@ hipError_t launch_krylov_init(uint32_t c, const double* norm2, int m, int32_t* l
 hipError_t launch_krylov_project(const float2* w, uint32_t n_w, const float2* rows, uint64_t row_stride_amps, uint32_t n, uint32_t c,
                                  uint32_t nb, double* parts, float2* coef, uint32_t coef_pitch, uint32_t first, int alpha_at,
                                  double* alpha, uint64_t alpha_pitch, hipStream_t stream) {
-  if (n < 1 || n_w < n || c == 0 || c > 65535u || nb < 1 || nb > kKryBlock || first + nb > coef_pitch) return hipErrorInvalidValue;
+  if (n < 1 || n_w < n || c == 0 || c > 65535u || nb < 1 || nb > kKrylovBlock || first + nb > coef_pitch) return hipErrorInvalidValue;
   const uint64_t words = uint64_t(1) << (n - 1), w_pitch = uint64_t(1) << (n_w - 1);
-  const uint32_t slices = th_slices(words);
+  const uint32_t slices = sweep_slices(words);
   const dim3 grid(slices, c);
   const float4 *w4 = reinterpret_cast<const float4*>(w), *r4 = reinterpret_cast<const float4*>(rows);
 #define KRY_CALL(NB) kry_launch_project<NB>(grid, stream, w4, w_pitch, r4, row_stride_amps / 2, words, parts)
   KRY_DISPATCH(nb, KRY_CALL)
 #undef KRY_CALL
-  hipLaunchKernelGGL(krylov_coef_kernel, dim3(c), dim3(kThThreads), 0, stream, parts, slices, nb, coef, coef_pitch, first, alpha_at,
+  hipLaunchKernelGGL(krylov_coef_kernel, dim3(c), dim3(kSweepThreads), 0, stream, parts, slices, nb, coef, coef_pitch, first, alpha_at,
                      alpha, alpha_pitch);
   return hipGetLastError();
 }
 
 hipError_t launch_krylov_subtract(float2* w, uint32_t n_w, const float2* rows, uint64_t row_stride_amps, uint32_t n, uint32_t c,
                                   uint32_t nb, const float2* coef, uint32_t coef_pitch, double* norm_parts, hipStream_t stream) {
-  if (n < 1 || n_w < n || c == 0 || c > 65535u || nb < 1 || nb > kKryBlock) return hipErrorInvalidValue;
+  if (n < 1 || n_w < n || c == 0 || c > 65535u || nb < 1 || nb > kKrylovBlock) return hipErrorInvalidValue;
   const uint64_t words = uint64_t(1) << (n - 1), w_pitch = uint64_t(1) << (n_w - 1);
-  const dim3 grid(th_slices(words), c);
+  const dim3 grid(sweep_slices(words), c);
   float4* w4 = reinterpret_cast<float4*>(w);
   const float4* r4 = reinterpret_cast<const float4*>(rows);
 #define KRY_CALL(NB) kry_launch_subtract<NB>(norm_parts != nullptr, grid, stream, w4, w_pitch, r4, row_stride_amps / 2, words, coef, coef_pitch, norm_parts)
@@ -271,7 +256,7 @@ hipError_t launch_krylov_subtract(float2* w, uint32_t n_w, const float2* rows, u
 hipError_t launch_krylov_norm(const double* norm_parts, uint32_t n, uint32_t c, double threshold, int j, double* beta,
                               uint64_t beta_pitch, int32_t* lengths, double* scale, hipStream_t stream) {
   if (n < 1 || c == 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(krylov_norm_kernel, dim3(c), dim3(kThThreads), 0, stream, norm_parts, th_slices(uint64_t(1) << (n - 1)),
+  hipLaunchKernelGGL(krylov_norm_kernel, dim3(c), dim3(kSweepThreads), 0, stream, norm_parts, sweep_slices(uint64_t(1) << (n - 1)),
                      threshold, j, beta, beta_pitch, lengths, scale);
   return hipGetLastError();
 }
@@ -283,9 +268,9 @@ hipError_t launch_krylov_combine(const float2* basis, uint32_t m, uint32_t U, ui
   const float4* b4 = reinterpret_cast<const float4*>(basis);
   float4* o4 = reinterpret_cast<float4*>(out);
   for (uint32_t u0 = 0; u0 < U; u0 += 65535u) {  // (the state is a grid dimension)
-    const dim3 grid(th_slices(words), std::min<uint32_t>(65535u, U - u0));
-    for (uint32_t s0 = 0; s0 < S; s0 += kKryBlock) {
-      const uint32_t sb = std::min<uint32_t>(kKryBlock, S - s0);
+    const dim3 grid(sweep_slices(words), std::min<uint32_t>(65535u, U - u0));
+    for (uint32_t s0 = 0; s0 < S; s0 += kKrylovBlock) {
+      const uint32_t sb = std::min<uint32_t>(kKrylovBlock, S - s0);
 #define KRY_CALL(SB) kry_launch_combine<SB>(grid, stream, b4 + uint64_t(u0) * words, uint64_t(U) * words, words, m, \
                                             coef + (uint64_t(u0) * S + s0) * m, S, o4 + (uint64_t(u0) * S + s0) * words)
       KRY_DISPATCH(sb, KRY_CALL)
@@ -296,3 +281,5 @@ hipError_t launch_krylov_combine(const float2* basis, uint32_t m, uint32_t U, ui
 }
 
 #undef KRY_DISPATCH
+
+}  // namespace qhbm

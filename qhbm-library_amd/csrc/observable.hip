@@ -689,8 +689,5 @@ hipError_t launch_observable_blocks(int mode, int block_bits, const float2* psi,
 }  // namespace qhbm
 
 // The energy-table kernels (a diagonal observable given as a table of 2^n energies) are a translation unit of their own
-// in the source tree and part of this object: the engine links against exactly kernels.o and observable.o, also in the
-// planning-only host build of tests/sanitize.
+// in the source tree and part of this object.
 #include "energy_table.hip"
-// ... and so is the import of caller-supplied start states.
-#include "import_states.hip"

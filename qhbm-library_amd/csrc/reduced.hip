@@ -18,8 +18,12 @@
 // slice order: no floating-point atomics, and the grid is a function of (n, keep_mask, M) alone.  Products are
 // float x float in double (exact); the column operand times w_m in double is the one rounding that is not an addition's.
 //
-// (included by kernels.hip inside namespace qhbm, after gram.hip)
+// (a translation unit of its own in the source tree, compiled as part of states.hip; it uses no name of another .hip file.
+// Its shape is its own -- panels in LDS, not state_sweep.h's streamed slices)
+#include "kernels.h"
+#include "rdm_index.h"
 
+namespace qhbm {
 namespace {
 
 struct RdmArgs {
@@ -246,3 +250,5 @@ hipError_t launch_reduced_density(const float2* states, uint32_t M, uint32_t n, 
                      stream, parts, p.kt, p.k, p.tile_rows, p.slices, rho);
   return hipGetLastError();
 }
+
+}  // namespace qhbm

@@ -11,97 +11,82 @@
 //   finish_step_kernel   norm = sqrt(sum of the state's partials, in index order); log_norm += log(norm) + x;
 //                        scale = 1 / norm (0 for norm 0: zeros and -inf); the state's upstream row (w_k / R) * scale
 //   evolve_init_kernel   scale = 1, log_norm = log ||phi|| from the import's squared norms, the upstream rows
-//   scale_copy_kernel    rows between the caller's pitch (2^n) and the workspace's (2^n_eff), times a per-state factor
 //   random_states_kernel random-sign states from Philox4x32-10, reproducible bit for bit (tests/thermal_ref.py)
+// The rows go back to the caller's pitch (2^n), times 1 / norm or ||phi||, through import_states.hip's
+// launch_scale_copy_states.
 //
-// Shape: streaming kernels, 16-byte words (two amplitudes), blockIdx.y = the state, blockIdx.x strides over the state's
-// words with gridDim.x = words / 1024 workgroups of 256 threads (four words per thread, consecutive threads on
-// consecutive words).  The grid depends on n alone, every state is summed by itself, the partials meet in a fixed LDS
-// tree and are added in index order: no floating-point atomics, and nothing depends on chunk_states or on which other
-// states share the call.
+// Shape (state_sweep.h): streaming kernels, 16-byte words (two amplitudes), blockIdx.y = the state, blockIdx.x strides
+// over the state's words with gridDim.x = words / 1024 workgroups of 256 threads (four words per thread, consecutive
+// threads on consecutive words).  The grid depends on n alone, every state is summed by itself, the partials meet in a
+// fixed LDS tree and are added in index order: no floating-point atomics, and nothing depends on chunk_states or on
+// which other states share the call.
 //
-// (a file of its own in the source tree, included by kernels.hip inside namespace qhbm: it uses philox4x32_10)
+// (a translation unit of its own in the source tree, compiled as part of states.hip; it uses no name of another .hip file)
+#include <algorithm>
+#include <cmath>
 
+#include "device_common.h"
+#include "kernels.h"
+#include "state_sweep.h"
+
+namespace qhbm {
 namespace {
-
-constexpr uint32_t kThThreads = 256;
-constexpr uint32_t kThSliceWords = 4 * kThThreads;
-
-uint32_t th_slices(uint64_t words) { return uint32_t((words + kThSliceWords - 1) / kThSliceWords); }
-
-__device__ __forceinline__ double th_block_sum(double v, double* sh) {
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (uint32_t s = kThThreads / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-    __syncthreads();
-  }
-  return sh[0];
-}
-
-// c * (two amplitudes)
-__device__ __forceinline__ float4 th_cmul(float2 c, float4 t) {
-  return make_float4(c.x * t.x - c.y * t.y, c.x * t.y + c.y * t.x, c.x * t.z - c.y * t.w, c.x * t.w + c.y * t.z);
-}
 
 // words = 2^(n_eff - 1): 16-byte words of one state in the workspace; w, tprev, acc: the chunk's states, element 0 first
 template <bool FIRST, bool NORM>
-__global__ __launch_bounds__(kThThreads) void cheb_step_kernel(const float4* __restrict__ w, float4* __restrict__ tprev,
-                                                               float4* __restrict__ acc, uint64_t words, float2 c0, float2 c,
-                                                               const double* __restrict__ scale, double* __restrict__ part) {
-  __shared__ double sh[NORM ? kThThreads : 1];
+__global__ __launch_bounds__(kSweepThreads) void cheb_step_kernel(const float4* __restrict__ w, float4* __restrict__ tprev,
+                                                                  float4* __restrict__ acc, uint64_t words, float2 c0, float2 c,
+                                                                  const double* __restrict__ scale, double* __restrict__ part) {
+  __shared__ double sh[NORM ? kSweepThreads : 1];
   const uint64_t base = uint64_t(blockIdx.y) * words;
   const double sc = FIRST ? scale[blockIdx.y] : 1.0;
   double sum = 0.0;
-  for (uint64_t i = uint64_t(blockIdx.x) * kThThreads + threadIdx.x; i < words; i += uint64_t(gridDim.x) * kThThreads) {
+  for (uint64_t i = uint64_t(blockIdx.x) * kSweepThreads + threadIdx.x; i < words; i += uint64_t(gridDim.x) * kSweepThreads) {
     const float4 wv = w[base + i];
     float4 t, a;
     if (FIRST) {
       const float4 s = acc[base + i];
       const float4 t0 = make_float4(float(double(s.x) * sc), float(double(s.y) * sc), float(double(s.z) * sc), float(double(s.w) * sc));
-      const float4 a0 = th_cmul(c0, t0), a1 = th_cmul(c, wv);
+      const float4 a0 = sweep_cmul(c0, t0), a1 = sweep_cmul(c, wv);
       t = t0;
       a = make_float4(a0.x + a1.x, a0.y + a1.y, a0.z + a1.z, a0.w + a1.w);
     } else {
       const float4 p = tprev[base + i], s = acc[base + i];
       t = make_float4(wv.x - p.x, wv.y - p.y, wv.z - p.z, wv.w - p.w);
-      const float4 d = th_cmul(c, t);
+      const float4 d = sweep_cmul(c, t);
       a = make_float4(s.x + d.x, s.y + d.y, s.z + d.z, s.w + d.w);
     }
     tprev[base + i] = t;
     acc[base + i] = a;
-    if (NORM) sum += (double(a.x) * double(a.x) + double(a.y) * double(a.y)) + (double(a.z) * double(a.z) + double(a.w) * double(a.w));
+    if (NORM) sum += word_norm2(a);
   }
   if (NORM) {
-    const double total = th_block_sum(sum, sh);
+    const double total = sweep_block_sum(sum, sh);
     if (threadIdx.x == 0) part[uint64_t(blockIdx.y) * gridDim.x + blockIdx.x] = total;
   }
 }
 
 // One workgroup per state of the chunk.  wr [n_ops]: w_k / R; up1 [c, n_ops]: the upstream rows of the next step's first term.
-__global__ __launch_bounds__(kThThreads) void finish_step_kernel(const double* __restrict__ part, uint32_t slices, double x,
-                                                                 double* __restrict__ log_norm, double* __restrict__ scale,
-                                                                 const double* __restrict__ wr, uint32_t n_ops,
-                                                                 float* __restrict__ up1) {
-  __shared__ double sh[kThThreads];
-  const double* row = part + uint64_t(blockIdx.x) * slices;
-  double acc = 0.0;
-  for (uint32_t i = threadIdx.x; i < slices; i += kThThreads) acc += row[i];
-  const double norm = sqrt(th_block_sum(acc, sh));
+__global__ __launch_bounds__(kSweepThreads) void finish_step_kernel(const double* __restrict__ part, uint32_t slices, double x,
+                                                                    double* __restrict__ log_norm, double* __restrict__ scale,
+                                                                    const double* __restrict__ wr, uint32_t n_ops,
+                                                                    float* __restrict__ up1) {
+  __shared__ double sh[kSweepThreads];
+  const double norm = sqrt(sweep_row_sum(part + uint64_t(blockIdx.x) * slices, slices, sh));
   const double sc = norm > 0.0 ? 1.0 / norm : 0.0;
   if (threadIdx.x == 0) {
     scale[blockIdx.x] = sc;
     log_norm[blockIdx.x] += log(norm) + x;  // (norm 0: -inf, and it stays there)
   }
-  for (uint32_t k = threadIdx.x; k < n_ops; k += kThThreads) up1[uint64_t(blockIdx.x) * n_ops + k] = float(wr[k] * sc);
+  for (uint32_t k = threadIdx.x; k < n_ops; k += kSweepThreads) up1[uint64_t(blockIdx.x) * n_ops + k] = float(wr[k] * sc);
 }
 
 // scale [c] = 1; log_norm [c] (or null) = log ||phi|| from norm2 [c]; up1 [c, n_ops] = wr, up2 [c, n_ops] (or null) = 2 wr
-__global__ __launch_bounds__(kThThreads) void evolve_init_kernel(uint32_t c, const double* __restrict__ norm2,
-                                                                 double* __restrict__ log_norm, double* __restrict__ scale,
-                                                                 const double* __restrict__ wr, uint32_t n_ops,
-                                                                 float* __restrict__ up1, float* __restrict__ up2) {
-  const uint64_t i = uint64_t(blockIdx.x) * kThThreads + threadIdx.x;
+__global__ __launch_bounds__(kSweepThreads) void evolve_init_kernel(uint32_t c, const double* __restrict__ norm2,
+                                                                    double* __restrict__ log_norm, double* __restrict__ scale,
+                                                                    const double* __restrict__ wr, uint32_t n_ops,
+                                                                    float* __restrict__ up1, float* __restrict__ up2) {
+  const uint64_t i = uint64_t(blockIdx.x) * kSweepThreads + threadIdx.x;
   if (i < c) {
     if (scale) scale[i] = 1.0;
     if (log_norm) log_norm[i] = 0.5 * log(norm2[i]);
@@ -113,32 +98,13 @@ __global__ __launch_bounds__(kThThreads) void evolve_init_kernel(uint32_t c, con
   }
 }
 
-// dst row r (dst_pitch words) = src row r (src_pitch words) * f_r for the first words_copy words, zeros behind them;
-// f_r = scale[r] (or 1) * sqrt(norm2[r]) (or 1)
-__global__ __launch_bounds__(kThThreads) void scale_copy_kernel(const float4* __restrict__ src, uint64_t src_pitch,
-                                                                float4* __restrict__ dst, uint64_t dst_pitch, uint64_t words_copy,
-                                                                const double* __restrict__ scale, const double* __restrict__ norm2) {
-  const float4* in = src + uint64_t(blockIdx.y) * src_pitch;
-  float4* out = dst + uint64_t(blockIdx.y) * dst_pitch;
-  const bool scaled = scale || norm2;
-  const double f = (scale ? scale[blockIdx.y] : 1.0) * (norm2 ? sqrt(norm2[blockIdx.y]) : 1.0);
-  for (uint64_t i = uint64_t(blockIdx.x) * kThThreads + threadIdx.x; i < dst_pitch; i += uint64_t(gridDim.x) * kThThreads) {
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (i < words_copy) {
-      v = in[i];
-      if (scaled) v = make_float4(float(double(v.x) * f), float(double(v.y) * f), float(double(v.z) * f), float(double(v.w) * f));
-    }
-    out[i] = v;
-  }
-}
-
 constexpr uint32_t kRandomStatesTag = 0x54505153u;
 
 // One thread per 16-byte word (amplitudes 2 i and 2 i + 1) of one state; words = 2^(n - 1)
-__global__ __launch_bounds__(kThThreads) void random_states_kernel(float4* __restrict__ out, uint64_t words, uint64_t seed,
-                                                                   uint32_t first_state, float mag) {
+__global__ __launch_bounds__(kSweepThreads) void random_states_kernel(float4* __restrict__ out, uint64_t words, uint64_t seed,
+                                                                      uint32_t first_state, float mag) {
   float4* row = out + uint64_t(blockIdx.y) * words;
-  for (uint64_t i = uint64_t(blockIdx.x) * kThThreads + threadIdx.x; i < words; i += uint64_t(gridDim.x) * kThThreads) {
+  for (uint64_t i = uint64_t(blockIdx.x) * kSweepThreads + threadIdx.x; i < words; i += uint64_t(gridDim.x) * kSweepThreads) {
     const uint64_t j = 2 * i, g = j >> 6;
     uint32_t c[4] = {uint32_t(g), uint32_t(g >> 32), first_state + blockIdx.y, kRandomStatesTag};
     philox4x32_10(c, uint32_t(seed), uint32_t(seed >> 32));
@@ -150,13 +116,11 @@ __global__ __launch_bounds__(kThThreads) void random_states_kernel(float4* __res
 
 }  // namespace
 
-size_t cheb_norm_parts_count(uint32_t n_eff, uint32_t c) { return size_t(c) * th_slices(uint64_t(1) << (n_eff - 1)); }
-
 hipError_t launch_cheb_step(bool first, bool with_norm, const float2* w, float2* tprev, float2* acc, uint32_t n_eff, uint32_t c,
                             float2 c0, float2 coef, const double* scale, double* parts, hipStream_t stream) {
   if (n_eff < 1 || c == 0 || c > 65535u || (first && !scale) || (with_norm && !parts)) return hipErrorInvalidValue;
   const uint64_t words = uint64_t(1) << (n_eff - 1);
-  const dim3 grid(th_slices(words), c), block(kThThreads);
+  const dim3 grid(sweep_slices(words), c), block(kSweepThreads);
   const float4* w4 = reinterpret_cast<const float4*>(w);
   float4 *t4 = reinterpret_cast<float4*>(tprev), *a4 = reinterpret_cast<float4*>(acc);
   if (first && with_norm) hipLaunchKernelGGL((cheb_step_kernel<true, true>), grid, block, 0, stream, w4, t4, a4, words, c0, coef, scale, parts);
@@ -169,7 +133,7 @@ hipError_t launch_cheb_step(bool first, bool with_norm, const float2* w, float2*
 hipError_t launch_finish_step(const double* parts, uint32_t n_eff, uint32_t c, double x, double* log_norm, double* scale,
                               const double* wr, uint32_t n_ops, float* up1, hipStream_t stream) {
   if (n_eff < 1 || c == 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(finish_step_kernel, dim3(c), dim3(kThThreads), 0, stream, parts, th_slices(uint64_t(1) << (n_eff - 1)), x,
+  hipLaunchKernelGGL(finish_step_kernel, dim3(c), dim3(kSweepThreads), 0, stream, parts, sweep_slices(uint64_t(1) << (n_eff - 1)), x,
                      log_norm, scale, wr, n_ops, up1);
   return hipGetLastError();
 }
@@ -178,19 +142,8 @@ hipError_t launch_evolve_init(uint32_t c, const double* norm2, double* log_norm,
                               float* up1, float* up2, hipStream_t stream) {
   const uint64_t count = std::max<uint64_t>(c, uint64_t(c) * n_ops);
   if (!count) return hipSuccess;
-  hipLaunchKernelGGL(evolve_init_kernel, dim3(unsigned((count + kThThreads - 1) / kThThreads)), dim3(kThThreads), 0, stream, c,
+  hipLaunchKernelGGL(evolve_init_kernel, dim3(unsigned((count + kSweepThreads - 1) / kSweepThreads)), dim3(kSweepThreads), 0, stream, c,
                      norm2, log_norm, scale, wr, n_ops, up1, up2);
-  return hipGetLastError();
-}
-
-hipError_t launch_scale_copy_states(const float2* src, uint32_t n_src, float2* dst, uint32_t n_dst, uint32_t n_copy, uint32_t c,
-                                    const double* scale, const double* norm2, hipStream_t stream) {
-  if (!c) return hipSuccess;
-  if (n_copy < 1 || n_copy > n_src || n_copy > n_dst || c > 65535u) return hipErrorInvalidValue;
-  const uint64_t dst_pitch = uint64_t(1) << (n_dst - 1);
-  hipLaunchKernelGGL(scale_copy_kernel, dim3(th_slices(dst_pitch), c), dim3(kThThreads), 0, stream,
-                     reinterpret_cast<const float4*>(src), uint64_t(1) << (n_src - 1), reinterpret_cast<float4*>(dst), dst_pitch,
-                     uint64_t(1) << (n_copy - 1), scale, norm2);
   return hipGetLastError();
 }
 
@@ -202,9 +155,10 @@ hipError_t launch_random_states(float2* out, uint32_t n_states, uint32_t n, uint
   const uint64_t words = uint64_t(1) << (n - 1);
   for (uint32_t r0 = 0; r0 < n_states; r0 += 65535u) {  // (the state is a grid dimension)
     const uint32_t rows = std::min<uint32_t>(65535u, n_states - r0);
-    hipLaunchKernelGGL(random_states_kernel, dim3(th_slices(words), rows), dim3(kThThreads), 0, stream,
+    hipLaunchKernelGGL(random_states_kernel, dim3(sweep_slices(words), rows), dim3(kSweepThreads), 0, stream,
                        reinterpret_cast<float4*>(out) + uint64_t(r0) * words, words, seed, first_state + r0, mag);
   }
   return hipGetLastError();
 }
 
+}  // namespace qhbm

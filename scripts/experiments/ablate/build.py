@@ -308,7 +308,7 @@ def main(which):
       subprocess.check_call(["/opt/rocm/bin/hipcc"] + flags + ["-c", path, "-o", obj], cwd=CSRC)
       subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", obj,
                              os.path.join(CSRC, "engine.o"), os.path.join(CSRC, "schedule.o"),
-                             os.path.join(CSRC, "observable.o"), "-o",
+                             os.path.join(CSRC, "observable.o"), os.path.join(CSRC, "states.o"), "-o",
                              os.path.join(OUT, f"lib_{name}.so")], cwd=CSRC)
       print("built", name, flush=True)
     except subprocess.CalledProcessError as exc:

@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "qhbm-library_amd", "csrc")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-mllvm", "-disable-promote-alloca-to-vector=1",
          "-mllvm", "-amdgpu-sched-strategy=max-ilp", "--cuda-device-only"]   # = csrc/Makefile CXXFLAGS + KFLAGS
-SOURCES = ("kernels.hip", "observable.hip")
+SOURCES = ("kernels.hip", "observable.hip", "states.hip")
 
 
 def _demangle(name):

@@ -5,5 +5,5 @@ include Makefile
 $(OUT)/dense_start.o: dense_start.cpp plan_emulate.h $(HDRS)
 	mkdir -p $(OUT)
 	$(HIPCC) $(FLAGS) -O2 -x hip -c $< -o $@
-$(OUT)/dense_start: $(OUT)/dense_start.o $(OUT)/plan_emulate.o $(OUT)/schedule.o $(OUT)/engine.o $(CSRC)/kernels.o $(CSRC)/observable.o
+$(OUT)/dense_start: $(OUT)/dense_start.o $(OUT)/plan_emulate.o $(OUT)/schedule.o $(OUT)/engine.o $(KERNEL_OBJS)
 	$(HIPCC) $(SAN) $^ -o $@

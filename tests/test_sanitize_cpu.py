@@ -37,7 +37,7 @@ def _build():
   if not shutil.which(HIPCC):
     pytest.skip("no hipcc")
   # the kernel launchers the engine links against come from the product build (never called here)
-  subprocess.run(["make", "kernels.o", "observable.o"], cwd=CSRC, check=True, capture_output=True, timeout=1200)
+  subprocess.run(["make", "kernels.o", "observable.o", "states.o"], cwd=CSRC, check=True, capture_output=True, timeout=1200)
   build = subprocess.run(["make", "-j4"], cwd=SAN, capture_output=True, text=True, timeout=900)
   assert build.returncode == 0, build.stdout[-2000:] + build.stderr[-2000:]
 

@@ -77,7 +77,7 @@ def test_no_register_spills_in_the_kernels_the_default_planner_selects():
 def test_no_floating_point_atomics_in_the_device_code():
   """README.md and DESIGN.md promise no floating-point atomics anywhere: every cross-workgroup sum is a fixed-order
   reduction or an integer (fixed-point) atomic, so a result does not depend on the order the workgroups run in.
-  The gfx950 assembly of both kernel sources, built with the Makefile's flags, must hold no floating-point atomic add
+  The gfx950 assembly of the three kernel sources, built with the Makefile's flags, must hold no floating-point atomic add
   of the vector-memory or LDS instruction sets."""
   import re
   import shutil
@@ -92,7 +92,7 @@ def test_no_floating_point_atomics_in_the_device_code():
                             r"|\bds_(?:pk_)?add(?:_rtn)?_(?:f16|bf16|f32|f64)\b")
   with tempfile.TemporaryDirectory() as tmp:
     procs = {}
-    for src in ("kernels.hip", "observable.hip"):
+    for src in ("kernels.hip", "observable.hip", "states.hip"):
       asm = os.path.join(tmp, src + ".s")
       procs[src] = (asm, subprocess.Popen(
           [hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-mllvm", "-disable-promote-alloca-to-vector=1",
@@ -114,3 +114,25 @@ def test_no_floating_point_atomics_in_the_device_code():
         if m:
           found.append((fn, m.group(0)))
       assert not found, f"{src}: floating-point atomics in {sorted(set(found))}"
+
+
+def test_every_state_vector_kernel_file_compiles_alone():
+  """csrc/states.hip is five #include lines; each of the five files is a translation unit of its own -- it includes what
+  it needs, opens namespace qhbm itself and uses no name another .hip file defines (what they share is state_sweep.h) --
+  so none of them depends on its place in the list, and the next state-vector feature is an edit of one small file."""
+  import shutil
+  import subprocess
+  import pytest
+  hipcc = "/opt/rocm/bin/hipcc"
+  if not shutil.which(hipcc):
+    pytest.skip("no hipcc")
+  csrc = os.path.join(ROOT, "qhbm-library_amd", "csrc")
+  with open(os.path.join(csrc, "states.hip")) as f:
+    listed = [line.split('"')[1] for line in f if line.startswith("#include")]
+  files = ("import_states.hip", "thermal.hip", "krylov.hip", "gram.hip", "reduced.hip")
+  assert sorted(listed) == sorted(files)
+  procs = {src: subprocess.Popen([hipcc, "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-fsyntax-only", src],
+                                 cwd=csrc, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for src in files}
+  for src, proc in procs.items():
+    log = proc.communicate(timeout=600)[0]
+    assert proc.returncode == 0, f"{src} does not compile alone:\n{log[-2000:]}"
