@@ -459,6 +459,57 @@ int qhbm_sample_counts(qhbm_engine* h, const int8_t* d_bits, int U, const float*
                        int n_programs, const int32_t* shift_gates, const float* shifts,
                        int n_shots, uint64_t seed, int32_t* d_out_counts, void* stream);
 
+/* ---- Pauli-string estimates from shots, at any register width ----
+ * Added WITHIN ABI version 5: purely additive, QHBM_ABI_VERSION stays 5.
+ *
+ * A Pauli-Z-string estimate needs neither the shots nor a counter per outcome, only T integers per (program, state):
+ *   out[q, s, t] = sum_{j < n_shots} (-1)^popcount(x_j & m_t)                                   int32
+ * THE DRAW.  For element (program q, state row s) and shot j:
+ *   uniform   exactly that of qhbm_sample_counts: Philox4x32-10, counter {j, s, 0x51b0c6a1, q}, key (seed low, seed high),
+ *             u = c0 2^-32 + c1 2^-64 in float64;
+ *   mass      p(x) = re^2 + im^2 of the complex64 amplitude in float64: both products exact, one rounding in the sum;
+ *   outcome   the first x whose inclusive prefix sum_{y <= x} p(y) exceeds u * total (one float64 multiply; total = sum p as
+ *             the kernel sums it).  Every sum is float64 in this fixed order: a sub-block of 16 consecutive amplitudes is
+ *             added in index order; the 64 sub-block masses of a block of 1024 amplitudes meet in a Hillis-Steele scan
+ *             (offsets 1, 2, 4, ..., 32); the block masses meet in the scan of qhbm_sample (256 at a time, offsets 1 .. 128,
+ *             a running carry).  The shot takes the first block whose prefix exceeds v = u * total, subtracts the prefix of
+ *             the blocks before it, takes the first sub-block of that block whose prefix exceeds the rest r, and the first
+ *             amplitude at which (prefix of the sub-blocks before) + p_0 + p_1 + ... exceeds r.  There is no fp32 step.
+ *             An outcome of zero mass is never drawn: where no prefix exceeds (u can round to 1), or where a scanned and a
+ *             sequential prefix differ in the last place, the shot takes the last outcome of non-zero mass at or before
+ *             the place the search reached.  A state of total 0 (or not > 0) draws nothing and its sums are 0.  For states
+ *             whose partial sums are all exact in float64 this is searchsorted(cumsum(p), u * total, side = "right"),
+ *             clamped to the last outcome of non-zero mass, whatever the order of additions;
+ *   masks     `masks` is a HOST array of T uint64 in QUBIT space, as keep_mask of qhbm_reduced_density: bit k set <=> qubit
+ *             k, and qubit 0 is the most significant bit of the amplitude index.  Mask 0 gives +n_shots.  (Host, like
+ *             shift_gates: a mask bit at or above n_qubits is refused before anything is launched, and the words reach the
+ *             device as kernel arguments -- no copy, nothing to synchronise with.)
+ * Integer atomics only: the result is bit-reproducible and independent of chunking, of launch-set cuts and of the order in
+ * which shots are processed.  Limits: 1 <= T <= 1024, 0 <= n_shots <= 2^31 - 1, n_qubits <= 31.
+ *
+ *   qhbm_sample_parities         d_out [n_programs, U, T] int32 (device, overwritten).  Programs and their validation exactly
+ *                                as in qhbm_sample_counts (HOST shift_gates / shifts; gate < 0 = the unshifted circuit; a
+ *                                shifted constant-exponent gate is refused).  The prefix tables (1/16 of a state) are engine
+ *                                owned and count against workspace_budget_mb when the launch sets are cut.  No limit on
+ *                                n_qubits beyond the engine's; idle padding qubits are the high index bits and stay |0>.
+ *   qhbm_sample_parities_states  d_states [M, 2^n_qubits] complex64, 16-byte aligned, only read, need not be normalised;
+ *                                d_out [M, T] int32 (overwritten).  Counter words: s = first_row + m, q = program.  No
+ *                                engine: the current device.  Asynchronous on `stream`; allocates nothing, synchronises
+ *                                nothing.  d_scratch: qhbm_sample_parities_scratch_bytes bytes, 8-byte aligned, which may
+ *                                hold anything.  Refused, each with a message and before anything is launched: M <= 0;
+ *                                n_qubits outside [1, 31]; T outside [1, 1024]; n_shots negative or above 2^31 - 1; masks,
+ *                                d_states, d_scratch or d_out NULL; a misaligned pointer; a mask bit at or above n_qubits;
+ *                                first_row + M above 2^32.
+ *   qhbm_sample_parities_scratch_bytes  *out = 4096 + 8 min(M, 65535) (2^max(n - 10, 0) + 2^max(n - 4, 0)); needs no device.
+ *                                Refused: the shape and the shot count as above, out NULL. */
+int qhbm_sample_parities(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, int n_programs,
+                         const int32_t* shift_gates, const float* shifts, const uint64_t* masks, int T, int64_t n_shots,
+                         uint64_t seed, int32_t* d_out, void* stream);
+int qhbm_sample_parities_scratch_bytes(int M, int n_qubits, int64_t n_shots, size_t* out);
+int qhbm_sample_parities_states(const void* d_states, int M, int n_qubits, const uint64_t* masks, int T, int64_t n_shots,
+                                uint64_t seed, uint64_t first_row, uint32_t program, void* d_scratch, int32_t* d_out,
+                                void* stream);
+
 /* One adjoint VJP per parameter-shifted program, all programs in one launch set -- the rows of the BKM information
  * matrix of a QHBM (baselines/train.py:161-249: every circuit variable shifted by +-1/2, a full gradient per shifted
  * expectation).  Program q is the installed circuit with `shifts[q]` added to the exponent of gate `shift_gates[q]`

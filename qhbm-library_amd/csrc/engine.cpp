@@ -200,6 +200,8 @@ struct qhbm_engine {
   DevBuf<float> op_scale, op_inv_scale; // per op: 2^(+-shift), see program.h kValueFracBits
   std::vector<float> h_op_scale, h_op_inv_scale;
   DevBuf<double> block_cum;
+  DevBuf<double> par_tables;    // qhbm_sample_parities: block and sub-block prefixes of a launch set (sample_parity.hip)
+  DevBuf<uint32_t> par_masks;    // ... its masks in index space
   DevBuf<int> param_slot_begin, param_slots;
   // qhbm_program_vjps: per-element copies of bitstrings and upstream rows, the base program's states of a shared prefix,
   // the gradient rows of the programs in flight, fp64 value accumulators
@@ -257,7 +259,7 @@ size_t plan_bytes(const DevicePlan& d) {
 // its footprint with it).
 size_t own_bytes(const qhbm_engine* h) {
   return buf_bytes(h->psi) + buf_bytes(h->lam) + buf_bytes(h->state_grad) + buf_bytes(h->tile_grad) +
-         buf_bytes(h->vals64) + buf_bytes(h->block_cum) + buf_bytes(h->coef_batch) + buf_bytes(h->vals_batch) +
+         buf_bytes(h->vals64) + buf_bytes(h->block_cum) + buf_bytes(h->par_tables) + buf_bytes(h->par_masks) + buf_bytes(h->coef_batch) + buf_bytes(h->vals_batch) +
          buf_bytes(h->value_part) + buf_bytes(h->probe_out) + buf_bytes(h->probe_sink) + buf_bytes(h->upstream_tmp) + buf_bytes(h->vals_tmp) + buf_bytes(h->prog_acc) +
          buf_bytes(h->shift_vals) + buf_bytes(h->shift_weight) + buf_bytes(h->shift_gates) + buf_bytes(h->shift_param) + buf_bytes(h->shift_dst) +
          buf_bytes(h->slot_factor) + buf_bytes(h->phase_cs) + buf_bytes(h->shift_phases) + buf_bytes(h->terms) +
@@ -1514,6 +1516,35 @@ int table_vjp(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params
   return 0;
 }
 
+// ---- signed shot sums of Pauli-Z strings (qhbm_sample_parities, qhbm_sample_parities_states; sample_parity.hip) ----
+constexpr int kParityMaxMasks = 1024;
+constexpr int64_t kParityMaxShots = 2147483647;
+
+// The masks are a HOST array in qubit space; *idx = the same strings in amplitude-index space (qubit 0 = the most
+// significant of the n index bits).
+int check_parity_masks(qhbm_engine* h, int n, const uint64_t* masks, int T, int64_t n_shots, std::vector<uint32_t>* idx) {
+  if (T < 1 || T > kParityMaxMasks) return fail(h, "T (the number of masks) must be in [1, 1024]");
+  if (n_shots < 0) return fail(h, "negative shot count");
+  if (n_shots > kParityMaxShots) return fail(h, "too many shots: n_shots <= 2^31 - 1");
+  if (!masks) return fail(h, "masks is NULL");
+  idx->assign(size_t(T), 0u);
+  for (int t = 0; t < T; ++t) {
+    if (n < 64 && (masks[t] >> n) != 0)
+      return fail(h, "masks[" + std::to_string(t) + "] has a bit at or above n_qubits = " + std::to_string(n));
+    for (int k = 0; k < n; ++k)
+      if ((masks[t] >> k) & 1u) (*idx)[size_t(t)] |= 1u << (n - 1 - k);
+  }
+  return 0;
+}
+
+int check_parity_states_shape(int M, int n_qubits) {
+  if (M <= 0) return fail(nullptr, "M (the number of states) must be positive");
+  if (n_qubits < 1 || n_qubits > 31) return fail(nullptr, "n_qubits must be in [1, 31]");
+  return 0;
+}
+
+constexpr size_t kParityMaskBytes = size_t(kParityMaxMasks) * sizeof(uint32_t);  // the head of the states entry's scratch
+
 }  // namespace
 
 // ================================================================================
@@ -2591,6 +2622,97 @@ int qhbm_sample_counts(qhbm_engine* h, const int8_t* d_bits, int U, const float*
     if (int rc = run_program_groups(h, d_bits, d_params, g, order, 0u, n_prog, s0, c, nullptr, {true, true, false}, s, draw))
       return rc;
   }
+  return 0;
+}
+
+int qhbm_sample_parities(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, int n_programs,
+                         const int32_t* shift_gates, const float* shifts, const uint64_t* masks, int T, int64_t n_shots,
+                         uint64_t seed, int32_t* d_out, void* stream) {
+  if (!h) return 1;
+  if (U < 0 || n_programs < 0) return fail(h, "negative batch size or program count");
+  if (n_programs && (!shift_gates || !shifts)) return fail(h, "shift_gates / shifts are NULL");
+  if (h->model.n < 1 || h->model.n > 31) return fail(h, "qhbm_sample_parities needs a circuit of 1 .. 31 qubits (qhbm_set_circuit)");
+  std::vector<uint32_t> idx_masks;
+  if (int rc = check_parity_masks(h, h->model.n, masks, T, n_shots, &idx_masks)) return rc;
+  for (int q = 0; q < n_programs; ++q)
+    if (shift_gates[q] >= int(h->model.gates.size())) return fail(h, "shift_gates entry out of range");
+  for (int q = 0; q < n_programs; ++q)
+    if (shift_gates[q] >= 0 && shifts[q] != 0.f && h->model.gates[size_t(shift_gates[q])].param_idx < 0)
+      return fail(h, "shift_gates entry addresses a gate with a constant exponent: only parametrised gates have shifted programs");
+  if (U && n_programs && !d_out) return fail(h, "d_out is NULL");
+  if (int rc = need_device(h)) return rc;
+  if (int rc = upload_model(h)) return rc;
+  if (U == 0 || n_programs == 0) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DevicePlan& d = h->fwd;
+  h->retained_U = 0;
+  h->state_grad_U = 0;
+  const uint32_t n_prog = uint32_t(n_programs), n_eff = uint32_t(d.plan.n_eff);
+  HIPCHK(launch_zero_fill(d_out, size_t(n_prog) * size_t(U) * size_t(T) * sizeof(int32_t), s));
+  if (n_shots == 0) return 0;
+  // every program from pass 0, in the caller's order, as in qhbm_sample_counts
+  const ProgramOrder order = order_programs(d.plan, h->model.gates.size(), shift_gates, n_prog, false, true);
+  if (int rc = upload_shift_tables(h, order, shift_gates, shifts, s)) return rc;
+  LaunchSets g = launch_set_geometry(h, U, n_prog, order, 1, true, false);
+  {  // the prefix tables of an element count against the workspace budget beside its state
+    const size_t per_element = state_bytes(h) + shot_parity_table_doubles(n_eff, 1) * sizeof(double);
+    const size_t cap = std::max<size_t>(1, budget_bytes(h) / per_element);
+    if (size_t(g.Uc) * g.Pc > cap) {
+      g.Uc = uint32_t(std::min<size_t>(g.Uc, cap));
+      g.Pc = uint32_t(std::max<size_t>(1, cap / g.Uc));
+    }
+  }
+  if (int rc = ensure_state_buffers(h, g.Uc * g.Pc, false)) return rc;
+  HIPCHK(h->par_tables.reserve(shot_parity_table_doubles(n_eff, size_t(g.Uc) * g.Pc)));
+  HIPCHK(h->par_masks.reserve(size_t(kParityMaxMasks)));
+  if (int rc = values_begin(h, int(g.Uc * g.Pc), s)) return rc;  // measurement by-products land in the fixed-point scratch
+  if (int rc = grow_coef_batch(h, g, s)) return rc;
+  HIPCHK(launch_shot_parity_masks(idx_masks.data(), uint32_t(T), h->par_masks.p, s));
+  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += g.Uc) {
+    const uint32_t c = std::min<uint32_t>(g.Uc, uint32_t(U) - s0);
+    auto draw = [&](uint32_t q0, uint32_t nq) -> int {
+      HIPCHK(launch_shot_parities(h->psi.p, n_eff, h->model.n, nq * c, c, q0, h->par_tables.p, h->par_masks.p, uint32_t(T),
+                                  uint32_t(n_shots), seed, s0, uint32_t(U), 0u, 0u, d_out, s));
+      return 0;
+    };
+    if (int rc = run_program_groups(h, d_bits, d_params, g, order, 0u, n_prog, s0, c, nullptr, {true, true, false}, s, draw))
+      return rc;
+  }
+  return 0;
+}
+
+int qhbm_sample_parities_scratch_bytes(int M, int n_qubits, int64_t n_shots, size_t* out) {
+  if (!out) return fail(nullptr, "out is NULL");
+  if (int rc = check_parity_states_shape(M, n_qubits)) return rc;
+  if (n_shots < 0) return fail(nullptr, "negative shot count");
+  if (n_shots > kParityMaxShots) return fail(nullptr, "too many shots: n_shots <= 2^31 - 1");
+  *out = kParityMaskBytes + shot_parity_table_doubles(uint32_t(n_qubits), size_t(std::min(M, 65535))) * sizeof(double);
+  return 0;
+}
+
+int qhbm_sample_parities_states(const void* d_states, int M, int n_qubits, const uint64_t* masks, int T, int64_t n_shots,
+                                uint64_t seed, uint64_t first_row, uint32_t program, void* d_scratch, int32_t* d_out,
+                                void* stream) {
+  if (int rc = check_parity_states_shape(M, n_qubits)) return rc;
+  std::vector<uint32_t> idx_masks;
+  if (int rc = check_parity_masks(nullptr, n_qubits, masks, T, n_shots, &idx_masks)) return rc;
+  if (first_row + uint64_t(M) > (uint64_t(1) << 32)) return fail(nullptr, "first_row + M exceeds 2^32");
+  if (int rc = check_pointer(nullptr, d_states, 16, "d_states")) return rc;
+  if (int rc = check_pointer(nullptr, d_scratch, 8, "d_scratch")) return rc;
+  if (int rc = check_pointer(nullptr, d_out, 4, "d_out")) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const uint32_t n = uint32_t(n_qubits);
+  hipError_t e = launch_zero_fill(d_out, size_t(M) * size_t(T) * sizeof(int32_t), s);
+  uint32_t* d_masks = static_cast<uint32_t*>(d_scratch);
+  double* tables = reinterpret_cast<double*>(static_cast<char*>(d_scratch) + kParityMaskBytes);
+  if (e == hipSuccess && n_shots > 0) e = launch_shot_parity_masks(idx_masks.data(), uint32_t(T), d_masks, s);
+  // states in slices of 65535 (grid.y); the slices run in stream order and share the tables
+  for (uint32_t m0 = 0; e == hipSuccess && n_shots > 0 && m0 < uint32_t(M); m0 += 65535u) {
+    const uint32_t c = std::min<uint32_t>(65535u, uint32_t(M) - m0);
+    e = launch_shot_parities(static_cast<const float2*>(d_states) + (size_t(m0) << n), n, n_qubits, c, c, 0u, tables, d_masks,
+                             uint32_t(T), uint32_t(n_shots), seed, m0, uint32_t(M), uint32_t(first_row), program, d_out, s);
+  }
+  if (e != hipSuccess) return fail(nullptr, std::string("qhbm_sample_parities_states: ") + hipGetErrorString(e));
   return 0;
 }
 

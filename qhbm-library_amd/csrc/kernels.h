@@ -181,6 +181,17 @@ struct ShiftPhase {
 hipError_t launch_sample_counts(const float2* psi, uint32_t n, int n_user, uint32_t n_elements, uint32_t prog_states,
                                 uint32_t prog0, double* block_cum, uint32_t n_shots, uint64_t seed, uint32_t state0,
                                 uint32_t n_states_total, int* out, hipStream_t stream);
+// Signed shot sums of Pauli-Z strings (sample_parity.hip): out[program, state, t] += sum over n_shots shots of
+// (-1)^popcount(x & mask_t) for the n_elements <= 65535 elements of launch_sample_counts' layout, rows 2^row_bits amplitudes
+// apart; out is zeroed by the caller.  d_masks [T] uint32 in INDEX space, written by launch_shot_parity_masks from a HOST
+// array (the words travel as kernel arguments).  tables: shot_parity_table_doubles(row_bits, n_elements) doubles of scratch
+// that may hold anything.  ctr_state / ctr_prog are added to the state row / program in the Philox counter alone.
+size_t shot_parity_table_doubles(uint32_t row_bits, size_t n_elements);
+hipError_t launch_shot_parity_masks(const uint32_t* host_masks, uint32_t T, uint32_t* d_masks, hipStream_t stream);
+hipError_t launch_shot_parities(const float2* psi, uint32_t row_bits, int n_user, uint32_t n_elements, uint32_t prog_states,
+                                uint32_t prog0, double* tables, const uint32_t* d_masks, uint32_t T, uint32_t n_shots,
+                                uint64_t seed, uint32_t state0, uint32_t n_states_total, uint32_t ctr_state, uint32_t ctr_prog, int* out,
+                                hipStream_t stream);
 hipError_t launch_global_phase(const CoefJob* jobs, int n_jobs, const ShiftPhase* shifts, int n_shifts,
                                const float* params, float* out_cs, hipStream_t stream);
 hipError_t launch_scale_states(float2* st, size_t count, const float* cs, hipStream_t stream);

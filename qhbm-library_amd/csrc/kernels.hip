@@ -3290,6 +3290,7 @@ hipError_t launch_parity_energy_vjp(const int8_t* bits, int64_t n_rows, int n, c
 
 #include "gwg.hip"
 #include "parity_table.hip"
+#include "sample_parity.hip"
 
 size_t observable_value_parts(uint32_t n, uint32_t n_states) { return size_t(n_states) * ((1u << n) / (256u * obs_amps_per_thread(n))); }
 

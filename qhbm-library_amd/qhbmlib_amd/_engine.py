@@ -50,6 +50,7 @@ ABI_SYMBOLS = (
     "qhbm_krylov_basis", "qhbm_krylov_combine", "qhbm_describe_krylov",
     "qhbm_gram_scratch_bytes", "qhbm_weighted_gram",
     "qhbm_reduced_density_scratch_bytes", "qhbm_reduced_density",
+    "qhbm_sample_parities", "qhbm_sample_parities_scratch_bytes", "qhbm_sample_parities_states",
 )
 
 
@@ -150,6 +151,10 @@ def load_library():
     lib.qhbm_weighted_gram.argtypes = [vp, i32, i32, vp, vp, vp, vp]
     lib.qhbm_reduced_density_scratch_bytes.argtypes = [i32, i32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_size_t)]
     lib.qhbm_reduced_density.argtypes = [vp, i32, i32, ctypes.c_uint64, vp, vp, vp, vp]
+    lib.qhbm_sample_parities.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, i32, i64, ctypes.c_uint64, vp, vp]
+    lib.qhbm_sample_parities_scratch_bytes.argtypes = [i32, i32, i64, ctypes.POINTER(ctypes.c_size_t)]
+    lib.qhbm_sample_parities_states.argtypes = [vp, i32, i32, vp, i32, i64, ctypes.c_uint64, ctypes.c_uint64,
+                                                ctypes.c_uint32, vp, vp, vp]
   except AttributeError:  # an older library given through QHBM_ENGINE_LIB (A/B runs): the probe is optional there
     pass
   _lib = lib
@@ -437,6 +442,51 @@ def reduced_density(states, keep_mask, weights=None):
                                                       scratch.data_ptr(), out.data_ptr(),
                                                       torch.cuda.current_stream().cuda_stream))
   return torch.view_as_complex(out)
+
+
+def _parity_masks(masks):
+  """The masks of a sample_parities call as a HOST uint64 array (the C entries validate them before they launch)."""
+  if torch.is_tensor(masks):
+    masks = masks.detach().cpu().numpy()
+  m = np.asarray(masks)
+  if m.ndim != 1 or m.size < 1:
+    raise ValueError("masks must be a non-empty 1-D sequence of integers")
+  if m.dtype.kind == "i" and (m < 0).any():
+    raise ValueError("masks must be non-negative")
+  return np.ascontiguousarray(m, dtype=np.uint64)
+
+
+def sample_parities_scratch_bytes(num_states, n_qubits, n_shots):
+  """Bytes of scratch one `qhbm_sample_parities_states` call needs (no device needed)."""
+  out = ctypes.c_size_t()
+  _check_global(load_library().qhbm_sample_parities_scratch_bytes(int(num_states), int(n_qubits), int(n_shots),
+                                                                  ctypes.byref(out)))
+  return int(out.value)
+
+
+def sample_parities_states(states, masks, n_shots, seed=0, first_row=0, program=0):
+  """int32 [M, T]: out[m, t] = sum over `n_shots` shots x drawn from |states[m]|^2 (not necessarily normalised) of
+  (-1)^popcount(x & masks[t]); bit k of a mask is qubit k, the k-th most significant bit of an amplitude index.  Shot j of
+  row m uses the uniform of qhbm_sample_counts with counter words (j, first_row + m, program): row m of a call equals a
+  one-state call with first_row = m, bit for bit (include/qhbm_engine.h qhbm_sample_parities_states).  complex128 states
+  are cast to complex64; the scratch is this call's own.  Not differentiable."""
+  if not (torch.is_tensor(states) and states.is_cuda and states.dim() == 2 and states.is_complex()):
+    raise EngineError("sample_parities_states needs complex CUDA states [M, 2^n]: the engine has no CPU fallback")
+  states = states.detach().to(torch.complex64).contiguous()
+  if states.data_ptr() % 16:
+    states = states.clone()
+  num, dim = (int(v) for v in states.shape)
+  n = dim.bit_length() - 1
+  if dim != (1 << n) or n < 1:
+    raise ValueError(f"states have {dim} amplitudes: not a power of two, or fewer than two")
+  m = _parity_masks(masks)
+  with torch.cuda.device(states.device):
+    scratch = torch.empty(sample_parities_scratch_bytes(num, n, n_shots) // 8, dtype=torch.float64, device=states.device)
+    out = torch.empty((num, len(m)), dtype=torch.int32, device=states.device)
+    _check_global(load_library().qhbm_sample_parities_states(
+        states.data_ptr(), num, n, m.ctypes.data, len(m), int(n_shots), int(seed) & (2**64 - 1), int(first_row),
+        int(program), scratch.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream))
+  return out
 
 
 class Engine:
@@ -945,6 +995,26 @@ class Engine:
           self._lib.qhbm_sample_counts(self._h, bits.data_ptr(), bits.shape[0], params.data_ptr(), len(sg),
                                        sg.ctypes.data, sv.ctypes.data, int(n_shots), int(seed) & (2**64 - 1),
                                        out.data_ptr(), self._stream()))
+    return out
+
+  def sample_parities(self, bits, params, masks, n_shots, seed=0, shift_gates=(-1,), shifts=(0.0,)):
+    """int32 [n_programs, batch, T]: sum over `n_shots` shots of (-1)^popcount(x & masks[t]) for every (shifted program,
+    state) pair, all programs in one launch set and at any register width: neither shots nor per-outcome counters are
+    stored (include/qhbm_engine.h qhbm_sample_parities).  Bit k of a mask is qubit k; the uniforms are those of
+    `sample_counts`."""
+    self.retained = None
+    bits, params = self._prep(bits, params)
+    sg = np.ascontiguousarray(shift_gates, dtype=np.int32)
+    sv = np.ascontiguousarray(shifts, dtype=np.float32)
+    if sg.shape != sv.shape or sg.ndim != 1:
+      raise ValueError("shift_gates and shifts must be 1-D and of equal length")
+    m = _parity_masks(masks)
+    out = torch.empty((len(sg), bits.shape[0], len(m)), dtype=torch.int32, device=self.device)
+    with torch.cuda.device(self.device):
+      self._check(
+          self._lib.qhbm_sample_parities(self._h, bits.data_ptr(), bits.shape[0], params.data_ptr(), len(sg),
+                                         sg.ctypes.data, sv.ctypes.data, m.ctypes.data, len(m), int(n_shots),
+                                         int(seed) & (2**64 - 1), out.data_ptr(), self._stream()))
     return out
 
   def program_vjps(self, bits, params, shift_gates, shifts, upstream, row_weights=None):

@@ -120,6 +120,65 @@ class StateVectorData(QuantumData):
     weights = self.weights.to(device=values.device, dtype=values.dtype)
     return torch.sum(weights * values.squeeze(-1))
 
+  def sampled_expectation(self, observable, num_shots, seed=None):
+    """The shot-noise estimate of sum_m w_m <phi_m| observable |phi_m> from `num_shots` computational-basis shots per
+    state and measurement basis, drawn and reduced on the device (`qhbm_sample_parities_states`).
+    `observable`: a PauliSum / PauliString (a scalar comes back) or a list of them ([n_ops]).  The strings are grouped by
+    their X/Y pattern as `SampledQuantumInference` groups them; a group's states are rotated once (X: H, Y: rx(pi / 2))
+    by `statevector_from_states`, Z-only groups are sampled as given.  Rows need not be normalised: a row's estimate is
+    scaled by its squared norm.  `seed` None draws a fresh one.  Not differentiable."""
+    import math  # pylint: disable=import-outside-toplevel
+    from qhbmlib_amd import _engine, ir  # pylint: disable=import-outside-toplevel
+    from qhbmlib_amd.inference import ebm  # pylint: disable=import-outside-toplevel
+    single = not isinstance(observable, (list, tuple))
+    ops = [ir.as_pauli_sum(op) for op in ([observable] if single else observable)]
+    num_shots = int(num_shots)
+    if num_shots < 1:
+      raise ValueError("num_shots must be positive")
+    qubits = self.qubits
+    if qubits is None:
+      qubits = sorted(set().union(*[op.qubits() for op in ops]))
+      if len(qubits) != self.num_qubits:
+        raise ValueError(f"the observable acts on {len(qubits)} qubits, the states live on {self.num_qubits}: "
+                         "give the data its `qubits`")
+    qindex = {q: i for i, q in enumerate(qubits)}
+    strings, mix = [], []
+    for t, op in enumerate(ops):
+      for term in op.terms:
+        if any(q not in qindex for q in term.paulis):
+          raise ValueError("the observable's qubits are not the data's")
+        strings.append(term)
+        mix.append((t, term.coefficient))
+    groups = {}
+    for k, st in enumerate(strings):
+      key = tuple(sorted((qindex[q], p) for q, p in st.paulis.items() if p in ("X", "Y")))
+      groups.setdefault(key, []).append(k)
+    states = self._device_states()
+    if not states.is_cuda:
+      raise _engine.EngineError("sampled_expectation needs an MI355X: the engine is HIP-only, no CPU fallback")
+    seed = int(ebm.fresh_seed() if seed is None else seed) & (2**63 - 1)
+    estimates = torch.ones((states.shape[0], len(strings)), dtype=torch.float64, device=states.device)
+    program = 0
+    for key, members in groups.items():
+      rotated = states
+      if key:
+        rot = ir.Circuit([ir.H(qubits[i]) if p == "X" else ir.rx(math.pi / 2)(qubits[i]) for i, p in key])
+        eng = _engine.Engine(states.device.index)
+        eng.set_circuit(self.num_qubits, rot.flat_gates(qubits, []), 0)
+        rotated = eng.statevector_from_states(states, torch.zeros(0))
+        del eng
+      masks = [sum(1 << qindex[q] for q in strings[k].paulis) for k in members]
+      for lo in range(0, len(masks), 1024):   # (the entry takes 1024 masks; every call its own random stream)
+        sums = _engine.sample_parities_states(rotated, masks[lo:lo + 1024], num_shots, seed, program=program)
+        estimates[:, members[lo:lo + 1024]] = sums.to(torch.float64) / float(num_shots)
+        program += 1
+    values = torch.zeros((states.shape[0], len(ops)), dtype=torch.float64, device=states.device)
+    for k, (t, c) in enumerate(mix):
+      values[:, t] += c * estimates[:, k]
+    norm2 = (states.real.to(torch.float64)**2 + states.imag.to(torch.float64)**2).sum(1)
+    out = torch.sum((self.weights.to(states.device) * norm2).unsqueeze(1) * values, dim=0)
+    return out[0] if single else out
+
   def metrics(self, model, **kwargs):
     """`inference.state_metrics(model, self, **kwargs)`: trace, purity, entropy, overlap, fidelity, cross entropy and
     relative entropy of this data against the QHBM `model`, matrix-free.  Not differentiable."""

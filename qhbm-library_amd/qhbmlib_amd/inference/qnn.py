@@ -532,7 +532,10 @@ class SampledQuantumInference(QuantumInference):
   values are averages over `expectation_samples` computational-basis shots drawn by the engine,
   derivatives use the parameter-shift rule on sampled estimates.  Estimates are taken from per-outcome
   shot COUNTS (`qhbm_sample_counts`: every shifted program of a backward pass in one launch set) up to
-  `MAX_COUNT_QUBITS` qubits, from materialised shots (`qhbm_sample`, one program per call) above."""
+  `MAX_COUNT_QUBITS` qubits, from materialised shots (`qhbm_sample`, one program per call) above.
+  `pauli_estimator="parities"` takes Pauli-string estimates from `qhbm_sample_parities` instead: per X/Y group one call
+  for all shifted programs and member strings, at every register width, which stores neither shots nor counters
+  (DESIGN.md 6k).  General (non-Pauli) Hamiltonians keep their route."""
 
   MAX_COUNT_QUBITS = 16   # 2^n counters per (program, state)
   # The counts of one engine call are [programs, states, 2^n] int32 and their frequencies the same again in float32:
@@ -550,8 +553,11 @@ class SampledQuantumInference(QuantumInference):
 
   def __init__(self, input_circuit: circuit.QuantumCircuit, expectation_samples: int,
                name: Union[None, str] = None, device: Union[None, int] = None,
-               initial_seed: Union[None, int] = None):
+               initial_seed: Union[None, int] = None, pauli_estimator: str = "outcomes"):
     super().__init__(input_circuit, name)
+    if pauli_estimator not in ("outcomes", "parities"):
+      raise ValueError(f'pauli_estimator must be "outcomes" or "parities", got {pauli_estimator!r}')
+    self._pauli_route = pauli_estimator
     self._expectation_samples = int(expectation_samples)
     self._device = device
     self._engines = {}
@@ -594,6 +600,8 @@ class SampledQuantumInference(QuantumInference):
     for k, st in enumerate(strings):
       key = tuple(sorted((qindex[q], p) for q, p in st.paulis.items() if p in ("X", "Y")))
       groups.setdefault(key, []).append(k)
+    if self._pauli_route == "parities":
+      return self._parity_estimator(qubits, names, base, qindex, groups, bits, values, strings), base
     use_counts = n <= self.MAX_COUNT_QUBITS
     outcomes = torch.arange(1 << n, dtype=torch.int64) if use_counts else None
     plans = []
@@ -632,6 +640,27 @@ class SampledQuantumInference(QuantumInference):
             out[q][:, members] = parity.mean(1).to(out.device)
       return out
     return estimator, base
+
+  def _parity_estimator(self, qubits, names, base, qindex, groups, bits, values, strings):
+    """The estimator of `_pauli_estimator` on `qhbm_sample_parities`: per X/Y group ONE engine call for all shifted
+    programs and all member strings, at any register width; the signed shot sums divided by the shots."""
+    plans = []
+    for key, members in groups.items():
+      rot = ir.Circuit([ir.H(qubits[i]) if p == "X" else ir.rx(math.pi / 2)(qubits[i]) for i, p in key])
+      eng = self._engine_for(qubits, base + rot.flat_gates(qubits, names), len(names))
+      masks = [sum(1 << qindex[q] for q in strings[k].paulis) for k in members]   # bit k = qubit k
+      plans.append((eng, members, masks))
+
+    def estimator(shift_gates=(-1,), shifts=(0.0,)):
+      shift_gates, shifts = list(shift_gates), list(shifts)
+      out = torch.ones((len(shift_gates), bits.shape[0], len(strings)), dtype=torch.float32, device=values.device)
+      for eng, members, masks in plans:
+        for lo in range(0, len(masks), 1024):                                       # (the entry takes 1024 masks)
+          sums = eng.sample_parities(bits, values, masks[lo:lo + 1024], self._expectation_samples, self._next_seed(),
+                                     shift_gates, shifts)                           # int32 [Q, U, members]
+          out[:, :, members[lo:lo + 1024]] = (sums.to(torch.float32) / float(self._expectation_samples)).to(out.device)
+      return out
+    return estimator
 
   def _expectation(self, circuits, symbol_names, symbol_values, observables):
     """qnn.py:228-264.  Pauli-sum observables and PauliMixin Hamiltonians are estimated term by
