@@ -281,8 +281,8 @@ int qhbm_statevector(qhbm_engine* h, const int8_t* d_bits, int U,
  * Each call is "another compute call": it drops the states of qhbm_expectation_retain, and the VJP replaces the rows
  * qhbm_state_gradients serves.
  *
- * OUT OF SCOPE from caller states: the parameter-shift method, the retain / vjp_retained pair, energy tables,
- * sampling and qhbm_program_vjps.
+ * OUT OF SCOPE from caller states: the parameter-shift method, the retain / vjp_retained pair, energy tables (a caller
+ * reaches them through qhbm_statevector_vjp_from_states below), sampling and qhbm_program_vjps.
  *
  *   qhbm_expectation_from_states       d_out[u, k] = <phi_u| C^dagger O_k C |phi_u>  (not divided by the norm)
  *   qhbm_expectation_vjp_from_states   the adjoint method only: d_grad [n_params] = sum_{u,k} d_upstream[u, k] *
@@ -298,6 +298,31 @@ int qhbm_expectation_vjp_from_states(qhbm_engine* h, const void* d_states, int U
 int qhbm_statevector_from_states(qhbm_engine* h, const void* d_states, int U, const float* d_params,
                                  void* d_out_states, void* stream);
 int qhbm_describe_schedule_from_states(qhbm_engine* h, char* buf, size_t buf_len);
+
+/* ---- Differentiating final states: the adjoint VJP from a caller's cotangent states ----
+ * Added WITHIN ABI version 5: purely additive, QHBM_ABI_VERSION stays 5.
+ *
+ * The contract is stated on the states qhbm_statevector_from_states returns: psi_u = C(params) phi_u, global phase
+ * included, not normalised.  For a real loss L and the cotangent g_u = dL/dRe psi_u + i dL/dIm psi_u (torch's
+ * convention for a complex tensor, so that dL = sum_u Re<g_u|dpsi_u>):
+ *   d_grad[p] = sum_u Re<g_u| d psi_u / d params[p]>                                   [n_params] float
+ * -- the backward sweep on lambda_u = 1/2 ||phi_u|| e^{-i theta} g_u, minus (d theta / d p) sum_u Im<g_u|psi_u> for the
+ * global phase theta(params) no kernel applies.  Any real function of the final states is differentiable through it.
+ *
+ *   d_states, d_cotangent  [U, 2^n_qubits] complex64 in the row order of qhbm_statevector, device, 16-byte aligned, only
+ *                          read, outside the engine's workspace (NULL, misaligned or aliasing: refused with a message)
+ *   d_out_states           NULL, or [U, 2^n_qubits] complex64 (16-byte aligned, overlapping neither input): receives exactly
+ *                          what qhbm_statevector_from_states would have written -- the same forward serves both outputs
+ *   d_grad                 [n_params] float, overwritten; U == 0 zero-fills it
+ * No observables are needed.  The call runs on the dense-start plans, honours qhbm_set_gradient_mask (masked entries are
+ * exactly 0) and chunk_states; no floating-point atomics: two calls give identical bits, whatever chunk_states.  It drops
+ * the states of qhbm_expectation_retain, and qhbm_state_gradients is refused after it (its rows would lack the phase term).
+ * There is no entry from bitstrings -- the basis-state plans prune leading diagonal gates and idle qubits, which is valid
+ * for expectation values and wrong for a phase-sensitive cotangent: basis starts go through this entry as one-hot states.
+ * OUT OF SCOPE: the gradient with respect to d_states, the parameter-shift method. */
+int qhbm_statevector_vjp_from_states(qhbm_engine* h, const void* d_states, int U, const float* d_params,
+                                     const void* d_cotangent, void* d_out_states /* may be NULL */, float* d_grad,
+                                     void* stream);
 
 /* ---- Evolving caller-supplied states: matrix-free thermal targets ----
  * Added WITHIN ABI version 5: purely additive, QHBM_ABI_VERSION stays 5.

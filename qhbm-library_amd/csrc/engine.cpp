@@ -90,6 +90,7 @@ struct PlanSet {
   DevBuf<float> slot_factor;
   DevBuf<ShiftPhase> shift_phases;
   int n_shift_phases = 0;
+  DevBuf<float> phase_slope;
   bool shift_ready = false;  // (the shift tables and coefficient copies follow the basis-state forward plan: parked here
   size_t coef_batch_programs = 0;  // while the dense-start set is in, so that building it does not reset them)
 };
@@ -185,6 +186,9 @@ struct qhbm_engine {
   DevBuf<float> state_grad, slot_factor, vals_tmp, upstream_tmp, phase_cs;
   DevBuf<ShiftPhase> shift_phases;  // gates with a cirq global_shift (qhbm_statevector restores their phases)
   int n_shift_phases = 0;
+  // d theta / d p of the global phase theta those two restore (pi times global_phase_kernel's sum: every exponent is linear in
+  // one parameter, so the slope is a constant of the model), zero where the gradient mask switches p off [n_params]
+  DevBuf<float> phase_slope;
   // batches of shifted programs: per-program coefficient buffers, ONE set of shift tables (upload_shift_tables), accumulators
   DevBuf<float> coef_batch, shift_vals, shift_weight, vals_batch;
   DevBuf<int> shift_gates, shift_param;
@@ -226,6 +230,8 @@ struct qhbm_engine {
   DevBuf<double> import_parts, import_norm2;  // import_states.hip: scratch, ||phi_u||^2 [U]
   DevBuf<float> import_up;                    // upstream rows times ||phi_u||^2
   DevBuf<int8_t> import_bits;                 // zeros: the bitstrings the pass kernels are handed (no pass reads them)
+  // a caller's cotangent as lambda (qhbm_statevector_vjp_from_states; cotangent.hip): per-slice partials, <g_u|chi_u> [U, 2]
+  DevBuf<double> cot_parts, cot_dot;
   // Chebyshev evolution of caller states (qhbm_evolve_states, qhbm_apply_observables; thermal.hip)
   int opt_evolve_step = 4;                    // bound on the argument x = delta R of one step ("evolve_step_argument")
   std::vector<double> evo_host_wr;            // w_k / R (or w_k) of the call in flight: the source of an asynchronous copy
@@ -262,7 +268,7 @@ size_t own_bytes(const qhbm_engine* h) {
          buf_bytes(h->vals64) + buf_bytes(h->block_cum) + buf_bytes(h->par_tables) + buf_bytes(h->par_masks) + buf_bytes(h->coef_batch) + buf_bytes(h->vals_batch) +
          buf_bytes(h->value_part) + buf_bytes(h->probe_out) + buf_bytes(h->probe_sink) + buf_bytes(h->upstream_tmp) + buf_bytes(h->vals_tmp) + buf_bytes(h->prog_acc) +
          buf_bytes(h->shift_vals) + buf_bytes(h->shift_weight) + buf_bytes(h->shift_gates) + buf_bytes(h->shift_param) + buf_bytes(h->shift_dst) +
-         buf_bytes(h->slot_factor) + buf_bytes(h->phase_cs) + buf_bytes(h->shift_phases) + buf_bytes(h->terms) +
+         buf_bytes(h->slot_factor) + buf_bytes(h->phase_cs) + buf_bytes(h->shift_phases) + buf_bytes(h->phase_slope) + buf_bytes(h->terms) +
          buf_bytes(h->global_terms) + buf_bytes(h->obs_groups) + buf_bytes(h->far[0].terms) + buf_bytes(h->far[0].groups) +
          buf_bytes(h->far[1].terms) + buf_bytes(h->far[1].groups) + buf_bytes(h->far[2].terms) + buf_bytes(h->far[2].groups) + buf_bytes(h->obs_bterms) + buf_bytes(h->obs_bgroups) + buf_bytes(h->op_scale) + buf_bytes(h->op_inv_scale) +
          buf_bytes(h->param_slot_begin) + buf_bytes(h->param_slots) + buf_bytes(h->pv_bits) + buf_bytes(h->pv_upstream) +
@@ -274,7 +280,7 @@ size_t own_bytes(const qhbm_engine* h) {
          }() + [&] {  // the other plan set and the import's buffers (nothing before the first from-states call)
            const PlanSet& o = h->dense;
            size_t b = plan_bytes(o.fwd) + plan_bytes(o.adj) + buf_bytes(o.global_terms) + buf_bytes(o.param_slot_begin) +
-                      buf_bytes(o.param_slots) + buf_bytes(o.slot_factor) + buf_bytes(o.shift_phases) + buf_bytes(h->import_parts) +
+                      buf_bytes(o.param_slots) + buf_bytes(o.slot_factor) + buf_bytes(o.shift_phases) + buf_bytes(o.phase_slope) + buf_bytes(h->cot_parts) + buf_bytes(h->cot_dot) + buf_bytes(h->import_parts) +
                       buf_bytes(h->import_norm2) + buf_bytes(h->import_up) + buf_bytes(h->import_bits) + buf_bytes(h->evo_wr) +
                       buf_bytes(h->evo_scale) + buf_bytes(h->evo_parts) + buf_bytes(h->evo_log_norm) + buf_bytes(h->evo_up1) +
                       buf_bytes(h->evo_up2) + buf_bytes(h->kry_parts) + buf_bytes(h->kry_norm_parts) + buf_bytes(h->kry_coef);
@@ -313,6 +319,7 @@ void swap_plan_sets(qhbm_engine* h) {
   swap_buf(h->slot_factor, o.slot_factor);
   swap_buf(h->shift_phases, o.shift_phases);
   std::swap(h->n_shift_phases, o.n_shift_phases);
+  swap_buf(h->phase_slope, o.phase_slope);
   std::swap(h->shift_ready, o.shift_ready);
   std::swap(h->coef_batch_programs, o.coef_batch_programs);
   h->dense_active = !h->dense_active;
@@ -865,6 +872,17 @@ int upload_model(qhbm_engine* h) {
       sp.push_back(ShiftPhase{-1, 0.f, 1.f, float(h->fwd.plan.const_phase)});
     HIPCHK(h->shift_phases.upload(sp));
     h->n_shift_phases = int(sp.size());
+    // the slope of that phase (kernels.hip global_phase_kernel, term by term): t/2 per X**t and Y**t job -- the X branch
+    // times jb.mult; its reduction mod 2 has no slope --, shift * t per entry above
+    std::vector<double> slope(size_t(h->model.n_params), 0.0);
+    for (const CoefJob& jb : h->fwd.plan.jobs)
+      if ((jb.mop == MOP_X || jb.mop == MOP_Y) && jb.param_idx >= 0)
+        slope[size_t(jb.param_idx)] += 0.5 * double(jb.scalar) * (jb.mop == MOP_X ? double(jb.mult) : 1.0);
+    for (const ShiftPhase& p : sp)
+      if (p.param_idx >= 0) slope[size_t(p.param_idx)] += double(p.shift) * double(p.scalar);
+    std::vector<float> slope_f(slope.size());
+    for (size_t p = 0; p < slope.size(); ++p) slope_f[p] = h->model.frozen(int(p)) ? 0.f : float(M_PI * slope[p]);
+    HIPCHK(h->phase_slope.upload(slope_f));
   }
   h->model_uploaded = true;
   return 0;
@@ -1984,6 +2002,67 @@ int qhbm_statevector_from_states(qhbm_engine* h, const void* d_states, int U, co
   HIPCHK(launch_global_phase(d.jobs.p, int(d.plan.jobs.size()), h->shift_phases.p, h->n_shift_phases, d_params,
                              h->phase_cs.p, s));
   HIPCHK(launch_scale_states(static_cast<float2*>(d_out_states), size_t(U) << h->model.n, h->phase_cs.p, s));
+  return 0;
+}
+
+int qhbm_statevector_vjp_from_states(qhbm_engine* h, const void* d_states, int U, const float* d_params,
+                                     const void* d_cotangent, void* d_out_states, float* d_grad, void* stream) {
+  if (int rc = check_states_call(h, d_states, U, false)) return rc;
+  if (!d_grad) return fail(h, "d_grad is NULL");
+  if (d_out_states)
+    if (int rc = check_pointer(h, d_out_states, 16, "d_out_states")) return rc;
+  if (U > 0) {
+    const size_t bytes = size_t(U) * (size_t(8) << h->model.n);
+    if (int rc = check_pointer(h, d_cotangent, 16, "d_cotangent")) return rc;
+    if (aliases_workspace(h, d_cotangent, bytes)) return fail(h, "d_cotangent lies inside the engine's workspace");
+    if (d_out_states && (ranges_overlap(d_out_states, bytes, d_cotangent, bytes) || ranges_overlap(d_out_states, bytes, d_states, bytes)))
+      return fail(h, "d_out_states overlaps d_states or d_cotangent");
+  }
+  DenseScope scope(h);
+  if (int rc = upload_model(h)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int P = h->model.n_params;
+  h->retained_U = 0;
+  h->state_grad_U = 0;  // (qhbm_state_gradients is refused after this call: the rows lack the phase term)
+  if (U == 0) {
+    if (P) HIPCHK(launch_zero_fill(d_grad, size_t(P) * sizeof(float), s));
+    return 0;
+  }
+  DevicePlan& f = h->fwd;
+  DevicePlan& b = h->adj;
+  if (int rc = begin_import(h, d_states, U, nullptr, s)) return rc;
+  if (int rc = prepare_coefs(h, f, d_params, -1, 0.0, s)) return rc;
+  if (int rc = prepare_coefs(h, b, d_params, -1, 0.0, s)) return rc;
+  const uint32_t n_slots = uint32_t(b.plan.slot_gate.size());
+  HIPCHK(h->state_grad.reserve(size_t(U) * std::max<uint32_t>(n_slots, 1)));
+  HIPCHK(launch_zero_fill(h->state_grad.p, size_t(U) * std::max<uint32_t>(n_slots, 1) * sizeof(float), s));
+  const uint32_t cs = adjoint_chunk_states(h, U);
+  if (int rc = ensure_state_buffers(h, cs, true)) return rc;
+  // (the buffers may have moved: the checks again, on the workspace the sweep will use)
+  if (aliases_workspace(h, d_cotangent, size_t(U) * (size_t(8) << h->model.n))) return fail(h, "d_cotangent lies inside the engine's workspace");
+  const uint32_t n = uint32_t(h->model.n), n_eff = uint32_t(f.plan.n_eff);
+  HIPCHK(h->cot_parts.reserve(cotangent_parts_count(n, cs)));
+  HIPCHK(h->cot_dot.reserve(size_t(U) * 2));
+  HIPCHK(h->phase_cs.reserve(2));  // the global phase the kernels leave out, as qhbm_statevector restores it
+  HIPCHK(launch_global_phase(f.jobs.p, int(f.plan.jobs.size()), h->shift_phases.p, h->n_shift_phases, d_params, h->phase_cs.p, s));
+  const float2* cot = static_cast<const float2*>(d_cotangent);
+  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += cs) {
+    const uint32_t c = std::min<uint32_t>(cs, uint32_t(U) - s0);
+    if (int rc = run_forward_chunk(h, h->import_bits.p, s0, c, true, s, true)) return rc;
+    if (d_out_states)  // the export of qhbm_statevector_from_states, before the backward sweep un-applies psi in place
+      HIPCHK(launch_scale_copy_states(h->psi.p, n_eff, static_cast<float2*>(d_out_states) + (size_t(s0) << n), n, n, c, nullptr,
+                                      h->import_norm2.p + s0, s));
+    hipEvent_t* ev = timer_begin(h, 2, s);  // (profile_events: the cotangent import counts as the lambda launch)
+    HIPCHK(launch_cotangent_import(cot, h->psi.p, n, n_eff, c, s0, h->import_norm2.p, h->phase_cs.p, h->lam.p, h->cot_parts.p,
+                                   h->cot_dot.p, s));
+    timer_end(ev, s);
+    if (int rc = run_adjoint_chunk(h, h->import_bits.p, s0, c, s)) return rc;
+  }
+  if (d_out_states) HIPCHK(launch_scale_states(static_cast<float2*>(d_out_states), size_t(U) << n, h->phase_cs.p, s));
+  HIPCHK(launch_reduce_grad(h->state_grad.p, uint32_t(U), n_slots, h->param_slot_begin.p, h->param_slots.p, h->slot_factor.p,
+                            d_grad, P, 0, s));
+  HIPCHK(launch_cotangent_phase_grad(h->cot_dot.p, h->import_norm2.p, uint32_t(U), h->phase_cs.p, h->phase_slope.p, d_grad,
+                                     uint32_t(P), s));
   return 0;
 }
 

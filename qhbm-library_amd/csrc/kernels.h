@@ -1,5 +1,5 @@
 // kernels.h -- launch entry points of the kernel objects (host side): kernels.hip (the pass kernels, with gwg.hip and
-// parity_table.hip), observable.hip (with energy_table.hip) and states.hip (import_states.hip, thermal.hip, krylov.hip,
+// parity_table.hip), observable.hip (with energy_table.hip and cotangent.hip) and states.hip (import_states.hip, thermal.hip, krylov.hip,
 // gram.hip, reduced.hip).  A .hip file reaches another one's kernels through these declarations only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -332,5 +332,19 @@ hipError_t launch_weighted_gram(const float2* states, uint32_t M, uint32_t n, co
 // `parts`: rdm_plan(n, keep_mask, M).scratch_bytes bytes, which may hold anything.
 hipError_t launch_reduced_density(const float2* states, uint32_t M, uint32_t n, uint64_t keep_mask, const double* weights,
                                   double* parts, double* rho, hipStream_t stream);
+
+// ---- a caller's cotangent of the final states as the backward sweep's lambda (cotangent.hip) ----
+// Doubles of scratch (`parts`) one chunk of c states of n qubits needs.
+size_t cotangent_parts_count(uint32_t n, uint32_t c);
+// Cotangent rows s0 .. s0 + c of `cot` ([., 2^n] complex64, read only, 16-byte aligned) against the chunk's final states
+// chi (pitch 2^n_eff): lam element i = 1/2 sqrt(norm2[s0 + i]) (phase_cs[0] - i phase_cs[1]) cot at the same pitch, zeros in
+// the padding; dot[2 (s0 + i)], [.. + 1] = Re, Im <cot|chi>, fp64 in a fixed order.  `parts` may hold anything.
+hipError_t launch_cotangent_import(const float2* cot, const float2* chi, uint32_t n, uint32_t n_eff, uint32_t c, uint32_t s0,
+                                   const double* norm2, const float* phase_cs, float2* lam, double* parts, double* dot,
+                                   hipStream_t stream);
+// grad[p] -= slope[p] sum_u sqrt(norm2[u]) Im((phase_cs[0] + i phase_cs[1]) dot_u), u in order, fp64; entries with slope 0
+// keep their bits.
+hipError_t launch_cotangent_phase_grad(const double* dot, const double* norm2, uint32_t U, const float* phase_cs, const float* slope,
+                                       float* grad, uint32_t n_params, hipStream_t stream);
 
 }  // namespace qhbm

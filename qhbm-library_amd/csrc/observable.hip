@@ -691,3 +691,7 @@ hipError_t launch_observable_blocks(int mode, int block_bits, const float2* psi,
 // The energy-table kernels (a diagonal observable given as a table of 2^n energies) are a translation unit of their own
 // in the source tree and part of this object.
 #include "energy_table.hip"
+
+// The third producer of the backward sweep's lambda, a caller's cotangent of the final states, likewise (it shares
+// state_sweep.h with the state-vector kernels and no name with any other .hip file).
+#include "cotangent.hip"

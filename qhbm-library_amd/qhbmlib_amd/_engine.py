@@ -45,7 +45,7 @@ ABI_SYMBOLS = (
     "qhbm_table_expectation", "qhbm_table_expectation_retain", "qhbm_table_expectation_vjp",
     "qhbm_table_expectation_vjp_retained",
     "qhbm_expectation_from_states", "qhbm_expectation_vjp_from_states", "qhbm_statevector_from_states",
-    "qhbm_describe_schedule_from_states",
+    "qhbm_describe_schedule_from_states", "qhbm_statevector_vjp_from_states",
     "qhbm_apply_observables", "qhbm_evolve_states", "qhbm_describe_evolution", "qhbm_random_states",
     "qhbm_krylov_basis", "qhbm_krylov_combine", "qhbm_describe_krylov",
     "qhbm_gram_scratch_bytes", "qhbm_weighted_gram",
@@ -140,6 +140,7 @@ def load_library():
     lib.qhbm_expectation_vjp_from_states.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     lib.qhbm_statevector_from_states.argtypes = [vp, vp, i32, vp, vp, vp]
     lib.qhbm_describe_schedule_from_states.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t]
+    lib.qhbm_statevector_vjp_from_states.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     lib.qhbm_apply_observables.argtypes = [vp, vp, i32, vp, vp, vp]
     lib.qhbm_evolve_states.argtypes = [vp, vp, i32, vp, ctypes.c_double, i32, vp, vp]
     lib.qhbm_describe_evolution.argtypes = [vp, vp, ctypes.c_double, i32, ctypes.c_char_p, ctypes.c_size_t]
@@ -887,6 +888,27 @@ class Engine:
       self._check(self._lib.qhbm_statevector_from_states(self._h, states.data_ptr(), states.shape[0], params.data_ptr(),
                                                          out.data_ptr(), self._stream()))
     return out
+
+  def statevector_vjp_from_states(self, states, params, cotangent, want_states=False):
+    """The adjoint VJP of the final states psi = `statevector_from_states(states, params)`: grad [n_params] =
+    sum_u Re<g_u| d psi_u / d params> for the cotangent g [batch, 2^n] (dL/dRe psi + i dL/dIm psi of a real loss L, torch's
+    convention; complex128 is cast).  `want_states`: (psi, grad), psi from the same forward.  No observables needed; the
+    gradient mask applies; `state_gradients` is refused after this call."""
+    states, params = self._prep_states(states, params)
+    cotangent = torch.as_tensor(cotangent)
+    if not cotangent.is_complex() or tuple(cotangent.shape) != tuple(states.shape):
+      raise ValueError(f"cotangent must be a complex tensor of shape {tuple(states.shape)}")
+    cotangent = cotangent.to(device=self.device, dtype=torch.complex64).contiguous()
+    if cotangent.data_ptr() % 16:
+      cotangent = cotangent.clone()
+    out = torch.empty_like(states) if want_states else None
+    grad = torch.zeros((self.n_params,), dtype=torch.float32, device=self.device)
+    self.retained = None
+    with torch.cuda.device(self.device):
+      self._check(self._lib.qhbm_statevector_vjp_from_states(
+          self._h, states.data_ptr(), states.shape[0], params.data_ptr(), cotangent.data_ptr(),
+          None if out is None else out.data_ptr(), grad.data_ptr(), self._stream()))
+    return (out, grad) if want_states else grad
 
   # ---- evolving caller-supplied states under H = sum_k w_k O_k of the installed observables ----
   def _weights(self, weights):

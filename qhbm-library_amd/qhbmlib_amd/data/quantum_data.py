@@ -34,9 +34,14 @@ class StateVectorData(QuantumData):
   `expectation(hamiltonian)` = sum_m w_m <phi_m| K |phi_m> runs in the HIP engine from the states themselves
   (`AnalyticQuantumInference.expectation_from_states` over an empty circuit) and is differentiable with respect to
   the Hamiltonian's variables, so `qmhl(StateVectorData(...), qhbm)` trains a QHBM on data that is no QHBM: the
-  eigen-ensemble of a density matrix, ground states, another simulator's output."""
+  eigen-ensemble of a density matrix, ground states, another simulator's output.
 
-  def __init__(self, states, weights=None, qubits=None):
+  `energy_tables` ("off", "general" or "all"; also an attribute that may be set later) is handed to that inference:
+  "off" (default) takes Hamiltonians with a Pauli-form energy only and raises TypeError for any other, "general" measures
+  an energy that is no `PauliMixin` -- an MLP on the bits -- through its table on the final states, so that `qmhl` fits
+  such a model to state-vector data too (`AnalyticQuantumInference.expectation_from_states`)."""
+
+  def __init__(self, states, weights=None, qubits=None, energy_tables="off"):
     states = torch.as_tensor(states)
     if not states.is_complex() or states.dim() != 2 or states.shape[0] < 1:
       raise ValueError(f"states must be a complex tensor of shape [M, 2^n], got {states.dtype} {tuple(states.shape)}")
@@ -54,11 +59,12 @@ class StateVectorData(QuantumData):
     self.weights = weights.detach()
     self.qubits = None if qubits is None else sorted(qubits)
     self.num_qubits = n
+    self.energy_tables = energy_tables
     self._inference = None
     self._on_device = None
 
   @classmethod
-  def from_density_matrix(cls, sigma, rtol=1e-10, qubits=None):
+  def from_density_matrix(cls, sigma, rtol=1e-10, qubits=None, energy_tables="off"):
     """The eigen-ensemble of a density matrix: `torch.linalg.eigh` in float64 / complex128, eigenvalues below
     `rtol` * (the largest) dropped, the kept eigenvalues as weights of their eigenvectors."""
     sigma = torch.as_tensor(sigma)
@@ -68,7 +74,7 @@ class StateVectorData(QuantumData):
     evals, evecs = torch.linalg.eigh(0.5 * (sigma + sigma.conj().transpose(0, 1)))
     keep = evals > rtol * evals.max()
     states = evecs[:, keep].transpose(0, 1).to(torch.complex128)
-    return cls(states, evals[keep], qubits)
+    return cls(states, evals[keep], qubits, energy_tables)
 
   @classmethod
   def thermal(cls, operators, beta, **kwargs):
@@ -104,6 +110,9 @@ class StateVectorData(QuantumData):
       # (an empty circuit on the data's qubits: no bitstring is ever injected, so the bit-order flag chooses nothing)
       empty = circuit.QuantumCircuit(ir.Circuit(), self.qubits, [], [], [], "state_vector_data", tfq_compat_bit_order=False)
       self._inference = qnn.AnalyticQuantumInference(empty)
+    if self.energy_tables not in self._inference.ENERGY_TABLES:
+      raise ValueError(f"energy_tables must be one of {self._inference.ENERGY_TABLES}, got {self.energy_tables!r}")
+    self._inference.energy_tables = self.energy_tables
     return self._inference
 
   def _device_states(self):
@@ -114,7 +123,8 @@ class StateVectorData(QuantumData):
     return self._on_device
 
   def expectation(self, observable):
-    """sum_m w_m <phi_m| observable |phi_m> as a scalar; `observable` is a Hamiltonian with a Pauli-form energy."""
+    """sum_m w_m <phi_m| observable |phi_m> as a scalar; `observable` is a Hamiltonian with a Pauli-form energy, or
+    with any energy that has a table when `energy_tables` is "general"."""
     q_inference = self._inference_for(observable.circuit.qubits)
     values = q_inference.expectation_from_states(self._device_states(), observable)  # [M, 1]
     weights = self.weights.to(device=values.device, dtype=values.dtype)

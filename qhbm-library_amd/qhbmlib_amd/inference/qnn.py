@@ -109,6 +109,29 @@ class _StatesExpectationFunction(torch.autograd.Function):
     return grad.to(symbol_values.device), None, None, None
 
 
+class _FinalStatesFunction(torch.autograd.Function):
+  """psi[M, 2^n] = C |phi_m> for caller-supplied states (qhbm_statevector_from_states), global phase included;
+  backward = the adjoint VJP from the caller's cotangent states (qhbm_statevector_vjp_from_states): any
+  real function of the final states is differentiable with respect to the circuit's symbols.  No gradient reaches
+  `states`."""
+
+  @staticmethod
+  def forward(ctx, symbol_values, engine, states, grad_mask=None):
+    ctx.engine, ctx.states = engine, states
+    ctx.grad_mask = None if grad_mask is None or all(grad_mask) else tuple(bool(f) for f in grad_mask)
+    ctx.save_for_backward(symbol_values)
+    return engine.statevector_from_states(states, symbol_values.detach())
+
+  @staticmethod
+  def backward(ctx, cotangent):
+    (symbol_values,) = ctx.saved_tensors
+    eng = ctx.engine
+    eng.set_gradient_mask(ctx.grad_mask)  # (a no-op unless another call on this engine set another one)
+    # (torch hands dL/dRe psi + i dL/dIm psi, the entry's convention; a complex128 cotangent is cast)
+    grad = eng.statevector_vjp_from_states(ctx.states, symbol_values.detach(), cotangent.to(torch.complex64).contiguous())
+    return grad.to(symbol_values.device), None, None, None
+
+
 class _TableExpectationFunction(torch.autograd.Function):
   """values[U, 1] = <x_u| C^dagger diag(table) C |x_u> (qhbm_table_expectation); backward = the table VJP: lambda =
   upstream * table * psi, the adjoint sweep, and d/d table[y] = sum_u upstream_u |psi_u[y]|^2 -- autograd carries the
@@ -306,7 +329,9 @@ class AnalyticQuantumInference(QuantumInference):
   circuit's qubits -- one streaming pass over the final states (`qhbm_table_expectation`), gradients by the adjoint
   sweep into the circuits and through the table into the energy's variables.  "all": every Hamiltonian goes through
   its table (one engine call whatever the number of Pauli shards).  Tables need n <= `max_table_qubits` (default 24: a
-  64-MiB table, 16 M energy rows), the adjoint gradient method, and no process group.
+  64-MiB table, 16 M energy rows), the adjoint gradient method, and no process group.  From caller-supplied states
+  (`expectation_from_states`) the same option measures the table on the differentiable final states
+  (`final_states_from_states`) instead of the table kernel.
   `parity_tables`: how the table of a `PauliMixin` energy routed through its table is built.  "terms" (default): the
   energy evaluated on all 2^n bitstrings; "transform": a Walsh-Hadamard transform of its coefficients
   (`energy_utils.energy_table(method="transform")`), whose cost does not depend on the number of terms.
@@ -451,12 +476,20 @@ class AnalyticQuantumInference(QuantumInference):
     `observables` as in `expectation`: a list of PauliSums, or a Hamiltonian with a Pauli-form energy (U^dagger is
     appended, the shards are measured, `operator_expectation` is applied).  Differentiable with respect to the
     variables of this inference's circuit and of the Hamiltonian's circuit and energy (adjoint VJP in the engine),
-    not with respect to `states`."""
+    not with respect to `states`.
+
+    With `energy_tables` "general" (or "all") a Hamiltonian whose energy is no `PauliMixin` (or every Hamiltonian) is
+    measured through its table instead: values[m] = sum_y E[y] |a[m, y]|^2 on a = `final_states_from_states` of the
+    total circuit, under the same `max_table_qubits` refusal as `expectation`; autograd carries the gradient through
+    the table into the energy's variables and through the final states into the circuits.  With "off" such an energy
+    raises TypeError as before."""
     states = torch.as_tensor(states)
     if states.requires_grad:
       raise ValueError("expectation_from_states is not differentiable with respect to `states`: pass states.detach()")
     if self._group() is not None:
       raise ValueError("expectation_from_states is not sharded yet: use an inference without a process_group")
+    if self._table_route(observables):
+      return self._table_expectation_from_states(states, observables)
     if isinstance(observables, hamiltonian.Hamiltonian):
       if not isinstance(observables.energy, energy.PauliMixin):
         raise TypeError("General Hamiltonians not accepted.  "
@@ -486,6 +519,69 @@ class AnalyticQuantumInference(QuantumInference):
       parts.append(_StatesExpectationFunction.apply(values, eng, states, grad_mask))
     expectations = parts[0] if len(parts) == 1 else torch.cat(parts, 1)
     return post_process(expectations)
+
+  def _final_states_of(self, total_circuit, states, what):
+    """[M, 2^n] complex64 = total_circuit |phi_m>, an autograd node over the circuit's symbols (`_FinalStatesFunction`)."""
+    states = torch.as_tensor(states)
+    if states.requires_grad:
+      raise ValueError(f"{what} is not differentiable with respect to `states`: pass states.detach()")
+    if self._group() is not None:
+      raise ValueError(f"{what} is not sharded yet: use an inference without a process_group")
+    qubits = total_circuit.qubits
+    if not states.is_complex() or states.dim() != 2 or states.shape[1] != (1 << len(qubits)):
+      raise ValueError(f"states must be a complex tensor of shape [M, {1 << len(qubits)}] "
+                       f"({len(qubits)} qubits), got {states.dtype} {tuple(states.shape)}")
+    values, flags = total_circuit.symbol_values_and_flags()
+    symbol_names = total_circuit.symbol_names
+    grad_mask = flags if values.requires_grad and len(flags) == len(symbol_names) else None
+    flat_gates = total_circuit.pqc.flat_gates(qubits, list(symbol_names))
+    eng = self._engine_for(len(qubits), flat_gates, len(symbol_names), [])  # (no observables: the table route's engine)
+    states = states.detach().to(device=eng.device, dtype=torch.complex64).contiguous()
+    return _FinalStatesFunction.apply(values.to(torch.float32), eng, states, grad_mask)
+
+  def final_states_from_states(self, states: torch.Tensor):
+    """[M, 2^n] complex64: C |phi_m> for `states` [M, 2^n] complex64 (complex128 is cast) in the row order of
+    `qnn_utils.unitary`, cirq's global phase included, not normalised.  Differentiable with respect to the variables of
+    this inference's circuit -- any real function of the result trains them (adjoint VJP from the cotangent states in
+    the engine) -- and not with respect to `states`.  One process; `states`, the result and its cotangent
+    are resident together."""
+    return self._final_states_of(self.circuit, states, "final_states_from_states")
+
+  def final_states(self, initial_states: torch.Tensor):
+    """[U, 2^n] complex64: C |x_u> for bitstrings `initial_states` [U, n], rows in input order; what `Engine.statevector`
+    returns for the same bits, as an autograd node (`final_states_from_states` on one-hot rows built on the device)."""
+    if self._group() is not None:
+      raise ValueError("final_states is not sharded yet: use an inference without a process_group")
+    bits = _engine_bits(self.circuit, torch.as_tensor(initial_states))
+    n = len(self.circuit.qubits)
+    if bits.dim() != 2 or bits.shape[1] != n:
+      raise ValueError(f"initial_states must have shape [U, {n}], got {tuple(bits.shape)}")
+    if not torch.cuda.is_available():
+      raise _engine.EngineError("final_states needs an MI355X: the engine is HIP-only and has no CPU fallback")
+    device = torch.device("cuda", torch.cuda.current_device() if self._device is None else self._device)
+    place = torch.tensor([1 << (n - 1 - q) for q in range(n)], dtype=torch.int64, device=device)  # qubit 0: most significant
+    index = (bits.to(device=device, dtype=torch.int64) * place).sum(1)
+    one_hot = torch.zeros((bits.shape[0], 1 << n), dtype=torch.complex64, device=device)
+    one_hot[torch.arange(bits.shape[0], device=device), index] = 1.0
+    return self._final_states_of(self.circuit, one_hot, "final_states")
+
+  def _table_expectation_from_states(self, states, observables):
+    """[M, 1] of a Hamiltonian measured through its energy table on the final states of caller-supplied states."""
+    total_circuit = self.circuit + observables.circuit_dagger
+    n = len(total_circuit.qubits)
+    if n > self.max_table_qubits:
+      raise ValueError(f"energy_tables={self.energy_tables!r}: the total circuit has {n} qubits, above "
+                       f"max_table_qubits={self.max_table_qubits} (a table has 2^n entries)")
+    if self.gradient_method != _engine.GRAD_ADJOINT:
+      raise ValueError(f"energy_tables={self.energy_tables!r} takes the adjoint gradient only, not the "
+                       "parameter-shift rule")
+    amplitudes = self._final_states_of(total_circuit, states, "expectation_from_states")
+    by_transform = self.parity_tables == "transform" and isinstance(observables.energy, energy.PauliMixin)
+    table = energy_utils.energy_table(observables.energy, n, self.max_table_qubits,
+                                      method="transform" if by_transform else "terms")
+    prob = amplitudes.real.to(torch.float64)**2 + amplitudes.imag.to(torch.float64)**2
+    values = (prob * table.to(device=prob.device, dtype=torch.float64)).sum(1)
+    return values.to(torch.float32).unsqueeze(-1)
 
 
 class _ParameterShiftSurrogate(torch.autograd.Function):
