@@ -457,6 +457,38 @@ int qhbm_reduced_density_scratch_bytes(int M, int n_qubits, uint64_t keep_mask, 
 int qhbm_reduced_density(const void* d_states, int M, int n_qubits, uint64_t keep_mask, const double* d_weights,
                          void* d_scratch, double* d_rho, void* stream);
 
+/* ---- A dense operator on k arbitrary qubits of every state: the VJP of the reduced density matrix ----
+ * Added WITHIN ABI version 5: purely additive, QHBM_ABI_VERSION stays 5.
+ *
+ *   out_m = scale_m (A (x) 1_env) phi_m,     dots_m = <phi_m|(A (x) 1_env)|phi_m>   (taken before scaling)
+ * keep_mask, the row order of A and the limits are those of qhbm_reduced_density: A acts on the kept qubits read
+ * big-endian in ascending qubit order, 1 <= k <= min(n_qubits, 10), n_qubits <= 31, M <= 65536, k = n_qubits allowed.  For a
+ * real loss L of rho_A with cotangent Gamma = dL/dRe rho + i dL/dIm rho, A = Gamma + Gamma^H and scale = the weights give
+ * the cotangent of the states in `out` and 1/2 Re dots is the cotangent of the weights.
+ *
+ *   qhbm_subsystem_apply     d_states, d_out [M, 2^n_qubits] complex64, interleaved, 16-byte aligned, not overlapping;
+ *                            d_operator [2^k, 2^k] complex64, row-major, 8-byte aligned; d_scale [M] float64 or NULL for
+ *                            all ones; d_dots [M, 2] float64 (re, im) or NULL; all on the device.  No engine: the current
+ *                            device.  Asynchronous on `stream`; allocates nothing, synchronises nothing.  d_scratch:
+ *                            qhbm_subsystem_apply_scratch_bytes bytes, 8-byte aligned, which may hold anything.
+ *                            Arithmetic: an output is an f32 fused-multiply-add chain over a' ascending of the real
+ *                            embedding Re = A_r phi_r - A_i phi_i, Im = A_r phi_i + A_i phi_r (k <= 3 vector code, k >= 4
+ *                            v_mfma_f32_16x16x4_f32, which is such a chain bit for bit), times scale_m in float64, rounded
+ *                            once.  dots: conj(phi) times the unscaled f32 output, float x float in float64 (exact); a
+ *                            thread adds its elements in row order, the lanes of a wave meet in a fixed shuffle tree, the
+ *                            waves in wave order, the workgroups of a state in order in a second kernel; no
+ *                            floating-point atomics.  The grid depends on (n_qubits, keep_mask, M) alone: two calls give
+ *                            the same bits in d_out and d_dots.
+ *                            Refused, each with a message and before anything is launched: the shapes
+ *                            qhbm_reduced_density refuses; d_states, d_operator, d_out or d_scratch NULL; a misaligned
+ *                            pointer; d_out overlapping d_states.
+ *   qhbm_subsystem_apply_scratch_bytes  *out = the bytes of d_scratch such a call needs (csrc/subsystem_plan.h sub_plan: the
+ *                            transposed operator, 8 * 4^k bytes from k = 4 on, and 16 bytes per state and workgroup of
+ *                            it); needs no device.  Refused: the shape as above, out NULL. */
+int qhbm_subsystem_apply_scratch_bytes(int M, int n_qubits, uint64_t keep_mask, size_t* out);
+int qhbm_subsystem_apply(const void* d_states, int M, int n_qubits, uint64_t keep_mask, const void* d_operator,
+                         const double* d_scale, void* d_out, double* d_dots, void* d_scratch, void* stream);
+
 /* Computational-basis samples of the final states (tfq.layers.Sample as used at
  * qhbmlib/inference/qnn.py:169,177-181,286-291):
  *   d_out_samples [U, n_shots, n_qubits] int8 (device); shot j of state u is drawn from

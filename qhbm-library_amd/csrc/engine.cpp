@@ -19,6 +19,7 @@
 #include "plan_args.h"
 #include "program.h"
 #include "rdm_index.h"
+#include "subsystem_plan.h"
 #include "schedule.h"
 
 using namespace qhbm;
@@ -2504,6 +2505,34 @@ int qhbm_reduced_density(const void* d_states, int M, int n_qubits, uint64_t kee
   hipError_t e = launch_reduced_density(static_cast<const float2*>(d_states), uint32_t(M), uint32_t(n_qubits), keep_mask,
                                         d_weights, static_cast<double*>(d_scratch), d_rho, static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return fail(nullptr, std::string("qhbm_reduced_density: ") + hipGetErrorString(e));
+  return 0;
+}
+
+// ---- a dense operator on k qubits of M states (include/qhbm_engine.h; subsystem_apply.hip, subsystem_plan.h) ----
+int qhbm_subsystem_apply_scratch_bytes(int M, int n_qubits, uint64_t keep_mask, size_t* out) {
+  if (!out) return fail(nullptr, "out is NULL");
+  if (int rc = check_reduced_shape(M, n_qubits, keep_mask)) return rc;
+  *out = sub_plan(n_qubits, keep_mask, M).scratch_bytes;
+  return 0;
+}
+
+int qhbm_subsystem_apply(const void* d_states, int M, int n_qubits, uint64_t keep_mask, const void* d_operator,
+                         const double* d_scale, void* d_out, double* d_dots, void* d_scratch, void* stream) {
+  if (int rc = check_reduced_shape(M, n_qubits, keep_mask)) return rc;
+  if (int rc = check_pointer(nullptr, d_states, 16, "d_states")) return rc;
+  if (int rc = check_pointer(nullptr, d_operator, 8, "d_operator")) return rc;
+  if (d_scale)
+    if (int rc = check_pointer(nullptr, d_scale, 8, "d_scale")) return rc;
+  if (int rc = check_pointer(nullptr, d_out, 16, "d_out")) return rc;
+  if (d_dots)
+    if (int rc = check_pointer(nullptr, d_dots, 8, "d_dots")) return rc;
+  if (int rc = check_pointer(nullptr, d_scratch, 8, "d_scratch")) return rc;
+  const size_t bytes = size_t(M) * (size_t(8) << n_qubits);
+  if (ranges_overlap(d_out, bytes, d_states, bytes)) return fail(nullptr, "d_out overlaps d_states");
+  hipError_t e = launch_subsystem_apply(static_cast<const float2*>(d_states), uint32_t(M), uint32_t(n_qubits), keep_mask,
+                                        static_cast<const float2*>(d_operator), d_scale, static_cast<float2*>(d_out), d_dots,
+                                        d_scratch, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, std::string("qhbm_subsystem_apply: ") + hipGetErrorString(e));
   return 0;
 }
 

@@ -1,5 +1,5 @@
 // kernels.h -- launch entry points of the kernel objects (host side): kernels.hip (the pass kernels, with gwg.hip and
-// parity_table.hip), observable.hip (with energy_table.hip and cotangent.hip) and states.hip (import_states.hip, thermal.hip, krylov.hip,
+// parity_table.hip), observable.hip (with energy_table.hip, cotangent.hip and subsystem_apply.hip) and states.hip (import_states.hip, thermal.hip, krylov.hip,
 // gram.hip, reduced.hip).  A .hip file reaches another one's kernels through these declarations only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -346,5 +346,12 @@ hipError_t launch_cotangent_import(const float2* cot, const float2* chi, uint32_
 // keep their bits.
 hipError_t launch_cotangent_phase_grad(const double* dot, const double* norm2, uint32_t U, const float* phase_cs, const float* slope,
                                        float* grad, uint32_t n_params, hipStream_t stream);
+
+// ---- a dense operator on k arbitrary qubits of M states (subsystem_apply.hip; the plan is subsystem_plan.h's) ----
+// out[m] = scale[m] (op (x) 1) states[m] (scale NULL: 1), complex64; op [2^k, 2^k] complex64 row-major on the kept qubits of
+// keep_mask in ascending order; dots [M, 2] = <states[m]|(op (x) 1)|states[m]> before scaling, fp64 in a fixed order, or NULL.
+// Shape limits as launch_reduced_density.  `scratch`: sub_plan(n, keep_mask, M).scratch_bytes bytes, which may hold anything.
+hipError_t launch_subsystem_apply(const float2* states, uint32_t M, uint32_t n, uint64_t keep_mask, const float2* op,
+                                  const double* scale, float2* out, double* dots, void* scratch, hipStream_t stream);
 
 }  // namespace qhbm

@@ -695,3 +695,7 @@ hipError_t launch_observable_blocks(int mode, int block_bits, const float2* psi,
 // The third producer of the backward sweep's lambda, a caller's cotangent of the final states, likewise (it shares
 // state_sweep.h with the state-vector kernels and no name with any other .hip file).
 #include "cotangent.hip"
+
+// A dense operator on k qubits of every state -- the cotangent of the states of a reduced density matrix -- likewise (it
+// shares rdm_index.h with reduced.hip and no name with any other .hip file).
+#include "subsystem_apply.hip"

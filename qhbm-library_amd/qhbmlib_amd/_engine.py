@@ -50,6 +50,7 @@ ABI_SYMBOLS = (
     "qhbm_krylov_basis", "qhbm_krylov_combine", "qhbm_describe_krylov",
     "qhbm_gram_scratch_bytes", "qhbm_weighted_gram",
     "qhbm_reduced_density_scratch_bytes", "qhbm_reduced_density",
+    "qhbm_subsystem_apply_scratch_bytes", "qhbm_subsystem_apply",
     "qhbm_sample_parities", "qhbm_sample_parities_scratch_bytes", "qhbm_sample_parities_states",
 )
 
@@ -152,6 +153,8 @@ def load_library():
     lib.qhbm_weighted_gram.argtypes = [vp, i32, i32, vp, vp, vp, vp]
     lib.qhbm_reduced_density_scratch_bytes.argtypes = [i32, i32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_size_t)]
     lib.qhbm_reduced_density.argtypes = [vp, i32, i32, ctypes.c_uint64, vp, vp, vp, vp]
+    lib.qhbm_subsystem_apply_scratch_bytes.argtypes = [i32, i32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_size_t)]
+    lib.qhbm_subsystem_apply.argtypes = [vp, i32, i32, ctypes.c_uint64, vp, vp, vp, vp, vp, vp]
     lib.qhbm_sample_parities.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, i32, i64, ctypes.c_uint64, vp, vp]
     lib.qhbm_sample_parities_scratch_bytes.argtypes = [i32, i32, i64, ctypes.POINTER(ctypes.c_size_t)]
     lib.qhbm_sample_parities_states.argtypes = [vp, i32, i32, vp, i32, i64, ctypes.c_uint64, ctypes.c_uint64,
@@ -443,6 +446,54 @@ def reduced_density(states, keep_mask, weights=None):
                                                       scratch.data_ptr(), out.data_ptr(),
                                                       torch.cuda.current_stream().cuda_stream))
   return torch.view_as_complex(out)
+
+
+def subsystem_apply_scratch_bytes(num_states, n_qubits, keep_mask):
+  """Bytes of scratch one `qhbm_subsystem_apply` of `num_states` states of `n_qubits` qubits on the qubits of `keep_mask`
+  (bit q set: qubit q is kept) needs (no device needed)."""
+  out = ctypes.c_size_t()
+  _check_global(load_library().qhbm_subsystem_apply_scratch_bytes(int(num_states), int(n_qubits), int(keep_mask),
+                                                                  ctypes.byref(out)))
+  return int(out.value)
+
+
+def subsystem_apply(states, keep_mask, operator, scale=None, want_dots=False):
+  """out[m] = scale[m] (operator (x) 1) states[m] (scale None: 1) for M device-resident states [M, 2^n] and a dense
+  [2^k, 2^k] operator on the kept qubits of `keep_mask` (as `reduced_density`: bit q set keeps qubit q, rows read the kept
+  qubits big-endian in ascending order): complex64 [M, 2^n], f32 arithmetic in a fixed order (include/qhbm_engine.h
+  qhbm_subsystem_apply).  With `want_dots` also dots[m] = <states[m]|(operator (x) 1)|states[m]>, taken before scaling,
+  complex128 [M].  complex128 states and operators are cast to complex64 and the scale to float64; the scratch is this
+  call's own.  Not differentiable."""
+  if not (torch.is_tensor(states) and states.is_cuda and states.dim() == 2 and states.is_complex()):
+    raise EngineError("subsystem_apply needs complex CUDA states [M, 2^n]: the engine has no CPU fallback")
+  states = states.detach().to(torch.complex64).contiguous()
+  if states.data_ptr() % 16:  # (a view at an odd offset: the entry point asks for 16-byte alignment)
+    states = states.clone()
+  num, dim = (int(v) for v in states.shape)
+  n = dim.bit_length() - 1
+  if dim != (1 << n) or n < 1:
+    raise ValueError(f"states have {dim} amplitudes: not a power of two, or fewer than two")
+  keep_mask = int(keep_mask)
+  if keep_mask < 0 or keep_mask >= 1 << 64:
+    raise ValueError(f"keep_mask {keep_mask} is not a 64-bit mask")
+  dim_a = 1 << bin(keep_mask).count("1")
+  operator = torch.as_tensor(operator)
+  if not operator.is_complex() or tuple(operator.shape) != (dim_a, dim_a):
+    raise ValueError(f"operator must be complex of shape [{dim_a}, {dim_a}], got {operator.dtype} {tuple(operator.shape)}")
+  operator = operator.detach().to(device=states.device, dtype=torch.complex64).contiguous()
+  if scale is not None:
+    scale = torch.as_tensor(scale).detach().to(device=states.device, dtype=torch.float64).contiguous()
+    if tuple(scale.shape) != (num,):
+      raise ValueError(f"scale must have shape [{num}], got {tuple(scale.shape)}")
+  with torch.cuda.device(states.device):
+    scratch = torch.empty(subsystem_apply_scratch_bytes(num, n, keep_mask) // 8, dtype=torch.float64, device=states.device)
+    out = torch.empty_like(states)
+    dots = torch.empty((num, 2), dtype=torch.float64, device=states.device) if want_dots else None
+    _check_global(load_library().qhbm_subsystem_apply(states.data_ptr(), num, n, keep_mask, operator.data_ptr(),
+                                                      None if scale is None else scale.data_ptr(), out.data_ptr(),
+                                                      None if dots is None else dots.data_ptr(), scratch.data_ptr(),
+                                                      torch.cuda.current_stream().cuda_stream))
+  return (out, torch.view_as_complex(dots)) if want_dots else out
 
 
 def _parity_masks(masks):

@@ -14,8 +14,9 @@ from qhbmlib_amd.inference.qmhl_loss import qmhl
 from qhbmlib_amd.inference.qnn import (AnalyticQuantumInference, QuantumInference,
                                        SampledQuantumInference)
 from qhbmlib_amd.inference.qnn_utils import unitary
-from qhbmlib_amd.inference.reduced import (mutual_information, reduced_density_matrix, sampled_reduced_density_matrix,
-                                           subsystem_entropy, trace_distance)
+from qhbmlib_amd.inference.reduced import (apply_operator, mutual_information, reduced_density_matrix,
+                                           sampled_ensemble_reduced, sampled_reduced_density_matrix, subsystem_entropy,
+                                           trace_distance)
 from qhbmlib_amd.inference.state_metrics import StateMetrics, state_metrics
 from qhbmlib_amd.inference.thermal import (ThermalEnsemble, imaginary_time_evolution, real_time_evolution,
                                            thermal_ensemble)
@@ -23,8 +24,8 @@ from qhbmlib_amd.inference.vqt_loss import vqt
 
 __all__ = ["AnalyticEnergyInference", "AnalyticQuantumInference", "BernoulliEnergyInference", "CapturedLoss",
            "EnergyInference", "EnergyInferenceBase", "GibbsWithGradientsInference", "KrylovSpace", "QHBM", "QuantumInference",
-           "SampledQuantumInference", "StateMetrics", "ThermalEnsemble", "ThermalSweep", "density_matrix",
+           "SampledQuantumInference", "StateMetrics", "ThermalEnsemble", "ThermalSweep", "apply_operator", "density_matrix",
            "fidelity", "ground_state", "imaginary_time_evolution", "information_matrix", "krylov_space", "mutual_information",
            "natural_gradient", "probabilities", "qmhl", "real_time_evolution", "reduced_density_matrix",
-           "sampled_reduced_density_matrix", "spectrum_extremes", "state_metrics", "subsystem_entropy", "thermal_ensemble",
+           "sampled_ensemble_reduced", "sampled_reduced_density_matrix", "spectrum_extremes", "state_metrics", "subsystem_entropy", "thermal_ensemble",
            "thermal_sweep", "trace_distance", "unitary", "vqt"]
