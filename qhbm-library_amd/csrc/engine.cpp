@@ -290,6 +290,14 @@ size_t own_bytes(const qhbm_engine* h) {
          }();
 }
 
+// "This call consumes the workspace": the states a retaining forward left in psi are overwritten or un-applied in place,
+// and the rows in state_grad are no finished adjoint VJP's any more (qhbm_state_gradients is refused until
+// reduce_state_grad).  A forward-only sweep overwrites psi alone and resets retained_U alone (run_sweep).
+void consume_workspace(qhbm_engine* h) {
+  h->retained_U = 0;
+  h->state_grad_U = 0;
+}
+
 // The ONE place where a setter declares the plans out of date (qhbm_set_circuit, qhbm_set_observables, the planning
 // options).  What was computed under them goes with them: the states a retaining forward left in psi, and the
 // per-state slot rows of the last adjoint VJP -- a rebuilt plan orders its slots, and maps them to parameters, in its
@@ -298,8 +306,7 @@ size_t own_bytes(const qhbm_engine* h) {
 void invalidate_plans(qhbm_engine* h) {
   h->plans_valid = false;
   h->dense.plans_valid = false;  // (the dense-start plans of the from-states calls: the same setters)
-  h->retained_U = 0;
-  h->state_grad_U = 0;
+  consume_workspace(h);
 }
 
 // Exchanges the basis-state plans and everything uploaded for them with the dense-start set (PlanSet), and plans for
@@ -1151,27 +1158,6 @@ int run_observable_chunk(qhbm_engine* h, uint32_t s0, uint32_t c, const float* d
                          const float2* src = nullptr, float2* dst = nullptr);
 int run_values_chunk(qhbm_engine* h, uint32_t row0, uint32_t c, hipStream_t stream);
 
-int forward(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, float* d_out,
-            int shift_gate, double shift, hipStream_t stream) {
-  DevicePlan& d = h->fwd;
-  h->retained_U = 0;
-  if (int rc = prepare_coefs(h, d, d_params, shift_gate, shift, stream)) return rc;
-  if (int rc = values_begin(h, U, stream)) return rc;
-  const uint32_t cs = chunk_states(h, U);
-  if (int rc = ensure_state_buffers(h, cs, false)) return rc;
-  // One observable and a state that passes through HBM anyway: the lean (paired, measurement-free) passes and one
-  // sweep of the lambda = O psi kernel for <psi|O|psi> -- nothing stored -- beat the measuring passes (config 3:
-  // 148 -> 124 ms per 4096 states).  A single-pass plan measures in its tile and never writes the state.
-  const bool from_obs = forward_values_from_observable(h);
-  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += cs) {
-    const uint32_t c = std::min<uint32_t>(cs, uint32_t(U) - s0);
-    if (int rc = run_forward_chunk(h, d_bits, s0, c, from_obs, stream, from_obs)) return rc;
-    if (from_obs)
-      if (int rc = run_values_chunk(h, s0, c, stream)) return rc;
-  }
-  return values_end(h, U, d_out, stream);
-}
-
 // One state per XCD at a time (1) or every XCD an eighth of each state (0)?  Measured on the block kernel, config 4
 // (24 qubits): 61.1 against 53.6 ms per 32 states -- a 128-MiB state that all eight XCDs read sits in the Infinity
 // Cache once; the gather kernel at config 3 (20 qubits): one state per XCD wins (3.7 against 5.1 fabric reads of the
@@ -1272,42 +1258,198 @@ uint32_t adjoint_chunk_states(qhbm_engine* h, int U) {
   return cs;
 }
 
-// values + per-state gradient slots (adjoint) for a given upstream.
-int adjoint_sweep(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params,
-                  const float* d_upstream, float* d_out_vals, hipStream_t stream) {
-  DevicePlan& f = h->fwd;
-  DevicePlan& b = h->adj;
-  h->retained_U = 0;
-  h->state_grad_U = 0;
-  const uint32_t n_slots = uint32_t(b.plan.slot_gate.size());
-  if (int rc = prepare_coefs(h, f, d_params, -1, 0.0, stream)) return rc;
-  if (int rc = prepare_coefs(h, b, d_params, -1, 0.0, stream)) return rc;
-  if (int rc = values_begin(h, U, stream)) return rc;
-  HIPCHK(h->state_grad.reserve(size_t(U) * std::max<uint32_t>(n_slots, 1)));
-  HIPCHK(launch_zero_fill(h->state_grad.p, size_t(U) * std::max<uint32_t>(n_slots, 1) * sizeof(float), stream));
-  const uint32_t cs = adjoint_chunk_states(h, U);
-  if (int rc = ensure_state_buffers(h, cs, true)) return rc;
-  const bool vm = value_mode(h), mv = multi_value_mode(h);
-  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += cs) {
-    const uint32_t c = std::min<uint32_t>(cs, uint32_t(U) - s0);
-    if (int rc = run_forward_chunk(h, d_bits, s0, c, true, stream, vm || mv)) return rc;
-    const bool gm = mv && gather_multi_mode(h);  // 2..4 observables on the gather kernel: values AND lambda from one launch
-    if (mv && !gm)  // several observables: their values from one launch over the final states, lambda (weighted) from the next
-      if (int rc = run_values_chunk(h, s0, c, stream)) return rc;
-    if (int rc = run_observable_chunk(h, s0, c, d_upstream, vm, stream, true, gm)) return rc;
-    if (int rc = run_adjoint_chunk(h, d_bits, s0, c, stream)) return rc;
-  }
-  // value mode ran the sweep on the unweighted lambda: the upstream weight goes onto the gradient rows
-  if (vm) HIPCHK(launch_scale_rows(h->state_grad.p, uint32_t(U), std::max<uint32_t>(n_slots, 1), d_upstream, stream));
-  return values_end(h, U, d_out_vals, stream);
+// ---- the per-state gradient rows (state_grad: [rows, slots of the backward plan]) have ONE owner ----
+uint32_t grad_slots(const qhbm_engine* h) { return std::max<uint32_t>(uint32_t(h->adj.plan.slot_gate.size()), 1); }
+
+hipError_t reserve_state_grad(qhbm_engine* h, size_t rows) { return h->state_grad.reserve(rows * grad_slots(h)); }
+
+// Rows [0, rows) exist and are zero: the tile reductions of the backward passes add into them.
+hipError_t begin_state_grad(qhbm_engine* h, size_t rows, hipStream_t s) {
+  const hipError_t e = reserve_state_grad(h, rows);
+  return e != hipSuccess ? e : launch_zero_fill(h->state_grad.p, rows * grad_slots(h) * sizeof(float), s);
 }
 
-int check_call(qhbm_engine* h, int U) {
+// Value mode (one observable, values from lambda = O psi): the backward sweep ran on the UNWEIGHTED lambda that gave
+// <psi|O|psi>; the upstream weight of every state goes onto its finished row instead.
+hipError_t weight_state_grad(qhbm_engine* h, uint32_t rows, const float* d_upstream, hipStream_t s) {
+  return launch_scale_rows(h->state_grad.p, rows, grad_slots(h), d_upstream, s);
+}
+
+// The rows of U states into d_grad [n_params], and whose rows they are: qhbm_state_gradients serves them (`servable`)
+// through the plan set that filled them (`dense`: a from-states VJP's, slots of the dense-start backward plan).
+int reduce_state_grad(qhbm_engine* h, int U, float* d_grad, bool dense, bool servable, hipStream_t s) {
+  HIPCHK(launch_reduce_grad(h->state_grad.p, uint32_t(U), uint32_t(h->adj.plan.slot_gate.size()), h->param_slot_begin.p,
+                            h->param_slots.p, h->slot_factor.p, d_grad, h->model.n_params, 0, s));
+  h->state_grad_U = servable ? U : 0;
+  h->state_grad_dense = dense;
+  return 0;
+}
+
+// The gradient of an empty batch.
+int empty_batch_grad(qhbm_engine* h, float* d_grad, hipStream_t s) {
+  if (h->model.n_params) HIPCHK(launch_zero_fill(d_grad, size_t(h->model.n_params) * sizeof(float), s));
+  return 0;
+}
+
+// ---- ONE driver for every sweep of the circuit over a batch of states ----
+// How a batch is cut into chunks of the workspace.
+enum class Chunks {
+  kStates,    // chunk_states: psi alone
+  kPairs,     // adjoint_chunk_states: lambda beside psi
+  kBatch,     // the whole batch in one chunk (a retaining forward: the caller has asked batch_fits_backward_chunk)
+  kShots,     // chunk_states, at most 65535: the sampler puts the chunk on a grid dimension
+  kResident,  // the whole batch, and its final states ARE in psi (a retained VJP): no forward work at all
+};
+
+struct Sweep {
+  const int8_t* d_bits; int U; const float* d_params;
+  Chunks chunks = Chunks::kStates;
+  int shift_gate = -1; double shift = 0.0;  // the forward coefficients are those of one shifted program (prepare_coefs)
+  bool with_lam = false;  // lambda sits beside psi in the workspace
+  bool backward = false;  // the caller runs backward passes: the backward plan's coefficients are prepared too
+  bool keep_state = false, skip_measure = false;  // forward_pass_args
+  bool values = false;    // the fixed-point accumulators are zeroed before the sweep and converted into d_out (if any) after it
+  float* d_out = nullptr;
+  bool passes = true;     // false: a chunk's states are imported and no pass runs (a from-states call on a circuit without gates)
+};
+bool batch_fits_backward_chunk(qhbm_engine* h, int U) { return adjoint_chunk_states(h, U) >= uint32_t(U); }
+uint32_t sweep_chunk_states(qhbm_engine* h, const Sweep& sw) {
+  switch (sw.chunks) {
+    case Chunks::kStates: return chunk_states(h, sw.U);
+    case Chunks::kPairs: return adjoint_chunk_states(h, sw.U);
+    case Chunks::kShots: return std::min<uint32_t>(chunk_states(h, sw.U), 65535u);
+    default: return uint32_t(sw.U);
+  }
+}
+
+// body(s0, c) for the chunks [s0, s0 + c) of U states, at most cs at a time.
+template <typename Body>
+int for_each_chunk(int U, uint32_t cs, Body&& body) {
+  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += cs)
+    if (int rc = body(s0, std::min<uint32_t>(cs, uint32_t(U) - s0))) return rc;
+  return 0;
+}
+
+// The sweep: coefficients, value accumulators, the workspace, then chunk by chunk the forward passes and `body(s0, c)`,
+// the caller's own work on a chunk whose final states are in psi.  `reserve(cs)` runs once between the growth of the
+// workspace and the first chunk: scratch sized by the chunk grows there, never inside the loop (a captured step must not
+// allocate), and a caller's pointer is checked against the workspace where it now lies.  Retained states end here.
+template <typename Reserve, typename Body>
+int run_sweep(qhbm_engine* h, const Sweep& sw, hipStream_t s, Reserve&& reserve, Body&& body) {
+  const bool resident = sw.chunks == Chunks::kResident;
+  h->retained_U = 0;
+  if (!resident)
+    if (int rc = prepare_coefs(h, h->fwd, sw.d_params, sw.shift_gate, sw.shift, s)) return rc;
+  if (sw.backward)
+    if (int rc = prepare_coefs(h, h->adj, sw.d_params, -1, 0.0, s)) return rc;
+  if (sw.values)
+    if (int rc = values_begin(h, sw.U, s)) return rc;
+  const uint32_t cs = sweep_chunk_states(h, sw);
+  if (!resident)
+    if (int rc = ensure_state_buffers(h, cs, sw.with_lam)) return rc;
+  if (int rc = reserve(cs)) return rc;
+  if (int rc = for_each_chunk(sw.U, cs, [&](uint32_t s0, uint32_t c) -> int {
+        if (!resident)
+          if (int rc = sw.passes ? run_forward_chunk(h, sw.d_bits, s0, c, sw.keep_state, s, sw.skip_measure)
+                                 : import_chunk(h, s0, c, s))
+            return rc;
+        return body(s0, c);
+      }))
+    return rc;
+  return sw.values ? values_end(h, sw.U, sw.d_out, s) : 0;
+}
+int no_reserve(uint32_t) { return 0; }  // (a caller of run_sweep with no scratch of its own)
+
+// Expectation values.  `retain`: the batch stays in psi, lambda allocated beside it so that psi is not moved later, for
+// qhbm_expectation_vjp_retained -- if it fits one backward chunk; otherwise nothing is kept.
+int forward(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, float* d_out,
+            int shift_gate, double shift, hipStream_t stream, bool retain = false) {
+  retain = retain && batch_fits_backward_chunk(h, U);
+  // One observable and a state that passes through HBM anyway: the lean (paired, measurement-free) passes and one
+  // sweep of the lambda = O psi kernel for <psi|O|psi> -- nothing stored -- beat the measuring passes (config 3:
+  // 148 -> 124 ms per 4096 states).  A single-pass plan measures in its tile and never writes the state.
+  // A retaining call takes the values as the adjoint VJP does, and in value mode keeps the unweighted lambda (retained_mu).
+  const bool vm = value_mode(h), lean = retain ? vm || multi_value_mode(h) : forward_values_from_observable(h);
+  Sweep sw{d_bits, U, d_params, retain ? Chunks::kBatch : Chunks::kStates, shift_gate, shift};
+  sw.with_lam = retain; sw.keep_state = retain || lean; sw.skip_measure = lean;
+  sw.values = true; sw.d_out = d_out;
+  if (int rc = run_sweep(h, sw, stream, no_reserve, [&](uint32_t s0, uint32_t c) -> int {
+        if (!lean) return 0;
+        return retain && vm ? run_observable_chunk(h, s0, c, nullptr, true, stream) : run_values_chunk(h, s0, c, stream);
+      }))
+    return rc;
+  if (retain) { h->retained_U = U; h->retained_mu = vm; h->retained_table = false; }
+  return 0;
+}
+
+// A VJP computes the values whether its caller wants them or not: without d_out_vals they go to scratch.
+int values_or_scratch(qhbm_engine* h, int U, float** d_out_vals) {
+  if (!*d_out_vals) HIPCHK(h->vals_tmp.reserve(size_t(U) * size_t(h->model.n_ops)));
+  if (!*d_out_vals) *d_out_vals = h->vals_tmp.p;
+  return 0;
+}
+
+// values + per-state gradient slots (adjoint) for a given upstream; the rows await reduce_state_grad or a scatter.
+int adjoint_sweep(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params,
+                  const float* d_upstream, float* d_out_vals, hipStream_t stream) {
+  consume_workspace(h);
+  HIPCHK(begin_state_grad(h, size_t(U), stream));
+  const bool vm = value_mode(h), mv = multi_value_mode(h);
+  Sweep sw{d_bits, U, d_params, Chunks::kPairs};
+  sw.with_lam = sw.backward = sw.keep_state = true; sw.skip_measure = vm || mv;
+  sw.values = true; sw.d_out = d_out_vals;
+  if (int rc = run_sweep(h, sw, stream, no_reserve, [&](uint32_t s0, uint32_t c) -> int {
+        const bool gm = mv && gather_multi_mode(h);  // 2..4 observables on the gather kernel: values AND lambda from one launch
+        if (mv && !gm)  // several observables: their values from one launch over the final states, lambda (weighted) from the next
+          if (int rc = run_values_chunk(h, s0, c, stream)) return rc;
+        if (int rc = run_observable_chunk(h, s0, c, d_upstream, vm, stream, true, gm)) return rc;
+        return run_adjoint_chunk(h, d_bits, s0, c, stream);
+      }))
+    return rc;
+  if (vm) HIPCHK(weight_state_grad(h, uint32_t(U), d_upstream, stream));
+  return 0;
+}
+
+// The final states leave the workspace without the global phase the kernels leave out: cirq's e^{i pi t / 2} per X**t / Y**t
+// and every gate's exp(i pi t global_shift).  global_phase puts (cos, sin) of it into phase_cs; apply_global_phase
+// multiplies U exported states [U, 2^n] by it.
+hipError_t global_phase(qhbm_engine* h, const float* d_params, hipStream_t s) {
+  const hipError_t e = h->phase_cs.reserve(2);
+  return e != hipSuccess ? e : launch_global_phase(h->fwd.jobs.p, int(h->fwd.plan.jobs.size()), h->shift_phases.p,
+                                                   h->n_shift_phases, d_params, h->phase_cs.p, s);
+}
+hipError_t apply_global_phase(qhbm_engine* h, void* d_out_states, int U, hipStream_t s) {
+  return launch_scale_states(static_cast<float2*>(d_out_states), size_t(U) << h->model.n, h->phase_cs.p, s);
+}
+
+// The plans that are in, and what the chooser of the adjoint tile and pass order compares (adjoint_plan_seconds).
+std::string describe_plans(const qhbm_engine* h) {
+  char line[96];
+  std::snprintf(line, sizeof(line), "adjoint time model: %.2f us per state\n", 1e6 * adjoint_plan_seconds(h->adj.plan, h->model));
+  return describe_plan(h->fwd.plan) + describe_plan(h->adj.plan) + line;
+}
+
+// The preamble of a compute call: what it requires of the engine and of its arguments, checked in this order.
+enum CallNeeds : unsigned {
+  kNeedCircuit = 1,      // qhbm_set_circuit has been called (the calls that upload the model learn it there)
+  kNeedObservables = 2,
+  kNeedTable = 4,        // `ptr` is the energy table
+  kNeedStates = 8,       // `ptr` is U caller states: 16-byte aligned, outside the workspace
+  kNoUpload = 16,        // the caller exchanges the plan sets first and uploads the model itself
+};
+int begin_call(qhbm_engine* h, int U, unsigned needs, const void* ptr = nullptr) {
   if (!h) return 1;
   if (int rc = need_device(h)) return rc;
   if (U < 0) return fail(h, "negative batch size");
-  if (h->model.n_ops <= 0) return fail(h, "qhbm_set_observables has not been called");
-  return upload_model(h);
+  if ((needs & kNeedCircuit) && !h->have_circuit) return fail(h, "qhbm_set_circuit has not been called");
+  if ((needs & kNeedObservables) && h->model.n_ops <= 0) return fail(h, "qhbm_set_observables has not been called");
+  if ((needs & kNeedTable) && !ptr) return fail(h, "energy table is NULL");
+  if ((needs & kNeedStates) && U > 0) {
+    if (int rc = check_pointer(h, ptr, 16, "d_states")) return rc;
+    if (aliases_workspace(h, ptr, size_t(U) * (size_t(8) << h->model.n)))
+      return fail(h, "d_states lies inside the engine's workspace");
+  }
+  return (needs & kNoUpload) ? 0 : upload_model(h);
 }
 
 // ---- batches of (state, shifted program) pairs: qhbm_expectation_vjp(parameter shift), qhbm_program_vjps and
@@ -1447,22 +1589,16 @@ int run_program_groups(qhbm_engine* h, const int8_t* d_bits, const float* d_para
 // ---- energy tables: E = sum_y table[y] |y><y| (a general BitstringEnergy's modular Hamiltonian) ----
 // No observables are needed: the forward runs the lean, measurement-free passes and keeps the state; the table kernel
 // (energy_table.hip) takes the values, lambda = upstream E psi and the table gradient from it.
-int check_table_call(qhbm_engine* h, int U, const float* d_table) {
-  if (!h) return 1;
-  if (int rc = need_device(h)) return rc;
-  if (U < 0) return fail(h, "negative batch size");
-  if (!d_table) return fail(h, "energy table is NULL");
-  return upload_model(h);
-}
-
-// Scratch of the table kernel for chunks of up to cs states (grown before the chunk loop, never inside it).
-int reserve_table_scratch(qhbm_engine* h, uint32_t cs, bool with_grad) {
+// Scratch of the table kernel for chunks of up to cs states (grown before the chunk loop, never inside it); `with_grad`:
+// and the running table gradient, zeroed.
+int reserve_table_scratch(qhbm_engine* h, uint32_t cs, bool with_grad, hipStream_t s) {
   const uint32_t n_eff = uint32_t(h->fwd.plan.n_eff), n = uint32_t(h->model.n);
   HIPCHK(h->tab_vpart.reserve(size_t(cs) << (n_eff - 10)));
   if (with_grad) {
     HIPCHK(h->tab_gpart.reserve(size_t((cs >> table_group_bits(n_eff)) + 2) << n));
     HIPCHK(h->tab_carry.reserve(size_t(1) << n));
     HIPCHK(h->tab_gsum.reserve(size_t(1) << n));
+    HIPCHK(launch_zero_fill(h->tab_gsum.p, (size_t(1) << n) * sizeof(double), s));
   }
   return 0;
 }
@@ -1476,25 +1612,22 @@ int run_table_chunk(qhbm_engine* h, int mode, const float* d_table, uint32_t s0,
   return 0;
 }
 
-// Values of the table; `retain`: the batch stays in psi (one chunk, lambda allocated beside it) for the retained VJP.
+// qhbm_table_expectation[_retain]: values of the table; `retain`: the batch stays in psi (one chunk, lambda allocated
+// beside it) for the retained VJP -- if it fits one backward chunk.
 int table_forward(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, const float* d_table, float* d_out,
-                  bool retain, hipStream_t s) {
-  DevicePlan& d = h->fwd;
-  h->retained_U = 0;
-  if (retain && adjoint_chunk_states(h, U) < uint32_t(U)) retain = false;  // the batch does not fit one backward chunk
-  if (int rc = prepare_coefs(h, d, d_params, -1, 0.0, s)) return rc;
-  const uint32_t cs = retain ? uint32_t(U) : chunk_states(h, U);
-  if (int rc = ensure_state_buffers(h, cs, retain)) return rc;
-  if (int rc = reserve_table_scratch(h, cs, false)) return rc;
-  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += cs) {
-    const uint32_t c = std::min<uint32_t>(cs, uint32_t(U) - s0);
-    if (int rc = run_forward_chunk(h, d_bits, s0, c, true, s, true)) return rc;
-    if (int rc = run_table_chunk(h, TABLE_VALUES, d_table, s0, c, U, nullptr, d_out, s)) return rc;
-  }
-  if (retain) {
-    h->retained_U = U;
-    h->retained_table = true;
-  }
+                  bool retain, void* stream) {
+  if (int rc = begin_call(h, U, kNeedTable, d_table)) return rc;
+  if (U == 0) return 0;
+  if (!d_out) return fail(h, "d_out is NULL");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  retain = retain && batch_fits_backward_chunk(h, U);
+  Sweep sw{d_bits, U, d_params, retain ? Chunks::kBatch : Chunks::kStates};
+  sw.with_lam = retain; sw.keep_state = sw.skip_measure = true;
+  if (int rc = run_sweep(
+          h, sw, s, [&](uint32_t cs) { return reserve_table_scratch(h, cs, false, s); },
+          [&](uint32_t s0, uint32_t c) { return run_table_chunk(h, TABLE_VALUES, d_table, s0, c, U, nullptr, d_out, s); }))
+    return rc;
+  if (retain) { h->retained_U = U; h->retained_table = true; }
   return 0;
 }
 
@@ -1502,36 +1635,43 @@ int table_forward(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_pa
 // `retained`: the final states of a table_forward(retain) are in psi -- no forward passes.
 int table_vjp(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, const float* d_table,
               const float* d_upstream, float* d_out_vals, float* d_grad, float* d_table_grad, bool retained, hipStream_t s) {
-  DevicePlan& f = h->fwd;
-  DevicePlan& b = h->adj;
-  const int P = h->model.n_params;
   const size_t dim = size_t(1) << h->model.n;
-  h->retained_U = 0;  // (the backward sweep un-applies psi in place: retained states are consumed)
-  h->state_grad_U = 0;
-  const uint32_t n_slots = uint32_t(b.plan.slot_gate.size());
-  if (!retained)
-    if (int rc = prepare_coefs(h, f, d_params, -1, 0.0, s)) return rc;
-  if (int rc = prepare_coefs(h, b, d_params, -1, 0.0, s)) return rc;
-  HIPCHK(h->state_grad.reserve(size_t(U) * std::max<uint32_t>(n_slots, 1)));
-  HIPCHK(launch_zero_fill(h->state_grad.p, size_t(U) * std::max<uint32_t>(n_slots, 1) * sizeof(float), s));
-  const uint32_t cs = retained ? uint32_t(U) : adjoint_chunk_states(h, U);
-  if (!retained)
-    if (int rc = ensure_state_buffers(h, cs, true)) return rc;
-  if (int rc = reserve_table_scratch(h, cs, d_table_grad != nullptr)) return rc;
-  if (d_table_grad) HIPCHK(launch_zero_fill(h->tab_gsum.p, dim * sizeof(double), s));
+  consume_workspace(h);  // (the backward sweep un-applies psi in place: retained states are consumed)
+  HIPCHK(begin_state_grad(h, size_t(U), s));
   const int mode = d_table_grad ? TABLE_LAMBDA_GRAD : TABLE_LAMBDA;
-  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += cs) {
-    const uint32_t c = std::min<uint32_t>(cs, uint32_t(U) - s0);
-    if (!retained)
-      if (int rc = run_forward_chunk(h, d_bits, s0, c, true, s, true)) return rc;
-    if (int rc = run_table_chunk(h, mode, d_table, s0, c, U, d_upstream, d_out_vals, s)) return rc;
-    if (int rc = run_adjoint_chunk(h, d_bits, s0, c, s)) return rc;
-  }
-  HIPCHK(launch_reduce_grad(h->state_grad.p, uint32_t(U), n_slots, h->param_slot_begin.p, h->param_slots.p,
-                            h->slot_factor.p, d_grad, P, 0, s));
-  h->state_grad_U = U;
-  h->state_grad_dense = false;
+  Sweep sw{d_bits, U, d_params, retained ? Chunks::kResident : Chunks::kPairs};
+  sw.with_lam = sw.backward = sw.keep_state = sw.skip_measure = true;
+  if (int rc = run_sweep(
+          h, sw, s, [&](uint32_t cs) { return reserve_table_scratch(h, cs, d_table_grad != nullptr, s); },
+          [&](uint32_t s0, uint32_t c) -> int {
+            if (int rc = run_table_chunk(h, mode, d_table, s0, c, U, d_upstream, d_out_vals, s)) return rc;
+            return run_adjoint_chunk(h, d_bits, s0, c, s);
+          }))
+    return rc;
+  if (int rc = reduce_state_grad(h, U, d_grad, false, true, s)) return rc;
   if (d_table_grad) HIPCHK(launch_doubles_to_floats(h->tab_gsum.p, d_table_grad, dim, s));
+  return 0;
+}
+
+// ---- shifted programs named by the caller: (shift_gates[q], shifts[q]), a negative gate = the unshifted circuit ----
+const char* const kNoTwoTermRule = "the two-term parameter-shift rule does not apply to ISWAPPOW; use the adjoint method";
+
+// `two_term_rule`: the values of the programs are combined by the two-term shift rule, which ISWAPPOW does not obey
+// (qhbm_program_vjps; the parameter-shift VJP builds its own programs and says the same of them); the sampling calls run
+// any shifted program.  The sampling calls report an entry out of range before any constant exponent (a pass over the
+// ranges first), qhbm_program_vjps the first entry at fault -- as each always did.
+int check_shifted_programs(qhbm_engine* h, int n_programs, const int32_t* shift_gates, const float* shifts, bool two_term_rule) {
+  const int n_gates = int(h->model.gates.size());
+  for (int pass = two_term_rule ? 1 : 0; pass < 2; ++pass)
+    for (int q = 0; q < n_programs; ++q) {
+      const int g = shift_gates[q];
+      if (g >= n_gates) return fail(h, "shift_gates entry out of range");
+      if (pass == 0 || g < 0 || shifts[q] == 0.f) continue;
+      const Gate& G = h->model.gates[size_t(g)];
+      if (two_term_rule && G.kind == QHBM_GATE_ISWAPPOW) return fail(h, kNoTwoTermRule);
+      if (G.param_idx < 0)
+        return fail(h, "shift_gates entry addresses a gate with a constant exponent: only parametrised gates have shifted programs");
+    }
   return 0;
 }
 
@@ -1664,8 +1804,7 @@ int qhbm_set_gradient_mask(qhbm_engine* h, const uint8_t* needs_grad, int n_para
     swap_plan_sets(h);
     h->model.param_frozen = std::move(frozen);
     h->shift_ready = false;
-    h->retained_U = 0;
-    h->state_grad_U = 0;
+    consume_workspace(h);
   }
   return 0;
 }
@@ -1788,62 +1927,37 @@ int qhbm_retained_states(qhbm_engine* h, int* out_U) {
 
 int qhbm_expectation(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, float* d_out,
                      void* stream) {
-  if (int rc = check_call(h, U)) return rc;
+  if (int rc = begin_call(h, U, kNeedObservables)) return rc;
   if (U == 0) return 0;
   return forward(h, d_bits, U, d_params, d_out, -1, 0.0, static_cast<hipStream_t>(stream));
 }
 
 int qhbm_expectation_retain(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, float* d_out,
                             void* stream) {
-  if (int rc = check_call(h, U)) return rc;
+  if (int rc = begin_call(h, U, kNeedObservables)) return rc;
   if (U == 0) return 0;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (adjoint_chunk_states(h, U) < uint32_t(U))  // the batch does not fit one backward chunk: nothing kept
-    return forward(h, d_bits, U, d_params, d_out, -1, 0.0, s);
-  DevicePlan& d = h->fwd;
-  h->retained_U = 0;
-  if (int rc = prepare_coefs(h, d, d_params, -1, 0.0, s)) return rc;
-  if (int rc = values_begin(h, U, s)) return rc;
-  if (int rc = ensure_state_buffers(h, uint32_t(U), true)) return rc;  // psi AND lambda, so psi is not moved later
-  const bool vm = value_mode(h), mv = multi_value_mode(h);
-  if (int rc = run_forward_chunk(h, d_bits, 0, uint32_t(U), true, s, vm || mv)) return rc;
-  if (vm) {
-    if (int rc = run_observable_chunk(h, 0, uint32_t(U), nullptr, true, s)) return rc;
-  } else if (mv) {
-    if (int rc = run_values_chunk(h, 0, uint32_t(U), s)) return rc;
-  }
-  if (int rc = values_end(h, U, d_out, s)) return rc;
-  h->retained_U = U;
-  h->retained_mu = vm;
-  h->retained_table = false;
-  return 0;
+  return forward(h, d_bits, U, d_params, d_out, -1, 0.0, static_cast<hipStream_t>(stream), true);
 }
 
 int qhbm_expectation_vjp_retained(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params,
                                   const float* d_upstream, float* d_grad, void* stream) {
-  if (int rc = check_call(h, U)) return rc;
+  if (int rc = begin_call(h, U, kNeedObservables)) return rc;
   if (U <= 0 || h->retained_U != U) return fail(h, "no retained forward state for this batch");
   if (h->retained_table) return fail(h, "the retained states are an energy-table call's: use qhbm_table_expectation_vjp_retained");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  DevicePlan& b = h->adj;
-  h->retained_U = 0;  // the backward sweep un-applies psi in place: the state is consumed
-  h->state_grad_U = 0;
-  const uint32_t n_slots = uint32_t(b.plan.slot_gate.size());
-  if (int rc = prepare_coefs(h, b, d_params, -1, 0.0, s)) return rc;
-  HIPCHK(h->state_grad.reserve(size_t(U) * std::max<uint32_t>(n_slots, 1)));
-  HIPCHK(launch_zero_fill(h->state_grad.p, size_t(U) * std::max<uint32_t>(n_slots, 1) * sizeof(float), s));
-  if (h->retained_mu) {  // lambda = O psi (unweighted) was computed with the values: weight the rows instead
-    if (int rc = run_adjoint_chunk(h, d_bits, 0, uint32_t(U), s)) return rc;
-    HIPCHK(launch_scale_rows(h->state_grad.p, uint32_t(U), std::max<uint32_t>(n_slots, 1), d_upstream, s));
-  } else {
-    if (int rc = run_observable_chunk(h, 0, uint32_t(U), d_upstream, false, s)) return rc;
-    if (int rc = run_adjoint_chunk(h, d_bits, 0, uint32_t(U), s)) return rc;
-  }
-  HIPCHK(launch_reduce_grad(h->state_grad.p, uint32_t(U), n_slots, h->param_slot_begin.p, h->param_slots.p,
-                            h->slot_factor.p, d_grad, h->model.n_params, 0, s));
-  h->state_grad_U = U;
-  h->state_grad_dense = false;
-  return 0;
+  const bool mu = h->retained_mu;  // lambda = O psi (unweighted) was computed with the values: the rows are weighted instead
+  consume_workspace(h);  // the backward sweep un-applies psi in place: the state is consumed
+  HIPCHK(begin_state_grad(h, size_t(U), s));
+  Sweep sw{d_bits, U, d_params, Chunks::kResident};
+  sw.with_lam = sw.backward = true;
+  if (int rc = run_sweep(h, sw, s, no_reserve, [&](uint32_t s0, uint32_t c) -> int {
+        if (!mu)
+          if (int rc = run_observable_chunk(h, s0, c, d_upstream, false, s)) return rc;
+        return run_adjoint_chunk(h, d_bits, s0, c, s);
+      }))
+    return rc;
+  if (mu) HIPCHK(weight_state_grad(h, uint32_t(U), d_upstream, s));
+  return reduce_state_grad(h, U, d_grad, false, true, s);
 }
 
 int qhbm_state_gradients(qhbm_engine* h, int U, float* d_rows, void* stream) {
@@ -1862,33 +1976,21 @@ int qhbm_state_gradients(qhbm_engine* h, int U, float* d_rows, void* stream) {
 
 int qhbm_statevector(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params,
                      void* d_out_states, void* stream) {
-  if (!h) return 1;
-  if (int rc = need_device(h)) return rc;
-  if (U < 0) return fail(h, "negative batch size");
-  if (int rc = upload_model(h)) return rc;
+  if (int rc = begin_call(h, U, 0)) return rc;
   if (U == 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  DevicePlan& d = h->fwd;
-  h->retained_U = 0;
-  if (int rc = prepare_coefs(h, d, d_params, -1, 0.0, s)) return rc;
-  // expectation values of installed observables are a by-product; they stay in the fixed-point scratch
-  if (int rc = values_begin(h, U, s)) return rc;
-  const uint32_t cs = chunk_states(h, U);
-  if (int rc = ensure_state_buffers(h, cs, false)) return rc;
-  const size_t row = size_t(8) << h->model.n, pitch = size_t(8) << d.plan.n_eff;
-  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += cs) {
-    const uint32_t c = std::min<uint32_t>(cs, uint32_t(U) - s0);
-    if (int rc = run_forward_chunk(h, d_bits, s0, c, true, s)) return rc;
-    // idle padding qubits (n < 10) are the high index bits and stay |0>: keep the first 2^n amplitudes
-    HIPCHK(hipMemcpy2DAsync(static_cast<char*>(d_out_states) + size_t(s0) * row, row, h->psi.p, pitch, row, c,
-                            hipMemcpyDeviceToDevice, s));
-  }
-  // restore the global phase the kernels leave out: cirq's e^{i pi t / 2} per X**t / Y**t and every
-  // gate's exp(i pi t global_shift)
-  HIPCHK(h->phase_cs.reserve(2));
-  HIPCHK(launch_global_phase(d.jobs.p, int(d.plan.jobs.size()), h->shift_phases.p, h->n_shift_phases, d_params,
-                             h->phase_cs.p, s));
-  HIPCHK(launch_scale_states(static_cast<float2*>(d_out_states), size_t(U) << h->model.n, h->phase_cs.p, s));
+  const size_t row = size_t(8) << h->model.n, pitch = size_t(8) << h->fwd.plan.n_eff;
+  Sweep sw{d_bits, U, d_params};
+  sw.keep_state = sw.values = true;  // (values of installed observables are a by-product; they stay in the fixed-point scratch)
+  if (int rc = run_sweep(h, sw, s, no_reserve, [&](uint32_t s0, uint32_t c) -> int {
+        // idle padding qubits (n < 10) are the high index bits and stay |0>: keep the first 2^n amplitudes
+        HIPCHK(hipMemcpy2DAsync(static_cast<char*>(d_out_states) + size_t(s0) * row, row, h->psi.p, pitch, row, c,
+                                hipMemcpyDeviceToDevice, s));
+        return 0;
+      }))
+    return rc;
+  HIPCHK(global_phase(h, d_params, s));
+  HIPCHK(apply_global_phase(h, d_out_states, U, s));
   return 0;
 }
 
@@ -1897,20 +1999,6 @@ int qhbm_statevector(qhbm_engine* h, const int8_t* d_bits, int U, const float* d
 }  // extern "C"
 
 namespace {
-
-// Argument checks of a from-states call, before the plan sets are exchanged.
-int check_states_call(qhbm_engine* h, const void* d_states, int U, bool need_observables) {
-  if (!h) return 1;
-  if (int rc = need_device(h)) return rc;
-  if (U < 0) return fail(h, "negative batch size");
-  if (!h->have_circuit) return fail(h, "qhbm_set_circuit has not been called");
-  if (need_observables && h->model.n_ops <= 0) return fail(h, "qhbm_set_observables has not been called");
-  if (U > 0)
-    if (int rc = check_pointer(h, d_states, 16, "d_states")) return rc;
-  if (U > 0 && aliases_workspace(h, d_states, size_t(U) * (size_t(8) << h->model.n)))
-    return fail(h, "d_states lies inside the engine's workspace");
-  return 0;
-}
 
 // The import's per-call buffers; from here on run_forward_chunk imports (the DenseScope of the call ends that).
 int begin_import(qhbm_engine* h, const void* d_states, int U, const float* d_upstream, hipStream_t stream) {
@@ -1927,13 +2015,22 @@ int begin_import(qhbm_engine* h, const void* d_states, int U, const float* d_ups
   return 0;
 }
 
+// The final states of a from-states chunk leave the workspace for the caller's rows [s0, s0 + c): idle padding qubits
+// stay |0>, so the first 2^n amplitudes of a row, times ||phi|| -- the state as given, evolved (the phase follows once,
+// over the whole output: apply_global_phase).
+hipError_t export_chunk(qhbm_engine* h, void* d_out_states, uint32_t s0, uint32_t c, hipStream_t s) {
+  const uint32_t n = uint32_t(h->model.n);
+  return launch_scale_copy_states(h->psi.p, uint32_t(h->fwd.plan.n_eff), static_cast<float2*>(d_out_states) + (size_t(s0) << n), n, n,
+                                  c, nullptr, h->import_norm2.p + s0, s);
+}
+
 }  // namespace
 
 extern "C" {
 
 int qhbm_expectation_from_states(qhbm_engine* h, const void* d_states, int U, const float* d_params, float* d_out,
                                  void* stream) {
-  if (int rc = check_states_call(h, d_states, U, true)) return rc;
+  if (int rc = begin_call(h, U, kNeedCircuit | kNeedObservables | kNeedStates | kNoUpload, d_states)) return rc;
   DenseScope scope(h);
   if (int rc = upload_model(h)) return rc;
   if (U == 0) return 0;
@@ -1947,73 +2044,51 @@ int qhbm_expectation_from_states(qhbm_engine* h, const void* d_states, int U, co
 
 int qhbm_expectation_vjp_from_states(qhbm_engine* h, const void* d_states, int U, const float* d_params,
                                      const float* d_upstream, float* d_out_vals, float* d_grad, void* stream) {
-  if (int rc = check_states_call(h, d_states, U, true)) return rc;
+  if (int rc = begin_call(h, U, kNeedCircuit | kNeedObservables | kNeedStates | kNoUpload, d_states)) return rc;
   if (!d_grad || (U > 0 && !d_upstream)) return fail(h, "d_upstream or d_grad is NULL");
   DenseScope scope(h);
   if (int rc = upload_model(h)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int P = h->model.n_params;
-  if (U == 0) {
-    if (P) HIPCHK(launch_zero_fill(d_grad, size_t(P) * sizeof(float), s));
-    return 0;
-  }
-  if (!d_out_vals) {
-    HIPCHK(h->vals_tmp.reserve(size_t(U) * size_t(h->model.n_ops)));
-    d_out_vals = h->vals_tmp.p;
-  }
+  if (U == 0) return empty_batch_grad(h, d_grad, s);
+  if (int rc = values_or_scratch(h, U, &d_out_vals)) return rc;
   if (int rc = begin_import(h, d_states, U, d_upstream, s)) return rc;
   // lambda = sum_k (upstream[u, k] ||phi_u||^2) O_k psi_u on the normalised psi_u: the gradient of the states as given
   if (int rc = adjoint_sweep(h, h->import_bits.p, U, d_params, h->import_up.p, d_out_vals, s)) return rc;
   HIPCHK(launch_scale_by_norm2(d_out_vals, d_out_vals, uint32_t(U), uint32_t(h->model.n_ops), h->import_norm2.p, s));
-  HIPCHK(launch_reduce_grad(h->state_grad.p, uint32_t(U), uint32_t(h->adj.plan.slot_gate.size()), h->param_slot_begin.p,
-                            h->param_slots.p, h->slot_factor.p, d_grad, P, 0, s));
-  h->state_grad_U = U;
-  h->state_grad_dense = true;
-  return 0;
+  return reduce_state_grad(h, U, d_grad, true, true, s);
 }
 
 int qhbm_statevector_from_states(qhbm_engine* h, const void* d_states, int U, const float* d_params, void* d_out_states,
                                  void* stream) {
-  if (int rc = check_states_call(h, d_states, U, false)) return rc;
+  if (int rc = begin_call(h, U, kNeedCircuit | kNeedStates | kNoUpload, d_states)) return rc;
   if (U > 0 || d_out_states)
     if (int rc = check_pointer(h, d_out_states, 16, "d_out_states")) return rc;
   DenseScope scope(h);
   if (int rc = upload_model(h)) return rc;
   if (U == 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  DevicePlan& d = h->fwd;
-  h->retained_U = 0;
   if (int rc = begin_import(h, d_states, U, nullptr, s)) return rc;
-  if (int rc = prepare_coefs(h, d, d_params, -1, 0.0, s)) return rc;
-  if (int rc = values_begin(h, U, s)) return rc;  // (by-product values of installed observables stay in the scratch)
-  const uint32_t cs = chunk_states(h, U);
-  if (int rc = ensure_state_buffers(h, cs, false)) return rc;
-  const uint32_t n = uint32_t(h->model.n), n_eff = uint32_t(d.plan.n_eff);
-  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += cs) {
-    const uint32_t c = std::min<uint32_t>(cs, uint32_t(U) - s0);
-    // (a circuit without gates: the imported states are the result.  The plan's one pass would load and store them
-    // unchanged; it is skipped -- and with it the by-product values of installed observables, which nobody can read --
-    // so that the forward events of such a call time the import alone: scripts/from_states_time.py measures it this way)
-    if (int rc = h->model.gates.empty() ? import_chunk(h, s0, c, s) : run_forward_chunk(h, h->import_bits.p, s0, c, true, s)) return rc;
-    // idle padding qubits stay |0>: the first 2^n amplitudes of a row, times ||phi|| -- the state as given, evolved
-    HIPCHK(launch_scale_copy_states(h->psi.p, n_eff, static_cast<float2*>(d_out_states) + (size_t(s0) << n), n, n, c, nullptr,
-                                    h->import_norm2.p + s0, s));
-  }
-  HIPCHK(h->phase_cs.reserve(2));  // the global phase the kernels leave out, as qhbm_statevector restores it
-  HIPCHK(launch_global_phase(d.jobs.p, int(d.plan.jobs.size()), h->shift_phases.p, h->n_shift_phases, d_params,
-                             h->phase_cs.p, s));
-  HIPCHK(launch_scale_states(static_cast<float2*>(d_out_states), size_t(U) << h->model.n, h->phase_cs.p, s));
+  Sweep sw{h->import_bits.p, U, d_params};
+  sw.keep_state = sw.values = true;  // (by-product values of installed observables stay in the scratch)
+  // (a circuit without gates: the imported states are the result.  The plan's one pass would load and store them
+  // unchanged; it is skipped -- and with it the by-product values of installed observables, which nobody can read --
+  // so that the forward events of such a call time the import alone: scripts/from_states_time.py measures it this way)
+  sw.passes = !h->model.gates.empty();
+  auto export_rows = [&](uint32_t s0, uint32_t c) -> int { HIPCHK(export_chunk(h, d_out_states, s0, c, s)); return 0; };
+  if (int rc = run_sweep(h, sw, s, no_reserve, export_rows)) return rc;
+  HIPCHK(global_phase(h, d_params, s));
+  HIPCHK(apply_global_phase(h, d_out_states, U, s));
   return 0;
 }
 
 int qhbm_statevector_vjp_from_states(qhbm_engine* h, const void* d_states, int U, const float* d_params,
                                      const void* d_cotangent, void* d_out_states, float* d_grad, void* stream) {
-  if (int rc = check_states_call(h, d_states, U, false)) return rc;
+  if (int rc = begin_call(h, U, kNeedCircuit | kNeedStates | kNoUpload, d_states)) return rc;
   if (!d_grad) return fail(h, "d_grad is NULL");
   if (d_out_states)
     if (int rc = check_pointer(h, d_out_states, 16, "d_out_states")) return rc;
+  const size_t bytes = size_t(U) * (size_t(8) << h->model.n);
   if (U > 0) {
-    const size_t bytes = size_t(U) * (size_t(8) << h->model.n);
     if (int rc = check_pointer(h, d_cotangent, 16, "d_cotangent")) return rc;
     if (aliases_workspace(h, d_cotangent, bytes)) return fail(h, "d_cotangent lies inside the engine's workspace");
     if (d_out_states && (ranges_overlap(d_out_states, bytes, d_cotangent, bytes) || ranges_overlap(d_out_states, bytes, d_states, bytes)))
@@ -2022,48 +2097,38 @@ int qhbm_statevector_vjp_from_states(qhbm_engine* h, const void* d_states, int U
   DenseScope scope(h);
   if (int rc = upload_model(h)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int P = h->model.n_params;
-  h->retained_U = 0;
-  h->state_grad_U = 0;  // (qhbm_state_gradients is refused after this call: the rows lack the phase term)
-  if (U == 0) {
-    if (P) HIPCHK(launch_zero_fill(d_grad, size_t(P) * sizeof(float), s));
-    return 0;
-  }
-  DevicePlan& f = h->fwd;
-  DevicePlan& b = h->adj;
+  consume_workspace(h);
+  if (U == 0) return empty_batch_grad(h, d_grad, s);
   if (int rc = begin_import(h, d_states, U, nullptr, s)) return rc;
-  if (int rc = prepare_coefs(h, f, d_params, -1, 0.0, s)) return rc;
-  if (int rc = prepare_coefs(h, b, d_params, -1, 0.0, s)) return rc;
-  const uint32_t n_slots = uint32_t(b.plan.slot_gate.size());
-  HIPCHK(h->state_grad.reserve(size_t(U) * std::max<uint32_t>(n_slots, 1)));
-  HIPCHK(launch_zero_fill(h->state_grad.p, size_t(U) * std::max<uint32_t>(n_slots, 1) * sizeof(float), s));
-  const uint32_t cs = adjoint_chunk_states(h, U);
-  if (int rc = ensure_state_buffers(h, cs, true)) return rc;
-  // (the buffers may have moved: the checks again, on the workspace the sweep will use)
-  if (aliases_workspace(h, d_cotangent, size_t(U) * (size_t(8) << h->model.n))) return fail(h, "d_cotangent lies inside the engine's workspace");
-  const uint32_t n = uint32_t(h->model.n), n_eff = uint32_t(f.plan.n_eff);
-  HIPCHK(h->cot_parts.reserve(cotangent_parts_count(n, cs)));
-  HIPCHK(h->cot_dot.reserve(size_t(U) * 2));
-  HIPCHK(h->phase_cs.reserve(2));  // the global phase the kernels leave out, as qhbm_statevector restores it
-  HIPCHK(launch_global_phase(f.jobs.p, int(f.plan.jobs.size()), h->shift_phases.p, h->n_shift_phases, d_params, h->phase_cs.p, s));
+  HIPCHK(begin_state_grad(h, size_t(U), s));
+  HIPCHK(global_phase(h, d_params, s));
+  const uint32_t n = uint32_t(h->model.n), n_eff = uint32_t(h->fwd.plan.n_eff);
   const float2* cot = static_cast<const float2*>(d_cotangent);
-  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += cs) {
-    const uint32_t c = std::min<uint32_t>(cs, uint32_t(U) - s0);
-    if (int rc = run_forward_chunk(h, h->import_bits.p, s0, c, true, s, true)) return rc;
-    if (d_out_states)  // the export of qhbm_statevector_from_states, before the backward sweep un-applies psi in place
-      HIPCHK(launch_scale_copy_states(h->psi.p, n_eff, static_cast<float2*>(d_out_states) + (size_t(s0) << n), n, n, c, nullptr,
-                                      h->import_norm2.p + s0, s));
-    hipEvent_t* ev = timer_begin(h, 2, s);  // (profile_events: the cotangent import counts as the lambda launch)
-    HIPCHK(launch_cotangent_import(cot, h->psi.p, n, n_eff, c, s0, h->import_norm2.p, h->phase_cs.p, h->lam.p, h->cot_parts.p,
-                                   h->cot_dot.p, s));
-    timer_end(ev, s);
-    if (int rc = run_adjoint_chunk(h, h->import_bits.p, s0, c, s)) return rc;
-  }
-  if (d_out_states) HIPCHK(launch_scale_states(static_cast<float2*>(d_out_states), size_t(U) << n, h->phase_cs.p, s));
-  HIPCHK(launch_reduce_grad(h->state_grad.p, uint32_t(U), n_slots, h->param_slot_begin.p, h->param_slots.p, h->slot_factor.p,
-                            d_grad, P, 0, s));
+  Sweep sw{h->import_bits.p, U, d_params, Chunks::kPairs};
+  sw.with_lam = sw.backward = sw.keep_state = sw.skip_measure = true;
+  if (int rc = run_sweep(
+          h, sw, s,
+          [&](uint32_t cs) -> int {
+            // (the buffers may have moved: the check again, on the workspace the sweep will use)
+            if (aliases_workspace(h, d_cotangent, bytes)) return fail(h, "d_cotangent lies inside the engine's workspace");
+            HIPCHK(h->cot_parts.reserve(cotangent_parts_count(n, cs)));
+            HIPCHK(h->cot_dot.reserve(size_t(U) * 2));
+            return 0;
+          },
+          [&](uint32_t s0, uint32_t c) -> int {
+            if (d_out_states) HIPCHK(export_chunk(h, d_out_states, s0, c, s));  // before the backward sweep un-applies psi in place
+            hipEvent_t* ev = timer_begin(h, 2, s);  // (profile_events: the cotangent import counts as the lambda launch)
+            HIPCHK(launch_cotangent_import(cot, h->psi.p, n, n_eff, c, s0, h->import_norm2.p, h->phase_cs.p, h->lam.p,
+                                           h->cot_parts.p, h->cot_dot.p, s));
+            timer_end(ev, s);
+            return run_adjoint_chunk(h, h->import_bits.p, s0, c, s);
+          }))
+    return rc;
+  if (d_out_states) HIPCHK(apply_global_phase(h, d_out_states, U, s));
+  // (qhbm_state_gradients is refused after this call: the rows lack the phase term, which goes into d_grad alone)
+  if (int rc = reduce_state_grad(h, U, d_grad, true, false, s)) return rc;
   HIPCHK(launch_cotangent_phase_grad(h->cot_dot.p, h->import_norm2.p, uint32_t(U), h->phase_cs.p, h->phase_slope.p, d_grad,
-                                     uint32_t(P), s));
+                                     uint32_t(h->model.n_params), s));
   return 0;
 }
 
@@ -2071,11 +2136,7 @@ int qhbm_describe_schedule_from_states(qhbm_engine* h, char* buf, size_t buf_len
   if (!h || !buf || !buf_len) return 1;
   DenseScope scope(h);
   if (int rc = build_plans(h)) return rc;
-  std::string s = describe_plan(h->fwd.plan) + describe_plan(h->adj.plan);
-  char line[96];
-  std::snprintf(line, sizeof(line), "adjoint time model: %.2f us per state\n", 1e6 * adjoint_plan_seconds(h->adj.plan, h->model));
-  s += line;
-  std::snprintf(buf, buf_len, "%s", s.c_str());
+  std::snprintf(buf, buf_len, "%s", describe_plans(h).c_str());
   return 0;
 }
 
@@ -2221,22 +2282,19 @@ int qhbm_apply_observables(qhbm_engine* h, const void* d_states, int U, const do
   DenseScope scope(h);
   if (int rc = upload_model(h)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  h->retained_U = 0;
-  h->state_grad_U = 0;
+  consume_workspace(h);
   const uint32_t n = uint32_t(h->model.n), n_eff = uint32_t(h->fwd.plan.n_eff), n_ops = uint32_t(h->model.n_ops);
   if (int rc = upload_evolve_weights(h, weights, 1.0, s)) return rc;
   const uint32_t cs = adjoint_chunk_states(h, U);
   HIPCHK(h->evo_up1.reserve(size_t(cs) * n_ops));
   if (n != n_eff)
     if (int rc = ensure_state_buffers(h, cs, true)) return rc;
-  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += cs) {
-    const uint32_t c = std::min<uint32_t>(cs, uint32_t(U) - s0);
+  return for_each_chunk(U, cs, [&](uint32_t s0, uint32_t c) -> int {
     const float2* in = reinterpret_cast<const float2*>(static_cast<const char*>(d_states) + size_t(s0) * row);
     float2* out = reinterpret_cast<float2*>(static_cast<char*>(d_out_states) + size_t(s0) * row);
     HIPCHK(launch_evolve_init(c, nullptr, nullptr, nullptr, h->evo_wr.p, n_ops, h->evo_up1.p, nullptr, s));
-    if (int rc = apply_h_chunk(h, in, out, c, s)) return rc;
-  }
-  return 0;
+    return apply_h_chunk(h, in, out, c, s);
+  });
 }
 
 int qhbm_evolve_states(qhbm_engine* h, void* d_states, int U, const double* weights, double tau, int mode,
@@ -2250,8 +2308,7 @@ int qhbm_evolve_states(qhbm_engine* h, void* d_states, int U, const double* weig
   DenseScope scope(h);
   if (int rc = upload_model(h)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  h->retained_U = 0;
-  h->state_grad_U = 0;
+  consume_workspace(h);
   const uint32_t n = uint32_t(h->model.n), n_eff = uint32_t(h->fwd.plan.n_eff), n_ops = uint32_t(h->model.n_ops);
   const size_t row = size_t(8) << n, pitch = size_t(1) << n_eff;
   // R = 0 (H = 0), and no step in real time: the identity -- the states are not written
@@ -2370,8 +2427,7 @@ int qhbm_krylov_basis(qhbm_engine* h, const void* d_start_states, int U, const d
   DenseScope scope(h);
   if (int rc = upload_model(h)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  h->retained_U = 0;
-  h->state_grad_U = 0;
+  consume_workspace(h);
   const uint32_t n_eff = uint32_t(h->fwd.plan.n_eff), n_ops = uint32_t(h->model.n_ops);
   const uint32_t cs = adjoint_chunk_states(h, U);
   if (int rc = ensure_state_buffers(h, cs, true)) return rc;
@@ -2550,29 +2606,23 @@ int qhbm_random_states(void* d_states, int U, int n_qubits, uint64_t seed, uint6
 
 int qhbm_table_expectation(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, const float* d_table,
                            float* d_out, void* stream) {
-  if (int rc = check_table_call(h, U, d_table)) return rc;
-  if (U == 0) return 0;
-  if (!d_out) return fail(h, "d_out is NULL");
-  return table_forward(h, d_bits, U, d_params, d_table, d_out, false, static_cast<hipStream_t>(stream));
+  return table_forward(h, d_bits, U, d_params, d_table, d_out, false, stream);
 }
 
 int qhbm_table_expectation_retain(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, const float* d_table,
                                   float* d_out, void* stream) {
-  if (int rc = check_table_call(h, U, d_table)) return rc;
-  if (U == 0) return 0;
-  if (!d_out) return fail(h, "d_out is NULL");
-  return table_forward(h, d_bits, U, d_params, d_table, d_out, true, static_cast<hipStream_t>(stream));
+  return table_forward(h, d_bits, U, d_params, d_table, d_out, true, stream);
 }
 
 int qhbm_table_expectation_vjp(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, const float* d_table,
                                const float* d_upstream, float* d_out_vals, float* d_grad, float* d_table_grad,
                                void* stream) {
-  if (int rc = check_table_call(h, U, d_table)) return rc;
+  if (int rc = begin_call(h, U, kNeedTable, d_table)) return rc;
   if (!d_grad || (U > 0 && !d_upstream)) return fail(h, "d_grad / d_upstream is NULL");
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (U == 0) {
     h->retained_U = 0;
-    if (h->model.n_params) HIPCHK(launch_zero_fill(d_grad, size_t(h->model.n_params) * sizeof(float), s));
+    if (int rc = empty_batch_grad(h, d_grad, s)) return rc;
     if (d_table_grad) HIPCHK(launch_zero_fill(d_table_grad, (size_t(1) << h->model.n) * sizeof(float), s));
     return 0;
   }
@@ -2582,7 +2632,7 @@ int qhbm_table_expectation_vjp(qhbm_engine* h, const int8_t* d_bits, int U, cons
 int qhbm_table_expectation_vjp_retained(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params,
                                         const float* d_table, const float* d_upstream, float* d_grad,
                                         float* d_table_grad, void* stream) {
-  if (int rc = check_table_call(h, U, d_table)) return rc;
+  if (int rc = begin_call(h, U, kNeedTable, d_table)) return rc;
   if (U <= 0 || h->retained_U != U || !h->retained_table)
     return fail(h, "no retained energy-table forward state for this batch");
   if (!d_grad || !d_upstream) return fail(h, "d_grad / d_upstream is NULL");
@@ -2672,22 +2722,16 @@ int qhbm_sample(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_para
   if (int rc = upload_model(h)) return rc;
   if (U == 0 || n_shots == 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  DevicePlan& d = h->fwd;
-  h->retained_U = 0;
-  if (int rc = prepare_coefs(h, d, d_params, shift_gate, shift, s)) return rc;
-  if (int rc = values_begin(h, U, s)) return rc;
-  const uint32_t cs = std::min<uint32_t>(chunk_states(h, U), 65535u);
-  if (int rc = ensure_state_buffers(h, cs, false)) return rc;
-  const uint32_t n_eff = uint32_t(d.plan.n_eff);
-  HIPCHK(h->block_cum.reserve(size_t(cs) << (n_eff - 10)));
-  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += cs) {
-    const uint32_t c = std::min<uint32_t>(cs, uint32_t(U) - s0);
-    if (int rc = run_forward_chunk(h, d_bits, s0, c, true, s)) return rc;
-    // shots are drawn in slices of <= 65535 (grid.x); the shot index feeds the counter RNG
-    HIPCHK(launch_sample(h->psi.p, n_eff, h->model.n, c, h->block_cum.p, uint32_t(n_shots), seed, s0,
-                         d_out_samples, s));
-  }
-  return 0;
+  const uint32_t n_eff = uint32_t(h->fwd.plan.n_eff);
+  Sweep sw{d_bits, U, d_params, Chunks::kShots, shift_gate, shift};
+  sw.keep_state = sw.values = true;  // (measurement by-products land in the fixed-point scratch)
+  return run_sweep(
+      h, sw, s, [&](uint32_t cs) -> int { HIPCHK(h->block_cum.reserve(size_t(cs) << (n_eff - 10))); return 0; },
+      [&](uint32_t s0, uint32_t c) -> int {
+        // shots are drawn in slices of <= 65535 (grid.x); the shot index feeds the counter RNG
+        HIPCHK(launch_sample(h->psi.p, n_eff, h->model.n, c, h->block_cum.p, uint32_t(n_shots), seed, s0, d_out_samples, s));
+        return 0;
+      });
 }
 
 int qhbm_sample_counts(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, int n_programs,
@@ -2698,17 +2742,12 @@ int qhbm_sample_counts(qhbm_engine* h, const int8_t* d_bits, int U, const float*
   if (U < 0 || n_shots < 0 || n_programs < 0) return fail(h, "negative batch size, program or shot count");
   if (n_programs && (!shift_gates || !shifts)) return fail(h, "shift_gates / shifts are NULL");
   if (h->model.n > 24) return fail(h, "qhbm_sample_counts keeps 2^n counters per (program, state): n_qubits <= 24; use qhbm_sample");
-  for (int q = 0; q < n_programs; ++q)
-    if (shift_gates[q] >= int(h->model.gates.size())) return fail(h, "shift_gates entry out of range");
-  for (int q = 0; q < n_programs; ++q)
-    if (shift_gates[q] >= 0 && shifts[q] != 0.f && h->model.gates[size_t(shift_gates[q])].param_idx < 0)
-      return fail(h, "shift_gates entry addresses a gate with a constant exponent: only parametrised gates have shifted programs");
+  if (int rc = check_shifted_programs(h, n_programs, shift_gates, shifts, false)) return rc;
   if (int rc = upload_model(h)) return rc;
   if (U == 0 || n_programs == 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
   DevicePlan& d = h->fwd;
-  h->retained_U = 0;
-  h->state_grad_U = 0;
+  consume_workspace(h);
   // every program from pass 0, in the caller's order (no prefix sharing here)
   const uint32_t n_prog = uint32_t(n_programs), n_eff = uint32_t(d.plan.n_eff);
   const ProgramOrder order = order_programs(d.plan, h->model.gates.size(), shift_gates, n_prog, false, true);
@@ -2720,17 +2759,14 @@ int qhbm_sample_counts(qhbm_engine* h, const int8_t* d_bits, int U, const float*
   if (int rc = grow_coef_batch(h, g, s)) return rc;
   if (n_eff > uint32_t(kMinTileBits))
     HIPCHK(launch_zero_fill(d_out_counts, ((size_t(n_prog) * size_t(U)) << h->model.n) * sizeof(int32_t), s));
-  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += g.Uc) {
-    const uint32_t c = std::min<uint32_t>(g.Uc, uint32_t(U) - s0);
+  return for_each_chunk(U, g.Uc, [&](uint32_t s0, uint32_t c) -> int {
     auto draw = [&](uint32_t q0, uint32_t nq) -> int {
       HIPCHK(launch_sample_counts(h->psi.p, n_eff, h->model.n, nq * c, c, q0, h->block_cum.p, uint32_t(n_shots), seed, s0,
                                   uint32_t(U), d_out_counts, s));
       return 0;
     };
-    if (int rc = run_program_groups(h, d_bits, d_params, g, order, 0u, n_prog, s0, c, nullptr, {true, true, false}, s, draw))
-      return rc;
-  }
-  return 0;
+    return run_program_groups(h, d_bits, d_params, g, order, 0u, n_prog, s0, c, nullptr, {true, true, false}, s, draw);
+  });
 }
 
 int qhbm_sample_parities(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params, int n_programs,
@@ -2742,19 +2778,14 @@ int qhbm_sample_parities(qhbm_engine* h, const int8_t* d_bits, int U, const floa
   if (h->model.n < 1 || h->model.n > 31) return fail(h, "qhbm_sample_parities needs a circuit of 1 .. 31 qubits (qhbm_set_circuit)");
   std::vector<uint32_t> idx_masks;
   if (int rc = check_parity_masks(h, h->model.n, masks, T, n_shots, &idx_masks)) return rc;
-  for (int q = 0; q < n_programs; ++q)
-    if (shift_gates[q] >= int(h->model.gates.size())) return fail(h, "shift_gates entry out of range");
-  for (int q = 0; q < n_programs; ++q)
-    if (shift_gates[q] >= 0 && shifts[q] != 0.f && h->model.gates[size_t(shift_gates[q])].param_idx < 0)
-      return fail(h, "shift_gates entry addresses a gate with a constant exponent: only parametrised gates have shifted programs");
+  if (int rc = check_shifted_programs(h, n_programs, shift_gates, shifts, false)) return rc;
   if (U && n_programs && !d_out) return fail(h, "d_out is NULL");
   if (int rc = need_device(h)) return rc;
   if (int rc = upload_model(h)) return rc;
   if (U == 0 || n_programs == 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
   DevicePlan& d = h->fwd;
-  h->retained_U = 0;
-  h->state_grad_U = 0;
+  consume_workspace(h);
   const uint32_t n_prog = uint32_t(n_programs), n_eff = uint32_t(d.plan.n_eff);
   HIPCHK(launch_zero_fill(d_out, size_t(n_prog) * size_t(U) * size_t(T) * sizeof(int32_t), s));
   if (n_shots == 0) return 0;
@@ -2776,17 +2807,14 @@ int qhbm_sample_parities(qhbm_engine* h, const int8_t* d_bits, int U, const floa
   if (int rc = values_begin(h, int(g.Uc * g.Pc), s)) return rc;  // measurement by-products land in the fixed-point scratch
   if (int rc = grow_coef_batch(h, g, s)) return rc;
   HIPCHK(launch_shot_parity_masks(idx_masks.data(), uint32_t(T), h->par_masks.p, s));
-  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += g.Uc) {
-    const uint32_t c = std::min<uint32_t>(g.Uc, uint32_t(U) - s0);
+  return for_each_chunk(U, g.Uc, [&](uint32_t s0, uint32_t c) -> int {
     auto draw = [&](uint32_t q0, uint32_t nq) -> int {
       HIPCHK(launch_shot_parities(h->psi.p, n_eff, h->model.n, nq * c, c, q0, h->par_tables.p, h->par_masks.p, uint32_t(T),
                                   uint32_t(n_shots), seed, s0, uint32_t(U), 0u, 0u, d_out, s));
       return 0;
     };
-    if (int rc = run_program_groups(h, d_bits, d_params, g, order, 0u, n_prog, s0, c, nullptr, {true, true, false}, s, draw))
-      return rc;
-  }
-  return 0;
+    return run_program_groups(h, d_bits, d_params, g, order, 0u, n_prog, s0, c, nullptr, {true, true, false}, s, draw);
+  });
 }
 
 int qhbm_sample_parities_scratch_bytes(int M, int n_qubits, int64_t n_shots, size_t* out) {
@@ -2827,25 +2855,14 @@ int qhbm_sample_parities_states(const void* d_states, int M, int n_qubits, const
 int qhbm_expectation_vjp(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params,
                          const float* d_upstream, float* d_out_vals, float* d_grad, int method,
                          void* stream) {
-  if (int rc = check_call(h, U)) return rc;
+  if (int rc = begin_call(h, U, kNeedObservables)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int P = h->model.n_params;
-  if (U == 0) {
-    if (P) HIPCHK(launch_zero_fill(d_grad, size_t(P) * sizeof(float), s));
-    return 0;
-  }
-  const size_t nv = size_t(U) * h->model.n_ops;
-  if (!d_out_vals) {
-    HIPCHK(h->vals_tmp.reserve(nv));
-    d_out_vals = h->vals_tmp.p;
-  }
+  if (U == 0) return empty_batch_grad(h, d_grad, s);
+  if (int rc = values_or_scratch(h, U, &d_out_vals)) return rc;
   if (method == QHBM_GRAD_ADJOINT) {
     if (int rc = adjoint_sweep(h, d_bits, U, d_params, d_upstream, d_out_vals, s)) return rc;
-    HIPCHK(launch_reduce_grad(h->state_grad.p, uint32_t(U), uint32_t(h->adj.plan.slot_gate.size()),
-                              h->param_slot_begin.p, h->param_slots.p, h->slot_factor.p, d_grad, P, 0, s));
-    h->state_grad_U = U;
-    h->state_grad_dense = false;
-    return 0;
+    return reduce_state_grad(h, U, d_grad, false, true, s);
   }
   if (method != QHBM_GRAD_PARAMETER_SHIFT) return fail(h, "unknown gradient method");
   // tfq ParameterShift / baselines/train.py:190-240: exponent c*s -> shift the gate's exponent by
@@ -2863,7 +2880,7 @@ int qhbm_expectation_vjp(qhbm_engine* h, const int8_t* d_bits, int U, const floa
       const Gate& G = h->model.gates[g];
       if (G.param_idx < 0 || G.kind == QHBM_GATE_I || h->model.frozen(G.param_idx)) continue;
       if (G.kind == QHBM_GATE_ISWAPPOW)
-        return fail(h, "the two-term parameter-shift rule does not apply to ISWAPPOW; use the adjoint method");
+        return fail(h, kNoTwoTermRule);
       sg.push_back(int(g)); sg.push_back(int(g));
       sv.push_back(0.5f); sv.push_back(-0.5f);
       sp.push_back(G.param_idx);
@@ -2880,10 +2897,7 @@ int qhbm_expectation_vjp(qhbm_engine* h, const int8_t* d_bits, int U, const floa
     h->shift_ready = true;
   }
   const uint32_t n_prog = h->shift_programs, n_shift_gates = h->shift_gate_count;
-  if (n_prog == 0) {
-    if (P) HIPCHK(launch_zero_fill(d_grad, size_t(P) * sizeof(float), s));
-    return 0;
-  }
+  if (n_prog == 0) return empty_batch_grad(h, d_grad, s);
   const LaunchSets g = launch_set_geometry(h, U, n_prog, h->shift_order, 1, false, true);
   if (int rc = ensure_state_buffers(h, g.Uc * g.Pc, false)) return rc;
   if (g.share) HIPCHK(h->lam.reserve(size_t(g.Uc) << d.plan.n_eff, false));   // the base states live where lambda would
@@ -2894,14 +2908,12 @@ int qhbm_expectation_vjp(qhbm_engine* h, const int8_t* d_bits, int U, const floa
   HIPCHK(h->prog_acc.reserve(n_prog));
   HIPCHK(launch_zero_fill(h->prog_acc.p, size_t(n_prog) * sizeof(double), s));
   if (int rc = grow_coef_batch(h, g, s)) return rc;
-  h->retained_U = 0;
-  h->state_grad_U = 0;
+  consume_workspace(h);
   // The values of a shifted program come the way a forward-only call takes them: where that is the observable kernel
   // (wide terms: lean passes, then one sweep over the final states, the lower block of every pair only), the
   // shifted programs do the same -- config 4's 480 masks cost 51 measurement passes per program otherwise.  The base
   // program's coefficients are those the forward call above prepared.
-  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += g.Uc) {
-    const uint32_t c = std::min<uint32_t>(g.Uc, uint32_t(U) - s0);
+  if (int rc = for_each_chunk(U, g.Uc, [&](uint32_t s0, uint32_t c) -> int {
     auto accumulate = [&](uint32_t q0, uint32_t nq) -> int {
       if (from_obs)
         if (int rc = run_values_chunk(h, 0u, nq * c, s)) return rc;
@@ -2909,10 +2921,10 @@ int qhbm_expectation_vjp(qhbm_engine* h, const int8_t* d_bits, int U, const floa
       HIPCHK(launch_shift_program_accumulate(h->vals_batch.p, d_upstream, nq, c, T, s0, h->prog_acc.p, s, h->shift_dst.p + q0));
       return 0;
     };
-    if (int rc = run_program_groups(h, d_bits, d_params, g, h->shift_order, 0u, n_prog, s0, c, h->lam.p,
-                                    {from_obs, from_obs, true}, s, accumulate))
-      return rc;
-  }
+    return run_program_groups(h, d_bits, d_params, g, h->shift_order, 0u, n_prog, s0, c, h->lam.p, {from_obs, from_obs, true}, s,
+                              accumulate);
+  }))
+    return rc;
   HIPCHK(launch_shift_combine(h->prog_acc.p, h->shift_param.p, h->shift_weight.p, int(n_shift_gates), d_grad, P, s));
   return 0;
 }
@@ -2932,18 +2944,9 @@ int qhbm_program_vjps(qhbm_engine* h, const int8_t* d_bits, int U, const float* 
   if (!h) return 1;
   if (n_programs < 0) return fail(h, "n_programs must be >= 0");
   if (n_programs && (!shift_gates || !shifts)) return fail(h, "shift_gates / shifts are NULL");
-  if (int rc = check_call(h, U)) return rc;
+  if (int rc = begin_call(h, U, kNeedObservables)) return rc;
   const int n_gates = int(h->model.gates.size());
-  for (int q = 0; q < n_programs; ++q) {
-    const int g = shift_gates[q];
-    if (g >= n_gates) return fail(h, "shift_gates entry out of range");
-    if (g < 0) continue;
-    const Gate& G = h->model.gates[size_t(g)];
-    if (shifts[q] != 0.f && G.kind == QHBM_GATE_ISWAPPOW)
-      return fail(h, "the two-term parameter-shift rule does not apply to ISWAPPOW; use the adjoint method");
-    if (shifts[q] != 0.f && G.param_idx < 0)
-      return fail(h, "shift_gates entry addresses a gate with a constant exponent: only parametrised gates have shifted programs");
-  }
+  if (int rc = check_shifted_programs(h, n_programs, shift_gates, shifts, true)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int P = h->model.n_params;
   const uint32_t T = uint32_t(h->model.n_ops), n_prog = uint32_t(n_programs);
@@ -2955,9 +2958,8 @@ int qhbm_program_vjps(qhbm_engine* h, const int8_t* d_bits, int U, const float* 
   }
   DevicePlan& d = h->fwd;
   DevicePlan& b = h->adj;
-  h->retained_U = 0;
-  h->state_grad_U = 0;
-  const uint32_t n_slots = uint32_t(b.plan.slot_gate.size()), ns1 = std::max<uint32_t>(n_slots, 1);
+  consume_workspace(h);
+  const uint32_t n_slots = uint32_t(b.plan.slot_gate.size()), ns1 = grad_slots(h);
   // values and lambda exactly as the adjoint VJP (adjoint_sweep) takes them: an unshifted program is its d_grad bit for bit
   const bool vm = value_mode(h), mv = multi_value_mode(h), gm = mv && gather_multi_mode(h), skip = vm || mv;
   const ProgramOrder order = order_programs(d.plan, size_t(n_gates), shift_gates, n_prog, h->opt_shift_prefix != 0, skip);
@@ -2989,7 +2991,7 @@ int qhbm_program_vjps(qhbm_engine* h, const int8_t* d_bits, int U, const float* 
   HIPCHK(h->pv_upstream.reserve(ne_max * T));
   HIPCHK(h->vals64.reserve(ne_max * T));
   HIPCHK(h->vals_batch.reserve(ne_max * T));
-  HIPCHK(h->state_grad.reserve(ne_max * ns1));
+  HIPCHK(reserve_state_grad(h, ne_max));
   HIPCHK(h->pv_rows.reserve(size_t(R) * U * ns1, false));
   HIPCHK(h->pv_vals.reserve(size_t(n_prog) * T));
   HIPCHK(launch_zero_fill(h->pv_vals.p, size_t(n_prog) * T * sizeof(double), s));
@@ -3010,7 +3012,7 @@ int qhbm_program_vjps(qhbm_engine* h, const int8_t* d_bits, int U, const float* 
         const uint32_t ne = nq * c;
         if (mv && !gm)
           if (int rc = run_values_chunk(h, 0u, ne, s)) return rc;
-        HIPCHK(launch_zero_fill(h->state_grad.p, size_t(ne) * ns1 * sizeof(float), s));
+        HIPCHK(begin_state_grad(h, ne, s));
         if (int rc = run_observable_chunk(h, 0u, ne, h->pv_upstream.p, vm, s, true, gm)) return rc;
         // backward sweeps: runs of programs on the shared coefficients, a program behind the first live gate on its own
         for (uint32_t j = 0; j < nq;) {
@@ -3027,8 +3029,7 @@ int qhbm_program_vjps(qhbm_engine* h, const int8_t* d_bits, int U, const float* 
           if (int rc = run_adjoint_chunk(h, h->pv_bits.p, j * c, (j1 - j) * c, s, j * c)) return rc;
           j = j1;
         }
-        // value mode: the sweep ran on the unweighted lambda, the upstream weight goes onto the rows (as adjoint_sweep)
-        if (vm) HIPCHK(launch_scale_rows(h->state_grad.p, ne, ns1, h->pv_upstream.p, s));
+        if (vm) HIPCHK(weight_state_grad(h, ne, h->pv_upstream.p, s));
         HIPCHK(launch_scatter_program_rows(h->state_grad.p, h->pv_rows.p, n_slots, c, s0, uint32_t(U), q0 - qa, ne, s));
         HIPCHK(launch_values_from_fixed(h->vals64.p, h->op_inv_scale.p, h->vals_batch.p, ne * T, T, s));
         HIPCHK(launch_accumulate_program_values(h->vals_batch.p, d_row_weights, nq, c, T, s0, h->shift_dst.p + q0,
@@ -3050,16 +3051,13 @@ int qhbm_program_vjps(qhbm_engine* h, const int8_t* d_bits, int U, const float* 
 
 int qhbm_expectation_jacobian(qhbm_engine* h, const int8_t* d_bits, int U, const float* d_params,
                               float* d_out_vals, float* d_jac, void* stream) {
-  if (int rc = check_call(h, U)) return rc;
+  if (int rc = begin_call(h, U, kNeedObservables)) return rc;
   if (U == 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int T = h->model.n_ops, P = h->model.n_params;
   const size_t nv = size_t(U) * T;
   HIPCHK(h->upstream_tmp.reserve(nv));
-  if (!d_out_vals) {
-    HIPCHK(h->vals_tmp.reserve(nv));
-    d_out_vals = h->vals_tmp.p;
-  }
+  if (int rc = values_or_scratch(h, U, &d_out_vals)) return rc;
   std::vector<float> up(nv);
   for (int k = 0; k < T; ++k) {
     for (size_t i = 0; i < nv; ++i) up[i] = (int(i % size_t(T)) == k) ? 1.f : 0.f;
@@ -3084,12 +3082,7 @@ int qhbm_num_passes(qhbm_engine* h, int* forward_passes, int* backward_passes) {
 int qhbm_describe_schedule(qhbm_engine* h, char* buf, size_t buf_len) {
   if (!h || !buf || !buf_len) return 1;
   if (int rc = build_plans(h)) return rc;
-  std::string s = describe_plan(h->fwd.plan) + describe_plan(h->adj.plan);
-  {  // what the chooser of the adjoint tile and pass order compares (adjoint_plan_seconds)
-    char line[96];
-    std::snprintf(line, sizeof(line), "adjoint time model: %.2f us per state\n", 1e6 * adjoint_plan_seconds(h->adj.plan, h->model));
-    s += line;
-  }
+  std::string s = describe_plans(h);
   if (!h->model.terms.empty()) {  // which kernel forms lambda = O psi / the values (bench.py names it in `roofline.kernel`)
     s += std::string("observable kernel: lambda = ") + (block_kernel(h) ? "observable_blocks_kernel" : "apply_observable_kernel");
     s += std::string(" values = ") + (gather_multi_mode(h) ? "apply_observable_kernel (an accumulator per observable)"
