@@ -489,6 +489,38 @@ int qhbm_subsystem_apply_scratch_bytes(int M, int n_qubits, uint64_t keep_mask, 
 int qhbm_subsystem_apply(const void* d_states, int M, int n_qubits, uint64_t keep_mask, const void* d_operator,
                          const double* d_scale, void* d_out, double* d_dots, void* d_scratch, void* stream);
 
+/* ---- The VJP of the weighted Gram matrix: state metrics as losses ----
+ * Added WITHIN ABI version 5: purely additive, QHBM_ABI_VERSION stays 5.
+ *
+ *   c_j(x) = sum_i H[i, j] a_i(x),    out_j(x) = t(x) c_j(x),    table_grad(x) = 1/2 sum_j Re(conj(c_j(x)) a_j(x))
+ * for the M states a_i and the table t of qhbm_weighted_gram.  For a real loss L of G with cotangent
+ * Gamma = dL/dRe G + i dL/dIm G, H = Gamma + Gamma^H gives the cotangent of the states in `out` and that of the table in
+ * `table_grad`.  H is used as given: the call does not symmetrise it.
+ *
+ *   qhbm_weighted_gram_vjp   d_states, d_out_states [M, 2^n_qubits] complex64, interleaved, 16-byte aligned, not
+ *                            overlapping; d_table [2^n_qubits] float32, 8-byte aligned, or NULL for t = 1 (out = c);
+ *                            d_cotangent = H, [M, M] complex64, row-major, 8-byte aligned; d_table_grad [2^n_qubits]
+ *                            float64; all on the device.  Either of d_out_states and d_table_grad may be NULL and is then
+ *                            not computed; the other's bits do not change.  No engine: the current device.  Asynchronous
+ *                            on `stream`; allocates nothing, synchronises nothing.  d_scratch:
+ *                            qhbm_gram_vjp_scratch_bytes bytes, 8-byte aligned, which may hold anything.
+ *                            Arithmetic: c_j(x) is an f32 fused-multiply-add chain over i ascending of the real embedding
+ *                            Re = H_r a_r - H_i a_i, Im = H_r a_i + H_i a_r (M <= 8 vector code, M >= 9
+ *                            v_mfma_f32_16x16x4_f32, which is such a chain bit for bit); out = t c, one rounding per
+ *                            part.  table_grad: the unscaled c times a, float x float in float64 (exact), Re then Im,
+ *                            j ascending in one accumulator, halved at the end; one workgroup finishes an x, so there
+ *                            are no partials and no floating-point atomics: two calls give the same bits.
+ *                            Refused, each with a message and before anything is launched: the shapes qhbm_weighted_gram
+ *                            refuses; d_states, d_cotangent or d_scratch NULL; d_out_states and d_table_grad both NULL;
+ *                            a misaligned pointer; d_out_states overlapping d_states.
+ *   qhbm_gram_vjp_scratch_bytes  *out = the bytes of d_scratch such a call needs (csrc/gram_vjp_plan.h gv_plan: 16 for
+ *                            M <= 8, where none is used; above, H as two zero-padded float planes, 8 P^2 bytes with
+ *                            P = 16 ceil(M / 16) up to 64 and 64 ceil(M / 64) beyond); needs no device.  Refused: M or
+ *                            n_qubits as above, out NULL. */
+int qhbm_gram_vjp_scratch_bytes(int M, int n_qubits, size_t* out);
+int qhbm_weighted_gram_vjp(const void* d_states, int M, int n_qubits, const float* d_table, const void* d_cotangent,
+                           void* d_out_states, double* d_table_grad, void* d_scratch, void* stream);
+
 /* Computational-basis samples of the final states (tfq.layers.Sample as used at
  * qhbmlib/inference/qnn.py:169,177-181,286-291):
  *   d_out_samples [U, n_shots, n_qubits] int8 (device); shot j of state u is drawn from

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/qhbm_engine.h"
+#include "gram_vjp_plan.h"
 #include "kernels.h"
 #include "plan_args.h"
 #include "program.h"
@@ -2589,6 +2590,36 @@ int qhbm_subsystem_apply(const void* d_states, int M, int n_qubits, uint64_t kee
                                         static_cast<const float2*>(d_operator), d_scale, static_cast<float2*>(d_out), d_dots,
                                         d_scratch, static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return fail(nullptr, std::string("qhbm_subsystem_apply: ") + hipGetErrorString(e));
+  return 0;
+}
+
+// ---- the VJP of the weighted Gram matrix (include/qhbm_engine.h; gram_vjp.hip, gram_vjp_plan.h) ----
+int qhbm_gram_vjp_scratch_bytes(int M, int n_qubits, size_t* out) {
+  if (!out) return fail(nullptr, "out is NULL");
+  if (int rc = check_gram_shape(M, n_qubits)) return rc;
+  *out = gv_plan(n_qubits, M).scratch_bytes;
+  return 0;
+}
+
+int qhbm_weighted_gram_vjp(const void* d_states, int M, int n_qubits, const float* d_table, const void* d_cotangent,
+                           void* d_out_states, double* d_table_grad, void* d_scratch, void* stream) {
+  if (int rc = check_gram_shape(M, n_qubits)) return rc;
+  if (int rc = check_pointer(nullptr, d_states, 16, "d_states")) return rc;
+  if (d_table)
+    if (int rc = check_pointer(nullptr, d_table, 8, "d_table")) return rc;
+  if (int rc = check_pointer(nullptr, d_cotangent, 8, "d_cotangent")) return rc;
+  if (!d_out_states && !d_table_grad) return fail(nullptr, "d_out_states and d_table_grad are both NULL: nothing to compute");
+  if (d_out_states)
+    if (int rc = check_pointer(nullptr, d_out_states, 16, "d_out_states")) return rc;
+  if (d_table_grad)
+    if (int rc = check_pointer(nullptr, d_table_grad, 8, "d_table_grad")) return rc;
+  if (int rc = check_pointer(nullptr, d_scratch, 8, "d_scratch")) return rc;
+  const size_t bytes = size_t(M) * (size_t(8) << n_qubits);
+  if (d_out_states && ranges_overlap(d_out_states, bytes, d_states, bytes)) return fail(nullptr, "d_out_states overlaps d_states");
+  hipError_t e = launch_gram_vjp(static_cast<const float2*>(d_states), uint32_t(M), uint32_t(n_qubits), d_table,
+                                 static_cast<const float2*>(d_cotangent), static_cast<float2*>(d_out_states), d_table_grad,
+                                 d_scratch, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, std::string("qhbm_weighted_gram_vjp: ") + hipGetErrorString(e));
   return 0;
 }
 

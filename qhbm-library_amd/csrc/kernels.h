@@ -1,5 +1,5 @@
 // kernels.h -- launch entry points of the kernel objects (host side): kernels.hip (the pass kernels, with gwg.hip and
-// parity_table.hip), observable.hip (with energy_table.hip, cotangent.hip and subsystem_apply.hip) and states.hip (import_states.hip, thermal.hip, krylov.hip,
+// parity_table.hip), observable.hip (with energy_table.hip, cotangent.hip, subsystem_apply.hip and gram_vjp.hip) and states.hip (import_states.hip, thermal.hip, krylov.hip,
 // gram.hip, reduced.hip).  A .hip file reaches another one's kernels through these declarations only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -353,5 +353,13 @@ hipError_t launch_cotangent_phase_grad(const double* dot, const double* norm2, u
 // Shape limits as launch_reduced_density.  `scratch`: sub_plan(n, keep_mask, M).scratch_bytes bytes, which may hold anything.
 hipError_t launch_subsystem_apply(const float2* states, uint32_t M, uint32_t n, uint64_t keep_mask, const float2* op,
                                   const double* scale, float2* out, double* dots, void* scratch, hipStream_t stream);
+
+// ---- the VJP of the weighted Gram matrix (gram_vjp.hip; the plan is gram_vjp_plan.h's) ----
+// c_j(x) = sum_i H[i, j] states[i, x] in f32; out[j, x] = table[x] c_j(x) (table NULL: c itself), complex64 [M, 2^n], or NULL;
+// table_grad[x] = 1/2 sum_j Re(conj(c_j(x)) states[j, x]), fp64 in a fixed order, [2^n], or NULL (not both).  H [M, M]
+// complex64 row-major, used as given.  Shape limits as launch_weighted_gram.  `scratch`: gv_plan(n, M).scratch_bytes bytes,
+// which may hold anything.
+hipError_t launch_gram_vjp(const float2* states, uint32_t M, uint32_t n, const float* table, const float2* H, float2* out,
+                           double* table_grad, void* scratch, hipStream_t stream);
 
 }  // namespace qhbm

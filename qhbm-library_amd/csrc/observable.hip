@@ -699,3 +699,7 @@ hipError_t launch_observable_blocks(int mode, int block_bits, const float2* psi,
 // A dense operator on k qubits of every state -- the cotangent of the states of a reduced density matrix -- likewise (it
 // shares rdm_index.h with reduced.hip and no name with any other .hip file).
 #include "subsystem_apply.hip"
+
+// The VJP of the weighted Gram matrix -- the cotangents of the states and of the table of a state metric -- likewise (its
+// plan is gram_vjp_plan.h's, and it shares no name with any other .hip file).
+#include "gram_vjp.hip"

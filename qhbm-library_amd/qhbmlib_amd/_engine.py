@@ -51,6 +51,7 @@ ABI_SYMBOLS = (
     "qhbm_gram_scratch_bytes", "qhbm_weighted_gram",
     "qhbm_reduced_density_scratch_bytes", "qhbm_reduced_density",
     "qhbm_subsystem_apply_scratch_bytes", "qhbm_subsystem_apply",
+    "qhbm_gram_vjp_scratch_bytes", "qhbm_weighted_gram_vjp",
     "qhbm_sample_parities", "qhbm_sample_parities_scratch_bytes", "qhbm_sample_parities_states",
 )
 
@@ -159,6 +160,8 @@ def load_library():
     lib.qhbm_sample_parities_scratch_bytes.argtypes = [i32, i32, i64, ctypes.POINTER(ctypes.c_size_t)]
     lib.qhbm_sample_parities_states.argtypes = [vp, i32, i32, vp, i32, i64, ctypes.c_uint64, ctypes.c_uint64,
                                                 ctypes.c_uint32, vp, vp, vp]
+    lib.qhbm_gram_vjp_scratch_bytes.argtypes = [i32, i32, ctypes.POINTER(ctypes.c_size_t)]
+    lib.qhbm_weighted_gram_vjp.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
   except AttributeError:  # an older library given through QHBM_ENGINE_LIB (A/B runs): the probe is optional there
     pass
   _lib = lib
@@ -494,6 +497,54 @@ def subsystem_apply(states, keep_mask, operator, scale=None, want_dots=False):
                                                       None if dots is None else dots.data_ptr(), scratch.data_ptr(),
                                                       torch.cuda.current_stream().cuda_stream))
   return (out, torch.view_as_complex(dots)) if want_dots else out
+
+
+def gram_vjp_scratch_bytes(num_states, n_qubits):
+  """Bytes of scratch one `qhbm_weighted_gram_vjp` of `num_states` states of `n_qubits` qubits needs (no device needed)."""
+  out = ctypes.c_size_t()
+  _check_global(load_library().qhbm_gram_vjp_scratch_bytes(int(num_states), int(n_qubits), ctypes.byref(out)))
+  return int(out.value)
+
+
+def weighted_gram_vjp(states, table, cotangent, want_states=True, want_table=True):
+  """The VJP of `weighted_gram` for M device-resident states [M, 2^n], its table (None: ones) and a cotangent matrix H
+  [M, M] (H = Gamma + Gamma^H for torch's cotangent Gamma of G; used as given): with c[j] = sum_i H[i, j] states[i],
+  (table * c as complex64 [M, 2^n], 1/2 sum_j Re(conj(c[j]) states[j]) as float64 [2^n]) -- the cotangents of the states and
+  of the table, from one pass in the HIP engine (include/qhbm_engine.h qhbm_weighted_gram_vjp); an output that is not
+  wanted is None and is not computed.  complex128 inputs are cast to complex64 and a float64 table to float32; the scratch is
+  this call's own.  Not differentiable."""
+  if not (torch.is_tensor(states) and states.is_cuda and states.dim() == 2 and states.is_complex()):
+    raise EngineError("weighted_gram_vjp needs complex CUDA states [M, 2^n]: the engine has no CPU fallback")
+  if not (want_states or want_table):
+    raise ValueError("weighted_gram_vjp: neither output is wanted")
+  states = states.detach().to(torch.complex64).contiguous()
+  if states.data_ptr() % 16:  # (a view at an odd offset: the entry point asks for 16-byte alignment)
+    states = states.clone()
+  num, dim = (int(v) for v in states.shape)
+  n = dim.bit_length() - 1
+  if dim != (1 << n) or n < 1:
+    raise ValueError(f"states have {dim} amplitudes: not a power of two, or fewer than two")
+  if table is not None:
+    if not (torch.is_tensor(table) and table.is_cuda and table.device == states.device):
+      raise EngineError("weighted_gram_vjp needs the table on the states' device")
+    if tuple(table.shape) != (dim,):
+      raise ValueError(f"table must have shape [{dim}], got {tuple(table.shape)}")
+    table = table.detach().to(torch.float32).contiguous()
+    if table.data_ptr() % 8:
+      table = table.clone()
+  cotangent = torch.as_tensor(cotangent)
+  if not cotangent.is_complex() or tuple(cotangent.shape) != (num, num):
+    raise ValueError(f"cotangent must be complex of shape [{num}, {num}], got {cotangent.dtype} {tuple(cotangent.shape)}")
+  cotangent = cotangent.detach().to(device=states.device, dtype=torch.complex64).contiguous()
+  with torch.cuda.device(states.device):
+    scratch = torch.empty(gram_vjp_scratch_bytes(num, n) // 8, dtype=torch.float64, device=states.device)
+    out = torch.empty_like(states) if want_states else None
+    grad = torch.empty(dim, dtype=torch.float64, device=states.device) if want_table else None
+    _check_global(load_library().qhbm_weighted_gram_vjp(states.data_ptr(), num, n, None if table is None else table.data_ptr(),
+                                                        cotangent.data_ptr(), None if out is None else out.data_ptr(),
+                                                        None if grad is None else grad.data_ptr(), scratch.data_ptr(),
+                                                        torch.cuda.current_stream().cuda_stream))
+  return out, grad
 
 
 def _parity_masks(masks):

@@ -191,16 +191,18 @@ class StateVectorData(QuantumData):
 
   def metrics(self, model, **kwargs):
     """`inference.state_metrics(model, self, **kwargs)`: trace, purity, entropy, overlap, fidelity, cross entropy and
-    relative entropy of this data against the QHBM `model`, matrix-free.  Not differentiable."""
+    relative entropy of this data against the QHBM `model`, matrix-free: python floats, or with
+    `differentiable=True` 0-dim tensors that train the model's variables."""
     from qhbmlib_amd.inference.state_metrics import state_metrics  # pylint: disable=import-outside-toplevel
     return state_metrics(model, self, **kwargs)
 
   def fidelity(self, model, **kwargs):
-    """(tr sqrt(sqrt(sigma) rho sqrt(sigma)))^2 against the QHBM `model`, as a float."""
+    """(tr sqrt(sqrt(sigma) rho sqrt(sigma)))^2 against the QHBM `model`, as a float; `differentiable=True`: as a loss."""
     return self.metrics(model, **kwargs).fidelity
 
   def relative_entropy(self, model, **kwargs):
-    """D(sigma || rho) = tr sigma (log sigma - log rho) against the QHBM `model`, as a float."""
+    """D(sigma || rho) = tr sigma (log sigma - log rho) against the QHBM `model`, as a float; `differentiable=True`: as a
+    loss."""
     return self.metrics(model, **kwargs).relative_entropy
 
   def reduced(self, qubits, rtol=1e-10):

@@ -17,7 +17,7 @@ from qhbmlib_amd.inference.qnn_utils import unitary
 from qhbmlib_amd.inference.reduced import (apply_operator, mutual_information, reduced_density_matrix,
                                            sampled_ensemble_reduced, sampled_reduced_density_matrix, subsystem_entropy,
                                            trace_distance)
-from qhbmlib_amd.inference.state_metrics import StateMetrics, state_metrics
+from qhbmlib_amd.inference.state_metrics import StateMetrics, state_metrics, weighted_gram
 from qhbmlib_amd.inference.thermal import (ThermalEnsemble, imaginary_time_evolution, real_time_evolution,
                                            thermal_ensemble)
 from qhbmlib_amd.inference.vqt_loss import vqt
@@ -28,4 +28,4 @@ __all__ = ["AnalyticEnergyInference", "AnalyticQuantumInference", "BernoulliEner
            "fidelity", "ground_state", "imaginary_time_evolution", "information_matrix", "krylov_space", "mutual_information",
            "natural_gradient", "probabilities", "qmhl", "real_time_evolution", "reduced_density_matrix",
            "sampled_ensemble_reduced", "sampled_reduced_density_matrix", "spectrum_extremes", "state_metrics", "subsystem_entropy", "thermal_ensemble",
-           "thermal_sweep", "trace_distance", "unitary", "vqt"]
+           "thermal_sweep", "trace_distance", "unitary", "vqt", "weighted_gram"]
