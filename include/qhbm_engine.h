@@ -170,7 +170,10 @@ int qhbm_set_observables(qhbm_engine* h, int n_ops, const int32_t* term_offsets,
  * pass stores its tiles), "x_two_shear" (1 = an X**t next to a full diagonal table whose angle is at most pi / 3
  * runs as two shears, its scaling folded into the table; 0 = always three shears), "forward_pairs" (1 = dense
  * lean forward passes run on pairs of states with the tiles in registers), "wide_last_pass" (-1 = the last forward gate pass may take a tile one or two bits
- * wider when that saves a pass, unless tile_qubits is set; 0 = never; 1 = always), "observable_xcd_states"
+ * wider when that saves a pass, unless tile_qubits is set; 0 = never; 1 = always), "forward_move_low_bits" (1 = a forward
+ * pass may leave any four of its index bits on the 128-byte line positions when it stores, where a cost model prefers
+ * the plan that results -- tiles of contiguous bits, fewer full passes; the last gate pass restores the layout; 0 = never:
+ * the plans and result bits of before; 2 = also with tile_qubits set and whenever such a plan exists), "observable_xcd_states"
  * (lambda = O psi: 1 = one state per XCD at a time, 0 = every XCD an eighth of each state, -1 = by state size: states of
  * 64 MiB and more are shared), "observable_kernel" (lambda = O psi and <psi|O|psi>: 0 = one L2 gather per X-mask and
  * block of 2^11 amplitudes, 1 = partner blocks of 2^13 amplitudes staged in LDS once per group of masks that share them

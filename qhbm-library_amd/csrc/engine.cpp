@@ -121,6 +121,7 @@ struct qhbm_engine {
   int opt_adj_stop_early = -1; // frozen parameters: the backward sweep stops at the first live gate (-1: if the time model says that is cheaper)
   int opt_adj_plan_search = 1; // adjoint: build the scheduler's best few pass orders and keep the one with the fewest model flops
   int opt_wide_last = -1;      // forward: the last gate pass may take a tile one or two bits wider (-1: unless tile_qubits is set)
+  int opt_fwd_move_low = 1;    // forward: a pass may move four of its bits onto the 128-byte line positions (schedule.h build_plan move_low_bits)
   int opt_fwd_pair = 1;        // dense lean forward passes run on pairs of states, tiles in registers (pass_fwd2_kernel)
   int opt_shift_prefix = 1;    // parameter shift: a shifted program starts at the pass that holds its gate, from the base program's state
   int opt_adj_relabel = 1;     // adjoint plans move finished index bits out of the 128-byte lines (schedule.h Pass)
@@ -433,11 +434,14 @@ void qhbm::fill_args(const Plan& plan, const Model& m, std::vector<PassArgs>* ar
     // differs from the input on such a bit among its NON-LOCAL bits is identically zero, stays zero
     // under the pass, and already reads as zeros in HBM (the first pass wrote them): the kernel
     // returns at once.  Config 3: half the tiles of the second (and heaviest) forward pass.
-    uint32_t touched = 0;  // (forward plans never relabel: logical = physical positions)
+    uint32_t touched = 0;  // logical bits
     for (size_t i = 0; i < args->size(); ++i) {
       uint32_t nl = 0;
       for (uint32_t k = 0; k < (*args)[i].n_nonlocal; ++k) nl |= 1u << (*args)[i].nonlocal_pos[k];
-      if (i > 0) (*args)[i].zero_mask = nl & ~touched;
+      uint32_t touched_phys = 0;  // ... at the positions they have when pass i loads its tiles (plans that move the low bits)
+      for (size_t bit = 0; bit < plan.passes[i].phys_of.size(); ++bit)
+        if (touched >> bit & 1u) touched_phys |= 1u << plan.passes[i].phys_of[bit];
+      if (i > 0) (*args)[i].zero_mask = nl & ~touched_phys;
       touched |= plan.passes[i].mat_bits;
     }
   }
@@ -502,6 +506,25 @@ double adjoint_plan_seconds(const Plan& plan, const Model& m) {
   return t;
 }
 
+// The layout a forward pass loads is the one the pass before it stored, and the circuit ends in logical = physical: a
+// function of the pass index alone.  Everything that enters the sweep behind pass 0 leans on this -- a shifted program
+// that starts at pass k from the base program's state (order_programs, psi_src), the base state advanced by pass k
+// (advance_base) -- and so does every consumer of final states.
+bool forward_layouts_chain(const Plan& plan) {
+  if (plan.passes.empty()) return true;
+  std::vector<int> layout = plan.passes[0].phys_of;
+  for (const Pass& p : plan.passes) {
+    if (p.phys_of != layout) return false;
+    if (!p.store_local_phys.empty()) {
+      if (p.store_local_phys.size() != p.local_pos.size() || !(p.flags & PASS_RELABEL)) return false;
+      for (size_t k = 0; k < p.local_pos.size(); ++k) layout[size_t(p.local_pos[k])] = p.store_local_phys[k];
+    }
+    if (p.completes_circuit || p.is_measure_only)
+      for (size_t b = 0; b < layout.size(); ++b) if (layout[b] != int(b)) return false;
+  }
+  return true;
+}
+
 int build_plans(qhbm_engine* h) {
   if (h->plans_valid && h->adj_valid) return 0;  // (whoever invalidated them dropped the retained states and the VJP rows)
   if (!h->have_circuit) return fail(h, "qhbm_set_circuit has not been called");
@@ -510,8 +533,9 @@ int build_plans(qhbm_engine* h) {
   if (!h->plans_valid) {  // (a change of the gradient mask alone keeps the forward plan: it does not depend on it)
     h->adj_cache.clear();
     if (!build_plan(h->model, h->opt_tile, h->opt_round, false, &h->fwd.plan, &err, h->opt_full_fwd, h->opt_meas_tile,
-                    h->opt_cph_wave_bits != 0, false, h->opt_wide_last))
+                    h->opt_cph_wave_bits != 0, false, h->opt_wide_last, nullptr, h->opt_fwd_move_low))
       return fail(h, "forward plan: " + err);
+    if (!forward_layouts_chain(h->fwd.plan)) return fail(h, "internal: the forward passes' layouts do not chain to the identity");
     h->fwd.uploaded = false;
     ++h->fwd_plans_built;
   }
@@ -1044,7 +1068,7 @@ PassArgs forward_pass_args(const qhbm_engine* h, size_t i, bool keep_state, bool
   bool read_after = keep_state || !plan.global_terms.empty();  // (global terms are measured on the final state in HBM)
   for (const Pass& q : plan.passes) read_after |= q.is_measure_only;
   PassArgs a = h->fwd.args[i];
-  a.flags = p.flags & (PASS_INIT_BASIS | PASS_GENERAL | PASS_NO_ZERO_FILL);
+  a.flags = p.flags & (PASS_INIT_BASIS | PASS_GENERAL | PASS_NO_ZERO_FILL | PASS_RELABEL);
   if (h->opt_force_general) a.flags |= PASS_GENERAL;
   if (skip_measure) a.flags |= PASS_SKIP_MEASURE;
   if (!p.is_measure_only && (!p.completes_circuit || read_after)) a.flags |= PASS_STORE;
@@ -1872,6 +1896,7 @@ int qhbm_set_option(qhbm_engine* h, const char* name, int64_t value) {
   else if (k == "adjoint_stop_early") { h->opt_adj_stop_early = int(value); invalidate_plans(h); }
   else if (k == "adjoint_plan_search") { h->opt_adj_plan_search = int(value); invalidate_plans(h); }
   else if (k == "wide_last_pass") { h->opt_wide_last = int(value); invalidate_plans(h); }
+  else if (k == "forward_move_low_bits") { h->opt_fwd_move_low = int(value); invalidate_plans(h); }
   else if (k == "observable_xcd_states") h->opt_obs_xcd_states = int(value);
   else if (k == "observable_kernel") { h->opt_obs_kernel = int(value); h->block_choice = -1; }
   else if (k == "observable_split_rows") h->opt_obs_split_rows = value != 0;

@@ -540,6 +540,73 @@ __device__ __forceinline__ uint32_t tile_base_of(const PassArgs& a, uint32_t til
   return ballot32((lane < 32) & ((((a.nonlocal_mask >> L) & (tile_id >> rank)) & 1u) != 0u));
 }
 
+// The relabeling store: only the amplitudes whose newly finished bits equal the input bitstring, in
+// the order of their NEW addresses (finished bits moved to the highest positions the tile owns):
+// whole 128-byte lines of live data, nothing written for the dead half.
+// Live out-index o -> (local index with the finished bits clear, offset in the state) is a table
+// (tables[relabel_off + 2 o]) that is OR-decomposable in o: a thread looks up the entry of ITS low part of o once
+// for both tiles (relabel_lookup) and ORs the entry of the iteration's high part, which the host put into the pass
+// arguments -- as a loop over table entries, every iteration of both stores waited for its own table load.
+struct RelabelCtx {
+  uint32_t l_mine, off_mine;  // the thread's own entry
+  uint32_t fz_addr;           // where the finished bits go in the address, carrying the input bits
+  uint32_t fz_local;          // the finished bits of the live amplitudes, local index space
+  uint32_t count;             // out-indices (pairs of them when relabel_pairs) the store covers
+};
+template <int K>
+__device__ __forceinline__ RelabelCtx relabel_lookup(const PassArgs& a, const uint32_t* __restrict__ tables, uint32_t in_local,
+                                                     int tid, int lane) {
+  RelabelCtx r;
+  const uint32_t n_live = uint32_t(K) - a.n_fz;
+  r.count = a.relabel_pairs ? 1u << (n_live - 1u) : 1u << n_live;
+  const uint32_t mine = min(uint32_t(tid), r.count - 1u) << (a.relabel_pairs ? 1 : 0);
+  const uint2 e = *reinterpret_cast<const uint2*>(tables + a.relabel_off + 2u * mine);
+  const uint32_t src = a.fz_src[uint32_t(lane) & 31u];
+  r.fz_addr = ballot32((lane < 32) & (src != 0xffu) & (((in_local >> (src & 31u)) & 1u) != 0u));
+  r.fz_local = in_local & a.frozen_new_local;
+  r.l_mine = e.x;
+  r.off_mine = e.y;
+  return r;
+}
+template <int K, int NT>
+__device__ __forceinline__ void store_tile_relabeled(const float2* __restrict__ tile, float2* __restrict__ st,
+                                                     const PassArgs& a, const RelabelCtx& r, uint32_t tile_base, int tid) {
+  float2* sb = st + (tile_base | r.fz_addr);
+  if (a.relabel_pairs) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      if (uint32_t(i) < a.relabel_iters && uint32_t(tid) + uint32_t(i * NT) < r.count) {
+        const uint32_t l0 = r.l_mine | a.relabel_hi[i][0] | r.fz_local;
+        const float2 v0 = tile[swz(l0)], v1 = tile[swz(l0 | a.relabel_l1)];
+        *reinterpret_cast<float4*>(sb + (r.off_mine | a.relabel_hi[i][1])) = make_float4(v0.x, v0.y, v1.x, v1.y);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      if (uint32_t(i) < a.relabel_iters && uint32_t(tid) + uint32_t(i * NT) < r.count)
+        sb[r.off_mine | a.relabel_hi[i][1]] = tile[swz(r.l_mine | a.relabel_hi[i][0] | r.fz_local)];
+    }
+  }
+}
+
+// The forward sweep's form of that store (plans that move the low bits: no finished bit, every amplitude of the tile,
+// consecutive out-indices adjacent in memory): a rolled loop over the table itself.  The forward kernels sit at their
+// register limit, and the unrolled form above, with its per-iteration words from the pass arguments, spilled there.
+template <int K, int NT, int UNROLL>
+__device__ __forceinline__ void store_tile_moved(const float2* __restrict__ tile, float2* __restrict__ st, const PassArgs& a,
+                                                 const uint32_t* __restrict__ tables, uint32_t tile_base, uint32_t tid) {
+  const uint32_t* __restrict__ tab = tables + a.relabel_off;
+  const uint32_t l1 = a.relabel_l1;
+  float2* sb = st + tile_base;
+#pragma unroll UNROLL
+  for (uint32_t o = 2u * tid; o < (1u << K); o += 2u * uint32_t(NT)) {
+    const uint2 e = *reinterpret_cast<const uint2*>(tab + 2u * o);  // (local index, offset in the state) of out-index o
+    const float2 v0 = tile[swz(e.x)], v1 = tile[swz(e.x | l1)];
+    *reinterpret_cast<float4*>(sb + e.y) = make_float4(v0.x, v0.y, v1.x, v1.y);
+  }
+}
+
 // Only the tiles that can hold a non-zero amplitude are launched (PassArgs::n_free): block b of the grid is
 // tile `b & (2^n_free - 1)` of the LIVE tiles of state `b >> n_free`; the tile-id bits that belong to index
 // bits of `zero_mask` are those of the input bitstring `idx` (given in the layout the pass loads).  Launching
@@ -1330,6 +1397,14 @@ __global__ __launch_bounds__(1 << (K - R), fwd_min_waves(K, R)) void pass_fwd_ke
       if (v) atomicAdd(&out64[size_t(out_row) * a.n_ops + i], v);
     }
   }
+  if ((a.flags & (PASS_STORE | PASS_RELABEL)) == (PASS_STORE | PASS_RELABEL)) {
+    // (PASS_RELABEL in a forward plan: the store moves four of the tile's bits onto the line positions -- a relabeling
+    // store with no finished bit, every amplitude of the tile, whole lines)
+    // (the barrier keeps the store's table loads and addresses out of the program loop, where a register more is a spill)
+    __builtin_amdgcn_sched_barrier(0);
+    store_tile_moved<K, NT, 2>(tile, st, a, tables, t.tile_base, uint32_t(tid));
+    return;
+  }
   if (a.flags & PASS_STORE) store_tile<K, NT>(tile, st, t, thread_offsets(t, tid), tid);
 }
 
@@ -1344,9 +1419,11 @@ __global__ __launch_bounds__(1 << (K - R), fwd_min_waves(K, R)) void pass_fwd_ke
 // Used when nothing distinguishes the two states' tiles: no tile pruned, nothing stale, no measurement
 // in the pass (or the values come from lambda = O psi), one program (engine.cpp run_forward_chunk).
 // ================================================================================
-template <int K>
-__global__ __launch_bounds__(1 << (K - 4), adjx_min_waves(K)) void pass_fwd2_kernel(
-    PassArgs a, float2* __restrict__ psi, const int8_t* __restrict__ bits, int n_user, uint32_t state0,
+// (MOVED: the instantiation for passes whose store moves the low bits -- an epilogue of its own in a kernel of its own,
+// so that the kernel of every other pass is the code it was: at K = 12 it sits at its register limit)
+template <int K, bool MOVED>
+__device__ __forceinline__ void pass_fwd2_body(
+    const PassArgs& a, float2* __restrict__ psi, const int8_t* __restrict__ bits, int n_user, uint32_t state0,
     const uint32_t* __restrict__ prog_base, const uint32_t* __restrict__ tables, const float* __restrict__ coef,
     uint32_t n_states) {
   constexpr int R = 4;
@@ -1429,6 +1506,23 @@ __global__ __launch_bounds__(1 << (K - 4), adjx_min_waves(K)) void pass_fwd2_ker
     TL = TLn;
     w0 = w1;
   }
+  if (MOVED) {
+    if (!(a.flags & PASS_STORE)) return;
+    // the store that moves four of the tile's bits onto the line positions (forward plans: no finished bit, every
+    // amplitude); each tile goes through the exchange buffer, and the scheduling barriers keep the second tile's LDS
+    // traffic from being hoisted over the first tile's stores, as in the adjoint kernel's epilogue
+    round_store0<R>(T, DB, p);
+    __syncthreads();
+    __builtin_amdgcn_sched_barrier(0);
+    store_tile_moved<K, NT, 2>(xt, st_a, a, tables, t.tile_base, uint32_t(tid));
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();
+    round_store0<R>(T, DB, q);
+    __syncthreads();
+    __builtin_amdgcn_sched_barrier(0);
+    if (s_b != s_a) store_tile_moved<K, NT, 2>(xt, st_b, a, tables, t.tile_base, uint32_t(tid));
+    return;
+  }
   if (a.flags & PASS_STORE) {
     round_store0<R>(T, DB, p);
     __syncthreads();
@@ -1439,6 +1533,21 @@ __global__ __launch_bounds__(1 << (K - 4), adjx_min_waves(K)) void pass_fwd2_ker
     __syncthreads();
     if (s_b != s_a) store_tile<K, NT>(xt, st_b, t, o, tid);
   }
+}
+
+template <int K>
+__global__ __launch_bounds__(1 << (K - 4), adjx_min_waves(K)) void pass_fwd2_kernel(
+    PassArgs a, float2* __restrict__ psi, const int8_t* __restrict__ bits, int n_user, uint32_t state0,
+    const uint32_t* __restrict__ prog_base, const uint32_t* __restrict__ tables, const float* __restrict__ coef,
+    uint32_t n_states) {
+  pass_fwd2_body<K, false>(a, psi, bits, n_user, state0, prog_base, tables, coef, n_states);
+}
+template <int K>
+__global__ __launch_bounds__(1 << (K - 4), adjx_min_waves(K)) void pass_fwd2_moved_kernel(
+    PassArgs a, float2* __restrict__ psi, const int8_t* __restrict__ bits, int n_user, uint32_t state0,
+    const uint32_t* __restrict__ prog_base, const uint32_t* __restrict__ tables, const float* __restrict__ coef,
+    uint32_t n_states) {
+  pass_fwd2_body<K, true>(a, psi, bits, n_user, state0, prog_base, tables, coef, n_states);
 }
 
 // ================================================================================
@@ -1588,56 +1697,6 @@ __device__ __forceinline__ void flush_cells(const float* cells, float* __restric
 #pragma unroll
     for (int w = 1; w < NW; ++w) v += cells[i * NW + w];
     grow[i] = v;
-  }
-}
-
-// The relabeling store: only the amplitudes whose newly finished bits equal the input bitstring, in
-// the order of their NEW addresses (finished bits moved to the highest positions the tile owns):
-// whole 128-byte lines of live data, nothing written for the dead half.
-// Live out-index o -> (local index with the finished bits clear, offset in the state) is a table
-// (tables[relabel_off + 2 o]) that is OR-decomposable in o: a thread looks up the entry of ITS low part of o once
-// for both tiles (relabel_lookup) and ORs the entry of the iteration's high part, which the host put into the pass
-// arguments -- as a loop over table entries, every iteration of both stores waited for its own table load.
-struct RelabelCtx {
-  uint32_t l_mine, off_mine;  // the thread's own entry
-  uint32_t fz_addr;           // where the finished bits go in the address, carrying the input bits
-  uint32_t fz_local;          // the finished bits of the live amplitudes, local index space
-  uint32_t count;             // out-indices (pairs of them when relabel_pairs) the store covers
-};
-template <int K>
-__device__ __forceinline__ RelabelCtx relabel_lookup(const PassArgs& a, const uint32_t* __restrict__ tables, uint32_t in_local,
-                                                     int tid, int lane) {
-  RelabelCtx r;
-  const uint32_t n_live = uint32_t(K) - a.n_fz;
-  r.count = a.relabel_pairs ? 1u << (n_live - 1u) : 1u << n_live;
-  const uint32_t mine = min(uint32_t(tid), r.count - 1u) << (a.relabel_pairs ? 1 : 0);
-  const uint2 e = *reinterpret_cast<const uint2*>(tables + a.relabel_off + 2u * mine);
-  const uint32_t src = a.fz_src[uint32_t(lane) & 31u];
-  r.fz_addr = ballot32((lane < 32) & (src != 0xffu) & (((in_local >> (src & 31u)) & 1u) != 0u));
-  r.fz_local = in_local & a.frozen_new_local;
-  r.l_mine = e.x;
-  r.off_mine = e.y;
-  return r;
-}
-template <int K, int NT>
-__device__ __forceinline__ void store_tile_relabeled(const float2* __restrict__ tile, float2* __restrict__ st,
-                                                     const PassArgs& a, const RelabelCtx& r, uint32_t tile_base, int tid) {
-  float2* sb = st + (tile_base | r.fz_addr);
-  if (a.relabel_pairs) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      if (uint32_t(i) < a.relabel_iters && uint32_t(tid) + uint32_t(i * NT) < r.count) {
-        const uint32_t l0 = r.l_mine | a.relabel_hi[i][0] | r.fz_local;
-        const float2 v0 = tile[swz(l0)], v1 = tile[swz(l0 | a.relabel_l1)];
-        *reinterpret_cast<float4*>(sb + (r.off_mine | a.relabel_hi[i][1])) = make_float4(v0.x, v0.y, v1.x, v1.y);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      if (uint32_t(i) < a.relabel_iters && uint32_t(tid) + uint32_t(i * NT) < r.count)
-        sb[r.off_mine | a.relabel_hi[i][1]] = tile[swz(r.l_mine | a.relabel_hi[i][0] | r.fz_local)];
-    }
   }
 }
 
@@ -2697,9 +2756,15 @@ static hipError_t launch_fwd2_t(const PassArgs& a, uint32_t n_states, float2* ps
                                 uint32_t state0, const uint32_t* prog, const uint32_t* tables, const float* coef,
                                 hipStream_t stream) {
   const size_t lds = size_t(8) << K;
-  static bool attr_done[kMaxDevices] = {};
-  if (hipError_t e = opt_in_lds(&pass_fwd2_kernel<K>, attr_done, lds); e != hipSuccess) return e;
+  static bool attr_done[kMaxDevices] = {}, attr_done_moved[kMaxDevices] = {};
   const uint32_t grid = ((n_states + 1u) / 2u) << a.n_nonlocal;
+  if (a.flags & PASS_RELABEL) {  // the store moves the low bits (forward plans)
+    if (hipError_t e = opt_in_lds(&pass_fwd2_moved_kernel<K>, attr_done_moved, lds); e != hipSuccess) return e;
+    hipLaunchKernelGGL((pass_fwd2_moved_kernel<K>), dim3(grid), dim3(1 << (K - 4)), lds, stream, a, psi, bits, n_user, state0,
+                       prog, tables, coef, n_states);
+    return hipGetLastError();
+  }
+  if (hipError_t e = opt_in_lds(&pass_fwd2_kernel<K>, attr_done, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL((pass_fwd2_kernel<K>), dim3(grid), dim3(1 << (K - 4)), lds, stream, a, psi, bits, n_user, state0, prog,
                      tables, coef, n_states);
   return hipGetLastError();

@@ -47,7 +47,8 @@ enum : uint32_t {
   PASS_ADJOINT = 1u << 2,     // tile pair (psi, lambda), program is a backward program
   PASS_GENERAL = 1u << 3,     // the program uses Y / dense 2x2 / dense two-qubit ops (rare-path kernel variant)
   PASS_SKIP_MEASURE = 1u << 4,  // forward: ignore the measurement groups (the values come from lambda = O psi)
-  PASS_RELABEL = 1u << 5,       // adjoint: the store moves the index bits this pass finished (PassArgs::relabel_*)
+  PASS_RELABEL = 1u << 5,       // adjoint: the store moves the index bits this pass finished (PassArgs::relabel_*);
+                                // forward: it moves four of the tile's bits onto positions 0..3 (no finished bit: n_fz = 0)
   PASS_NO_ZERO_FILL = 1u << 6,  // forward, with PASS_INIT_BASIS: tiles without the basis amplitude write nothing (later
                                 // passes clear what they load of them: PassArgs::frozen_old_local)
 };

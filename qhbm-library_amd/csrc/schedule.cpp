@@ -401,6 +401,12 @@ class Builder {
     for (size_t i = 0; i < p.local_pos.size(); ++i) if (gbits >> p.local_pos[i] & 1) l |= 1u << i;
     return l;
   }
+  // Logical index bits -> the positions they have when the pass loads its tiles (what a tile's base address spells).
+  static uint32_t to_phys(const Pass& p, uint32_t gbits) {
+    uint32_t ph = 0;
+    for (size_t b = 0; b < p.phys_of.size(); ++b) if (gbits >> b & 1) ph |= 1u << p.phys_of[b];
+    return ph | (gbits & ~((p.phys_of.size() < 32 ? 1u << p.phys_of.size() : 0u) - 1u));
+  }
   static uint32_t local_set_mask(const Pass& p) {
     uint32_t s = 0;
     for (int b : p.local_pos) s |= 1u << b;
@@ -799,7 +805,7 @@ class Builder {
         uint32_t cb;
         std::memcpy(&cb, &t.coeff, 4);
         p->prog.push_back(to_local(*p, t.z & S));
-        p->prog.push_back(t.z & ~S);
+        p->prog.push_back(to_phys(*p, t.z & ~S));  // (tested against the tile's base address)
         p->prog.push_back(cb);
         p->prog.push_back(uint32_t(t.op));
         ++p->n_meas_terms;
@@ -817,7 +823,7 @@ class Builder {
         uint32_t cb;
         std::memcpy(&cb, &t.coeff, 4);
         p->prog.push_back(to_local(*p, t.z & S));
-        p->prog.push_back(t.z & ~S);
+        p->prog.push_back(to_phys(*p, t.z & ~S));  // (tested against the tile's base address)
         p->prog.push_back(cb);
         p->prog.push_back(uint32_t(t.op) | (uint32_t(t.ny & 3) << 24));
         ++p->n_meas_terms;
@@ -833,11 +839,57 @@ class Builder {
   Plan* plan_;
 };
 
-}  // namespace
+// Forward plans that move the low index bits (schedule.h build_plan `move_low_bits`): one searched pass.
+struct FwdStep {
+  uint32_t S = 0;    // local set, logical bits
+  int K = 0;         // tile size of the pass (the last pass may be one bit wider)
+  uint32_t low = 0;  // the four logical bits of S on physical positions 0..3 after the pass's store
+};
+constexpr double kFwdFixed = 1.3, kFwdPerX = 0.093;  // ms per 1024 states at 20 qubits (forward_plan_cost)
 
-bool build_plan(const Model& m, int tile_bits, int round_bits, bool adjoint, Plan* plan, std::string* err,
-                int full_threshold, int meas_tile_bits, bool cph_wave_bits, bool relabel, int wide_last_pass,
-                const std::vector<uint32_t>* forced_order) {
+// (never less than the time of the pass's tile traffic: 1024 states of 2^20 amplitudes read and written are 17.2 GB, 3.1 ms
+// at the 5.5 TB/s of a pass with nothing to compute -- engine.cpp adjoint_plan_seconds; the fit saw passes of 33 X ops and more)
+// ... and a part per pass that pruning does not shrink (the grid's ramp and drain, the launch): measured on the headline
+// circuit, forward kernel time per 4096-state step with 0 / 0.5 / 1.0 here = plans of 6 / 5 / 4 gate passes: 76.7 / 78.0 /
+// 79.8 ms against 92.4 ms without moving -- alike within 4 %; 0.5 keeps the plan with fewer passes and 0.56 of the bytes
+constexpr double kFwdMemory = 3.1, kFwdPerPass = 0.5;
+// All of these are in units of the headline shape (1024 states of 2^20 amplitudes); every term of a pass scales with the
+// state alike, and plans are compared by ratios only, so the choice does not depend on the register width or the batch.
+double fwd_per_pass() {  // a cost per pass that pruning does not shrink (QHBM_FWD_PLAN_KPASS: developer knob, read once)
+  static const double per_pass = [] {
+    const char* e = std::getenv("QHBM_FWD_PLAN_KPASS");
+    return e ? std::atof(e) : kFwdPerPass;
+  }();
+  return per_pass;
+}
+double fwd_pass_cost(double share, int n_mat) {
+  return fwd_per_pass() + std::max(share, 1.0 / 256.0) * std::max(kFwdMemory, kFwdFixed + kFwdPerX * double(n_mat));
+}
+
+// The layout after a pass with local set S whose store puts the bits `low` (four bits of S, ascending) on positions
+// 0..3: every other bit of S goes home (position = logical bit) if the tile owns that position, the rest fill the
+// positions left over in ascending order.  In place: the bits of S keep the positions of S.
+void move_low_after(uint32_t S, uint32_t low, int n_eff, std::vector<int>* ph) {
+  uint32_t owned = 0;
+  for (int b = 0; b < n_eff; ++b) if (S >> b & 1u) owned |= 1u << (*ph)[size_t(b)];
+  int next_low = 0;
+  uint32_t homeless = 0;
+  for (int b = 0; b < n_eff; ++b) {
+    if (!(S >> b & 1u)) continue;
+    if (low >> b & 1u) { (*ph)[size_t(b)] = next_low; owned &= ~(1u << next_low); ++next_low; }
+  }
+  for (int b = 0; b < n_eff; ++b) {
+    if (!(S >> b & 1u) || (low >> b & 1u)) continue;
+    if (owned >> b & 1u) { (*ph)[size_t(b)] = b; owned &= ~(1u << b); }
+    else homeless |= 1u << b;
+  }
+  for (int b = 0; b < n_eff; ++b)
+    if (homeless >> b & 1u) { const int pos = __builtin_ctz(owned); (*ph)[size_t(b)] = pos; owned &= owned - 1u; }
+}
+
+bool build_plan_impl(const Model& m, int tile_bits, int round_bits, bool adjoint, Plan* plan, std::string* err,
+                     int full_threshold, int meas_tile_bits, bool cph_wave_bits, bool relabel, int wide_last_pass,
+                     const std::vector<uint32_t>* forced_order, int moving) {
   *plan = Plan();
   plan->full_threshold = full_threshold;
   plan->cph_wave_bits = cph_wave_bits;
@@ -1204,6 +1256,193 @@ bool build_plan(const Model& m, int tile_bits, int round_bits, bool adjoint, Pla
     if (left == 0) plan->candidate_orders.push_back(greedy_sets);
     if (left == 0 && planned.size() > greedy_passes + (plan->relabel ? 4 : 1)) planned.clear();
   }
+  // Forward plans that move the low index bits.  With logical = physical, every tile is the four low bits plus an
+  // eight-bit window: two light cones of width 4 and 8.  Letting a pass leave any four of its bits on positions 0..3
+  // makes tiles of twelve contiguous logical bits possible -- one light cone of width 12 -- at the same whole-line
+  // accesses.  The first pass loads nothing, so the layout it starts from is free; the last one restores the identity.
+  // Beam search over (local set, next low bits) on fwd_pass_cost.
+  std::vector<FwdStep> steps;
+  if (moving) {
+    // (the wide last pass under the conditions of the plain plans; 13: the paired forward kernel's largest tile)
+    const bool widen_ok = (wide_last_pass > 0 || (wide_last_pass < 0 && tile_bits == 0)) && !std::getenv("QHBM_NO_WIDE_LAST_PASS");
+    const int K_wide = widen_ok && K + 1 <= std::min(n_eff, 13) ? K + 1 : K;
+    struct Node { std::vector<char> dn; size_t n_done; double cost; std::vector<FwdStep> steps; std::vector<int> phys; std::vector<int> phys0; uint32_t touched; };
+    auto low_of = [&](const std::vector<int>& ph) {
+      uint32_t L = 0;
+      for (int bb = 0; bb < n_eff; ++bb) if (ph[size_t(bb)] < c_min) L |= 1u << bb;
+      return L;
+    };
+    auto is_identity = [&](const std::vector<int>& ph) {
+      for (int bb = 0; bb < n_eff; ++bb) if (ph[size_t(bb)] != bb) return false;
+      return true;
+    };
+    auto mats_left = [&](const std::vector<char>& dn) {
+      size_t left = 0;
+      for (size_t oi = 0; oi < ops.size(); ++oi) left += !dn[oi] && ops[oi].type != LOW_DIAG;
+      return left;
+    };
+    size_t kBeam = ops.size() <= 4000 ? 96 : (ops.size() <= 12000 ? 24 : 8);
+    if (const char* e = std::getenv("QHBM_PLAN_BEAM")) kBeam = size_t(std::max(1, std::atoi(e)));
+    const uint32_t home_low = (1u << c_min) - 1u;
+    std::vector<Node> beam(1);
+    beam[0].dn = done;
+    beam[0].n_done = 0;
+    beam[0].cost = 0.0;
+    beam[0].phys = phys;
+    beam[0].touched = 0;
+    double best_cost = -1.0;
+    size_t most_in_a_pass = 1;
+    for (int depth = 0; depth < 64 && !beam.empty(); ++depth) {
+      std::vector<Node> next;
+      for (const Node& nd : beam) {
+        // ---- candidate (local set, tile size, layout at load) ----
+        struct Cand { uint32_t S; int K; std::vector<int> ph; };
+        std::vector<Cand> cs;
+        auto add = [&](uint32_t S, int Kp, const std::vector<int>& ph) {
+          if (popc(S) != Kp) return;
+          for (const Cand& c : cs) if (c.S == S && c.ph == ph) return;
+          cs.push_back(Cand{S, Kp, ph});
+        };
+        if (depth == 0) {
+          // the start layout is free: any four consecutive bits of a contiguous window on positions 0..3
+          for (int p0 = 0; p0 + K <= n_eff; ++p0)
+            for (int l0 = p0; l0 + c_min <= p0 + K; ++l0) {
+              const uint32_t S = ((1u << K) - 1u) << p0, L0 = home_low << l0;
+              std::vector<int> ph = nd.phys;
+              move_low_after(L0 | home_low, L0, n_eff, &ph);
+              add(S, K, ph);
+            }
+          for (uint32_t S : gen_cands(nd.dn, nd.phys)) add(S, K, nd.phys);
+        } else {
+          const uint32_t Lc = low_of(nd.phys);
+          std::vector<int> others;
+          for (int bb = 0; bb < n_eff; ++bb) if (!(Lc >> bb & 1u)) others.push_back(bb);
+          const size_t hh = size_t(K - c_min);
+          for (size_t p0 = 0; p0 + hh <= others.size(); ++p0) {
+            uint32_t S = Lc;
+            for (size_t k = 0; k < hh; ++k) S |= 1u << others[p0 + k];
+            add(S, K, nd.phys);
+          }
+          for (int with_diag = 0; with_diag < 2; ++with_diag) {  // demand-driven, as gen_cands
+            uint32_t S = Lc, blocked = 0;
+            for (int oi : order) {
+              if (nd.dn[size_t(oi)]) continue;
+              const LoweredOp& op = ops[size_t(oi)];
+              if (op.bits & blocked) { blocked |= op.bits; continue; }
+              if (op.type == LOW_DIAG && !with_diag) continue;
+              if (popc(S | op.bits) <= K) S |= op.bits; else blocked |= op.bits;
+            }
+            for (int bit = n_eff - 1; bit >= 0 && popc(S) < K; --bit) if (!(S >> bit & 1u)) S |= 1u << bit;
+            add(S, K, nd.phys);
+          }
+          // the pass that takes all that is left and restores the layout: the low bits, every bit that is not at
+          // home, the home bits 0..3 and the bits of the ops left
+          uint32_t S = Lc | home_low;
+          for (int bb = 0; bb < n_eff; ++bb) if (nd.phys[size_t(bb)] != bb) S |= 1u << bb;
+          for (int oi : order) {
+            if (nd.dn[size_t(oi)]) continue;
+            const LoweredOp& op = ops[size_t(oi)];
+            S |= op.type == LOW_DIAG ? (op.bits & S ? 0u : (op.bits & (0u - op.bits))) : op.bits;
+          }
+          if (popc(S) <= K_wide) {
+            const int Kp = popc(S) <= K ? K : K_wide;
+            for (int bit = n_eff - 1; bit >= 0 && popc(S) < Kp; --bit) if (!(S >> bit & 1u)) S |= 1u << bit;
+            add(S, Kp, nd.phys);
+          }
+        }
+        for (const Cand& cd : cs) {
+          int n_mat = 0;
+          std::vector<int> lst = absorb(ops, order, nd.dn, cd.S, all_bits, &n_mat);
+          if (lst.empty()) continue;
+          Node c;
+          c.dn = nd.dn;
+          for (int oi : lst) c.dn[size_t(oi)] = 1;
+          c.n_done = nd.n_done + lst.size();
+          const double share = depth == 0 ? 1.0 / double(1u << (n_eff - cd.K))
+                                          : 1.0 / double(1u << popc(all_bits & ~cd.S & ~nd.touched));
+          c.cost = nd.cost + fwd_pass_cost(share, n_mat);
+          most_in_a_pass = std::max(most_in_a_pass, size_t(n_mat));
+          if (best_cost >= 0.0 && c.cost >= best_cost) continue;
+          c.touched = nd.touched;
+          for (int oi : lst) if (ops[size_t(oi)].type != LOW_DIAG) c.touched |= ops[size_t(oi)].bits;
+          c.phys0 = depth == 0 ? cd.ph : nd.phys0;
+          c.steps = nd.steps;
+          if (c.n_done == ops.size()) {  // complete: only if this pass can restore logical = physical
+            if ((home_low & ~cd.S) != 0) continue;
+            if (moving == 2 && is_identity(cd.ph)) continue;  // (asked for a plan that permutes: the last store must)
+            std::vector<int> ph = cd.ph;
+            move_low_after(cd.S, home_low, n_eff, &ph);
+            if (!is_identity(ph)) continue;
+            c.steps.push_back(FwdStep{cd.S, cd.K, home_low});
+            best_cost = c.cost;
+            steps = c.steps;
+            phys = c.phys0;
+            continue;
+          }
+          if (cd.K != K) continue;  // (the wide tile is for the last pass only)
+          // ---- the low bits after this pass: as they are, home, or four consecutive bits of the set ----
+          std::vector<uint32_t> lows;
+          lows.push_back(low_of(cd.ph));
+          if ((home_low & ~cd.S) == 0) lows.push_back(home_low);
+          {
+            std::vector<int> sb;
+            for (int bb = 0; bb < n_eff; ++bb) if (cd.S >> bb & 1u) sb.push_back(bb);
+            for (size_t p0 = 0; p0 + size_t(c_min) <= sb.size(); ++p0) {
+              uint32_t L = 0;
+              for (int k = 0; k < c_min; ++k) L |= 1u << sb[p0 + size_t(k)];
+              lows.push_back(L);
+            }
+          }
+          std::sort(lows.begin() + 1, lows.end());
+          lows.erase(std::unique(lows.begin() + 1, lows.end()), lows.end());
+          for (size_t li = 0; li < lows.size(); ++li) {
+            if (li > 0 && lows[li] == lows[0]) continue;
+            Node c2 = c;
+            c2.phys = cd.ph;
+            if (li > 0) move_low_after(cd.S, lows[li], n_eff, &c2.phys);  // (li == 0: the pass stores in place)
+            c2.steps.push_back(FwdStep{cd.S, cd.K, lows[li]});
+            bool dup = false;
+            for (Node& o : next)
+              if (o.n_done == c2.n_done && o.phys == c2.phys && o.dn == c2.dn) { dup = true; if (c2.cost < o.cost) o = c2; break; }
+            if (!dup) next.push_back(std::move(c2));
+          }
+        }
+      }
+      // (what is left costs at least its X ops and the fixed part of the passes that must hold them: no pass has absorbed
+      // more non-diagonal ops than `most_in_a_pass` so far)
+      auto rank = [&](const Node& nd) {
+        const size_t left = mats_left(nd.dn);
+        return nd.cost + kFwdPerX * double(left) + (kFwdFixed + fwd_per_pass()) * double((left + most_in_a_pass - 1) / most_in_a_pass);
+      };
+      std::vector<std::pair<double, size_t>> keyed;
+      for (size_t i = 0; i < next.size(); ++i) keyed.push_back({rank(next[i]), i});
+      std::stable_sort(keyed.begin(), keyed.end());
+      // (at most nine layouts per set of done ops: the beam must not fill up with one prefix under many layouts)
+      std::vector<Node> kept;
+      for (const auto& kv : keyed) {
+        if (kept.size() >= kBeam) break;
+        const Node& nd = next[kv.second];
+        if (best_cost >= 0.0 && nd.cost >= best_cost) continue;
+        size_t same = 0;
+        for (const Node& o : kept) same += o.n_done == nd.n_done && o.dn == nd.dn;
+        if (same >= 9) continue;
+        kept.push_back(nd);
+      }
+      if (std::getenv("QHBM_PLAN_DEBUG"))
+        for (size_t i = 0; i < kept.size() && i < 8; ++i) {
+          std::fprintf(stderr, "[fwd plan] depth %d #%zu cost %.3f done %zu:", depth, i, kept[i].cost, kept[i].n_done);
+          for (const FwdStep& st : kept[i].steps) std::fprintf(stderr, " %x/%x", st.S, st.low);
+          std::fprintf(stderr, "\n");
+        }
+      beam.swap(kept);
+    }
+    if (steps.empty()) { *err = "no forward plan that moves the low bits"; return false; }
+    if (std::getenv("QHBM_PLAN_DEBUG")) {
+      std::fprintf(stderr, "[fwd plan] chosen, cost %.3f:", best_cost);
+      for (const FwdStep& st : steps) std::fprintf(stderr, " %x/%x(K=%d)", st.S, st.low, st.K);
+      std::fprintf(stderr, "\n");
+    }
+  }
   size_t planned_i = 0;
   {  // developer knobs: QHBM_ADJ_SETS / QHBM_FWD_SETS=hex,hex,... force the local sets of the first passes
     if (const char* env = std::getenv(adjoint ? "QHBM_ADJ_SETS" : "QHBM_FWD_SETS")) {
@@ -1219,7 +1458,13 @@ bool build_plan(const Model& m, int tile_bits, int round_bits, bool adjoint, Pla
   }
 
   while (n_done < ops.size()) {
-    std::vector<uint32_t> cands = planned_i < planned.size() ? std::vector<uint32_t>{planned[planned_i++]} : gen_cands(done, phys);
+    const FwdStep* step = nullptr;  // the searched pass of a plan that moves the low bits
+    if (moving) {
+      if (plan->passes.size() >= steps.size()) { *err = "internal: the searched forward plan leaves ops undone"; return false; }
+      step = &steps[plan->passes.size()];
+    }
+    std::vector<uint32_t> cands = step ? std::vector<uint32_t>{step->S}
+                                       : (planned_i < planned.size() ? std::vector<uint32_t>{planned[planned_i++]} : gen_cands(done, phys));
     // A WIDER last pass: when everything that is left needs one or two index bits more than a tile has, the
     // last gate pass takes a tile of 2^(K+1) or 2^(K+2) amplitudes instead of leaving a pass of its own to a
     // handful of gates (config 3: 33 gates on 13 bits were 32 + 1 in two passes, the second a full read and
@@ -1228,7 +1473,7 @@ bool build_plan(const Model& m, int tile_bits, int round_bits, bool adjoint, Pla
     uint32_t wide_S = 0;
     // (not for the first pass, and not against an explicit tile size unless asked for: wide_last_pass = 1)
     const bool widen = wide_last_pass > 0 || (wide_last_pass < 0 && tile_bits == 0);
-    if (!adjoint && K < n_eff && plan->tail_tiles && widen && !plan->passes.empty() && !std::getenv("QHBM_NO_WIDE_LAST_PASS")) {
+    if (!step && !adjoint && K < n_eff && plan->tail_tiles && widen && !plan->passes.empty() && !std::getenv("QHBM_NO_WIDE_LAST_PASS")) {
       uint32_t S = (1u << c_min) - 1;
       for (int oi : order) {
         if (done[oi]) continue;
@@ -1241,7 +1486,7 @@ bool build_plan(const Model& m, int tile_bits, int round_bits, bool adjoint, Pla
         wide_S = S;
       }
     }
-    if (!adjoint && K < n_eff && !groups.empty()) {
+    if (!step && !adjoint && K < n_eff && !groups.empty()) {
       // If one tile can hold every remaining op, this is the last gate pass: spend its spare local
       // bits on the X-masks of the groups no earlier pass can measure, so that the measurement
       // needs no pass (a full read of the state) of its own -- only if ALL of them fit (a
@@ -1303,8 +1548,8 @@ bool build_plan(const Model& m, int tile_bits, int round_bits, bool adjoint, Pla
       }
     }
     if (best_list.empty()) { *err = "scheduler made no progress"; return false; }
-    Builder wide(m, wide_K ? wide_K : K, R, n_eff, adjoint, plan);
-    Builder* bp = &b;
+    Builder wide(m, step ? step->K : (wide_K ? wide_K : K), R, n_eff, adjoint, plan);
+    Builder* bp = step && step->K != K ? &wide : &b;
     if (wide_K) {  // does the wider tile really take everything that is left?
       int n_mat = 0;
       std::vector<int> all_left = absorb(ops, order, done, wide_S, all_bits, &n_mat);
@@ -1357,6 +1602,39 @@ bool build_plan(const Model& m, int tile_bits, int round_bits, bool adjoint, Pla
           p.relabel_tab[2 * size_t(o) + 1] = off;
         }
       }
+    }
+    if (step) {
+      // The store that moves the low bits: a relabeling store with no finished bit.  Out-index o counts the positions
+      // the tile owns in ascending order (o bit 0 = address bit 0: consecutive o are adjacent amplitudes, 16-byte stores
+      // of whole lines); the table is OR-decomposable in o as the adjoint's is.
+      if (n_done == ops.size() && plan->passes.size() + 1 != steps.size()) { *err = "internal: the searched forward plan has passes left over"; return false; }
+      uint32_t low_now = 0;
+      for (int bb = 0; bb < n_eff; ++bb) if (phys[size_t(bb)] < c_min) low_now |= 1u << bb;
+      const std::vector<int> before(phys);
+      if (step->low != low_now || n_done == ops.size()) move_low_after(best_S, step->low, n_eff, &phys);
+      if (phys != before) {
+        const int Kp = p.K;
+        p.flags |= PASS_RELABEL;
+        std::vector<int> by_pos(size_t(n_eff), -1);  // position at the store -> local index bit
+        for (int i = 0; i < Kp; ++i) {
+          p.store_local_phys.push_back(phys[size_t(p.local_pos[size_t(i)])]);
+          by_pos[size_t(p.store_local_phys.back())] = i;
+        }
+        std::vector<int> src, pos;  // per bit of o
+        for (int q = 0; q < n_eff; ++q) if (by_pos[size_t(q)] >= 0) { src.push_back(by_pos[size_t(q)]); pos.push_back(q); }
+        if (int(src.size()) != Kp || pos[0] != 0) { *err = "internal: the moving store is not a permutation of the tile"; return false; }
+        p.relabel_tab.resize(size_t(2) << Kp);
+        for (uint32_t o = 0; o < (1u << Kp); ++o) {
+          uint32_t l = 0, off = 0;
+          for (int j = 0; j < Kp; ++j)
+            if (o >> j & 1u) { l |= 1u << src[size_t(j)]; off |= 1u << pos[size_t(j)]; }
+          p.relabel_tab[2 * size_t(o)] = l;
+          p.relabel_tab[2 * size_t(o) + 1] = off;
+        }
+      }
+      if (n_done == ops.size())
+        for (int bb = 0; bb < n_eff; ++bb)
+          if (phys[size_t(bb)] != bb) { *err = "internal: the last forward pass does not restore the layout"; return false; }
     }
     plan->passes.push_back(std::move(p));
   }
@@ -1487,6 +1765,65 @@ bool build_plan(const Model& m, int tile_bits, int round_bits, bool adjoint, Pla
   return true;
 }
 
+}  // namespace
+
+double forward_plan_cost(const Plan& p) {
+  double cost = 0.0;
+  uint32_t touched = 0;
+  const uint32_t all_bits = p.n_eff >= 32 ? ~0u : (1u << p.n_eff) - 1u;
+  for (size_t i = 0; i < p.passes.size(); ++i) {
+    const Pass& q = p.passes[i];
+    uint32_t S = 0;
+    for (int b : q.local_pos) S |= 1u << b;
+    double share = 1.0;  // (a measurement-only pass reads every tile)
+    if (!q.is_measure_only && !p.dense_input)
+      share = i == 0 ? 1.0 / double(1u << std::min(20, p.n_eff - q.K)) : 1.0 / double(1u << popc(all_bits & ~S & ~touched));
+    cost += fwd_pass_cost(share, q.n_mat_ops);
+    touched |= q.mat_bits;
+  }
+  return cost;
+}
+
+bool build_plan(const Model& m, int tile_bits, int round_bits, bool adjoint, Plan* plan, std::string* err,
+                int full_threshold, int meas_tile_bits, bool cph_wave_bits, bool relabel, int wide_last_pass,
+                const std::vector<uint32_t>* forced_order, int move_low_bits) {
+  if (!build_plan_impl(m, tile_bits, round_bits, adjoint, plan, err, full_threshold, meas_tile_bits, cph_wave_bits, relabel,
+                       wide_last_pass, forced_order, 0))
+    return false;
+  // Forward plans that move the low bits: only where the plan is the scheduler's own choice throughout (no start state
+  // of the caller's, no explicit tile size, no forced order), lean (the moving store exists in the lean kernels' epilogue
+  // only), tiled, and complete without zero-filling (pruning is what the early, small passes are cheap by).
+  // (`move_low_bits` 2, for tests: with an explicit tile size too, and whenever a plan that permutes exists)
+  const bool forced = move_low_bits == 2;
+  if (!move_low_bits || adjoint || m.dense_input || (tile_bits != 0 && !forced) || forced_order || std::getenv("QHBM_FWD_SETS") ||
+      plan->K >= plan->n_eff || !plan->tail_tiles || plan->passes.size() < 2 || !(plan->passes[0].flags & PASS_NO_ZERO_FILL))
+    return true;
+  for (const Pass& p : plan->passes) if (p.flags & PASS_GENERAL) return true;
+  Plan moved;
+  std::string e2;
+  if (!build_plan_impl(m, tile_bits, round_bits, adjoint, &moved, &e2, full_threshold, meas_tile_bits, cph_wave_bits, relabel,
+                       wide_last_pass, nullptr, forced ? 2 : 1))
+    return true;
+  bool permutes = false;
+  size_t meas_only = 0, meas_only_moved = 0;
+  for (const Pass& p : plan->passes) meas_only += p.is_measure_only;
+  for (const Pass& p : moved.passes) {
+    if (p.flags & PASS_GENERAL) return true;
+    permutes |= (p.flags & PASS_RELABEL) != 0;
+    meas_only_moved += p.is_measure_only;
+  }
+  // (the model knows the gate passes; a plan that needs more measurement passes or global terms loses on what it leaves out)
+  if (!permutes) return true;
+  if (!forced && (meas_only_moved > meas_only || moved.global_terms.size() > plan->global_terms.size())) return true;
+  if (std::getenv("QHBM_PLAN_DEBUG"))
+    std::fprintf(stderr, "[fwd plan] modelled cost %.3f moving, %.3f without\n", forward_plan_cost(moved), forward_plan_cost(*plan));
+  // (by a tenth at least: the model does not resolve less -- three plans of the headline circuit that it priced within 2 %
+  // of each other measured 4 % apart, in another order -- and a plan that gains nothing must be the plan of before, bit
+  // for bit in its results)
+  if (forced || forward_plan_cost(moved) < 0.90 * forward_plan_cost(*plan)) *plan = std::move(moved);
+  return true;
+}
+
 std::string describe_plan(const Plan& p) {
   std::ostringstream os;
   os << (p.adjoint ? (p.relabel ? "adjoint (relabeling)" : "adjoint") : "forward") << " plan: n=" << p.n << " n_eff=" << p.n_eff
@@ -1580,6 +1917,17 @@ std::string describe_plan(const Plan& p) {
       for (size_t k = 0; k < q.local_phys.size(); ++k) os << (k ? "," : "") << q.local_phys[k];
       if (q.flags & PASS_RELABEL) os << " moves-local-bits=" << std::hex << q.frozen_new_local << std::dec;
       if (q.frozen_old_local) os << " stale-local-bits=" << std::hex << q.frozen_old_local << std::dec;
+    } else if (!p.adjoint && ((q.flags & PASS_RELABEL) || q.local_phys != q.local_pos)) {
+      // a forward plan that moves the low bits: where the tile sits, and the logical bits its store puts on positions 0..3
+      os << " at=";
+      for (size_t k = 0; k < q.local_phys.size(); ++k) os << (k ? "," : "") << q.local_phys[k];
+      if (q.flags & PASS_RELABEL) {
+        os << " moves-to-low=[";
+        bool first = true;
+        for (size_t k = 0; k < q.store_local_phys.size(); ++k)
+          if (q.store_local_phys[k] < 4) { os << (first ? "" : ",") << q.local_pos[k]; first = false; }
+        os << "]";
+      }
     }
     {  // per round: X micro-ops next to a FULL table / all X micro-ops (which may run as two shears: x_shear.h)
       const RecordLayout L(p.R, p.adjoint);

@@ -70,6 +70,8 @@ struct Pass {
   // finishes an index bit stores its tiles with that bit moved to the highest position the tile owns, so
   // that in every later pass the live half of the state (finished bit == input bit) is made of WHOLE
   // 128-byte lines instead of every other amplitude of every line.
+  // Forward plans that move the low bits (build_plan `move_low_bits`) use the same fields with no finished bit: a pass
+  // stores its tile with four bits of its choice on positions 0..3, and the last gate pass restores the identity.
   std::vector<int> local_pos;
   std::vector<int> nonlocal_pos;
   std::vector<int> local_phys, nonlocal_phys;  // their physical positions when the pass LOADS its tiles (ascending)
@@ -150,11 +152,21 @@ struct Model {
 // true, the backward plan over (psi, lambda) tile pairs.  `tile_bits` = 0
 // selects automatically.  Returns false and fills `err` on failure.
 // `meas_tile_bits`: tile size of measurement-only passes (0 = the largest the forward kernel has).
+// `move_low_bits` (forward plans): a pass may choose which four of its local logical bits sit on physical positions
+// 0..3 after its store (Pass::store_local_phys with no finished bit), so that a tile can be twelve CONTIGUOUS logical
+// bits; the plan is searched on the per-pass cost model of forward_plan_cost and kept only if that model prices it a
+// tenth below the plan built without the freedom and it needs no further measurement pass or global term (1), or
+// whenever such a plan exists, an explicit tile size included (2: for tests of the moving store at small sizes).  The pass that completes the circuit restores logical = physical.
 bool build_plan(const Model& m, int tile_bits, int round_bits, bool adjoint, Plan* out,
                 std::string* err, int full_threshold = 60, int meas_tile_bits = 0, bool cph_wave_bits = true,
-                bool relabel = false, int wide_last_pass = -1, const std::vector<uint32_t>* forced_order = nullptr);
+                bool relabel = false, int wide_last_pass = -1, const std::vector<uint32_t>* forced_order = nullptr,
+                int move_low_bits = 0);
 
 std::string describe_plan(const Plan& p);
+
+// Modelled time of a forward plan's passes, ms per 1024 states at 20 qubits: per pass (share of the tiles that are
+// launched, at least 1/256) x (fixed + per X op), the fit of the four full passes of the headline circuit.
+double forward_plan_cost(const Plan& p);
 
 // For every gate of a forward plan: the first pass that reads its coefficients (the pass count for a gate no record
 // depends on; 0 for every gate if the walk meets a program it does not know).  `first_measuring`: the first pass with a

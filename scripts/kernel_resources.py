@@ -142,7 +142,7 @@ def default_selectable(name):
     return True
   if name.startswith("shot_parity_"):   # (sample_parity.hip: the masks, table and draw kernels of qhbm_sample_parities)
     return True
-  return name.startswith(("pass_fwd2_kernel", "pass_adjx_kernel"))
+  return name.startswith(("pass_fwd2_kernel", "pass_fwd2_moved_kernel", "pass_adjx_kernel"))
 
 
 def report():
