@@ -401,6 +401,38 @@ int qhbm_krylov_combine(const void* d_basis, int m, int U, int n_qubits, const v
                         void* stream);
 int qhbm_describe_krylov(qhbm_engine* h, int U, int m, int reorth, char* buf, size_t len);
 
+/* ---- Streamed Lanczos: the same results without a stored basis, in two passes ----
+ * Added WITHIN ABI version 5: purely additive, QHBM_ABI_VERSION stays 5.
+ *
+ * H, `weights`, R, the breakdown threshold 2^-16 R and the conventions of qhbm_krylov_basis.  The basis of m rows is
+ * replaced by a ring of three state buffers per chunk element in engine-owned memory (at the workspace's pitch), so the
+ * memory of a call does not grow with m.  Full reorthogonalisation needs the stored basis and is not offered here.
+ *
+ *   qhbm_krylov_tridiagonal  pass one: the recurrence of qhbm_krylov_basis(reorth = 0).  d_alpha, d_beta [U, m] float64 and
+ *                            d_lengths [U] int32 are, bit for bit, what that call writes.  d_recurrence [U, m, 2] complex64:
+ *                            the complex64-rounded coefficients (c_{j-1}, c_j) step j subtracted, (0, c_0) for j = 0 -- with
+ *                            beta all a replay needs: v_{j+1} = (H v_j - c_{j-1} v_{j-1} - c_j v_j) / beta_j.
+ *   qhbm_krylov_replay       pass two: d_out_states[u, s] = sum_j d_coef[u, s, j] v_j(u), j ascending in fp32; d_coef
+ *                            [U, S, m] complex64, d_out_states [U, S, 2^n] (the layout of qhbm_krylov_combine).  v_0 is
+ *                            imported again from d_start_states, which the caller has left unchanged, and every later v_j is
+ *                            regenerated from d_beta and d_recurrence with NO inner products: bit for bit the row the stored
+ *                            route would hold.  The scale of step j is 1 / beta_j, 0 where beta_j = 0 (an exhausted space, a
+ *                            start state of norm 0): exact zeros from there on.  S > 8 runs the recurrence once per group of
+ *                            eight outputs.  d_lengths is checked like the other pointers; the kernels do not read it.
+ *   qhbm_describe_krylov_stream  "workspace_bytes=... chunk_states=... tridiagonal_applications=... replay_applications=...
+ *                            tridiagonal_bytes_per_state=... replay_bytes_per_state=..." of such a pair of calls by the byte
+ *                            model of DESIGN.md 6o; workspace_bytes does not depend on m; needs no device.
+ * Both passes are asynchronous on `stream` and read nothing back; results do not depend on the chunking nor on which other
+ * states share the call.  Refused, each with a message and every buffer untouched: m outside [1, 1024]; U <= 0; S < 1; no
+ * observables installed; a NULL or misaligned pointer (states 16 bytes, the rest their element size); start states or
+ * outputs inside the engine's workspace; outputs overlapping the start states. */
+int qhbm_krylov_tridiagonal(qhbm_engine* h, const void* d_start_states, int U, const double* weights, int m, double* d_alpha,
+                            double* d_beta, int32_t* d_lengths, void* d_recurrence, void* stream);
+int qhbm_krylov_replay(qhbm_engine* h, const void* d_start_states, int U, const double* weights, int m, const double* d_beta,
+                       const int32_t* d_lengths, const void* d_recurrence, const void* d_coef, int S, void* d_out_states,
+                       void* stream);
+int qhbm_describe_krylov_stream(qhbm_engine* h, int U, int m, int S, char* buf, size_t len);
+
 /* ---- The weighted Gram matrix of M states: fidelity, entropy and relative entropy of state-vector data ----
  * Added WITHIN ABI version 5: purely additive, QHBM_ABI_VERSION stays 5.
  *

@@ -244,6 +244,8 @@ struct qhbm_engine {
   // of ||w||^2, the round's coefficients [chunk, m] complex64
   DevBuf<double> kry_parts, kry_norm_parts;
   DevBuf<float2> kry_coef;
+  // streamed Lanczos (qhbm_krylov_tridiagonal, qhbm_krylov_replay): three state buffers per chunk element at the workspace's pitch
+  DevBuf<float2> kry_ring;
 };
 
 namespace {
@@ -286,7 +288,7 @@ size_t own_bytes(const qhbm_engine* h) {
                       buf_bytes(o.param_slots) + buf_bytes(o.slot_factor) + buf_bytes(o.shift_phases) + buf_bytes(o.phase_slope) + buf_bytes(h->cot_parts) + buf_bytes(h->cot_dot) + buf_bytes(h->import_parts) +
                       buf_bytes(h->import_norm2) + buf_bytes(h->import_up) + buf_bytes(h->import_bits) + buf_bytes(h->evo_wr) +
                       buf_bytes(h->evo_scale) + buf_bytes(h->evo_parts) + buf_bytes(h->evo_log_norm) + buf_bytes(h->evo_up1) +
-                      buf_bytes(h->evo_up2) + buf_bytes(h->kry_parts) + buf_bytes(h->kry_norm_parts) + buf_bytes(h->kry_coef);
+                      buf_bytes(h->evo_up2) + buf_bytes(h->kry_parts) + buf_bytes(h->kry_norm_parts) + buf_bytes(h->kry_coef) + buf_bytes(h->kry_ring);
            for (const auto& kv : o.adj_cache) b += plan_bytes(*kv.second);
            return b;
          }();
@@ -1086,7 +1088,7 @@ bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes
 // Does [p, p + bytes) meet the statevector workspace?
 bool aliases_workspace(const qhbm_engine* h, const void* p, size_t bytes) {
   auto meets = [&](const DevBuf<float2>& b) { return b.p && ranges_overlap(p, bytes, b.p, b.n * sizeof(float2)); };
-  return meets(h->psi) || meets(h->lam);
+  return meets(h->psi) || meets(h->lam) || meets(h->kry_ring);
 }
 
 // A pointer argument that must be there and a multiple of `align` bytes (h NULL: an entry point without an engine).
@@ -2527,6 +2529,225 @@ int qhbm_krylov_combine(const void* d_basis, int m, int U, int n_qubits, const v
                                        static_cast<const float2*>(d_coef), uint32_t(S), static_cast<float2*>(d_out_states),
                                        static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return fail(nullptr, std::string("qhbm_krylov_combine: ") + hipGetErrorString(e));
+  return 0;
+}
+
+// ---- streamed Lanczos: the same results without a stored basis (include/qhbm_engine.h; krylov.hip) ----
+}  // extern "C"
+
+namespace {
+
+constexpr uint32_t kKrylovRing = 3;             // v_{j-1}, v_j and v_{j+1} of pass one (the replay turns two of them)
+constexpr uint32_t kKrylovStreamBuffers = 5;    // psi, lam and the ring: state buffers per chunk element
+
+int check_krylov_stream_shape(qhbm_engine* h, int U, int m, int S) {
+  if (int rc = check_krylov_shape(h, U, m, 0)) return rc;
+  if (S < 1) return fail(h, "S must be at least 1");
+  return 0;
+}
+
+uint32_t krylov_stream_chunk_states(qhbm_engine* h, int U) {
+  uint32_t cs = chunk_states(h, U);
+  if (h->opt_chunk <= 0)
+    cs = uint32_t(std::min<size_t>(std::min<size_t>(size_t(U), 65535),
+                                   std::max<size_t>(1, budget_bytes(h) / (kKrylovStreamBuffers * state_bytes(h)))));
+  return cs;
+}
+
+// Rows j - 1 and j of pass one lie in the ring's slots (j - 1) % 3 and j % 3: the second slot follows the first, or the
+// pair wraps (j % 3 == 0) and it lies two slots below it.
+bool krylov_ring_wraps(int j) { return j >= 1 && j % int(kKrylovRing) == 0; }
+
+// The byte model in units of one state (8 * 2^n bytes).  Pass one launches what the stored local route launches, on ring
+// slots for basis rows: krylov_state_sweeps(m, 0).
+double krylov_tridiagonal_sweeps(int m) { return krylov_state_sweeps(m, 0); }
+
+// The replay, per group of sb outputs: the import 3; step 0 subtracts one row (3) and the scaled copy reads w and v_0 and
+// writes v_1 and the outputs (3 + sb); every later step subtracts two rows (4) and the scaled copy reads w and the outputs
+// and writes v_{j+1} and the outputs (2 + 2 sb).  m = 1: one import, and the combine kernel reads v_0 once per group and
+// writes the outputs.
+double krylov_replay_sweeps(int m, int S) {
+  if (m == 1) return 3.0 + double((S + kKrylovBlock - 1) / kKrylovBlock) + double(S);
+  double sweeps = 0.0;
+  for (int s0 = 0; s0 < S; s0 += kKrylovBlock) {
+    const int sb = std::min(kKrylovBlock, S - s0);
+    sweeps += 3.0 + double(6 + sb) + double(m - 2) * double(6 + 2 * sb);
+  }
+  return sweeps;
+}
+
+// What both passes reserve: the workspace, the ring beside it and the scratch of the import and of the sums.
+int reserve_krylov_stream(qhbm_engine* h, int U, uint32_t cs) {
+  const uint32_t n = uint32_t(h->model.n), n_eff = uint32_t(h->fwd.plan.n_eff), n_ops = uint32_t(h->model.n_ops);
+  if (int rc = ensure_state_buffers(h, cs, true)) return rc;
+  HIPCHK(h->kry_ring.reserve((size_t(kKrylovRing) * cs) << n_eff, false));
+  HIPCHK(h->import_norm2.reserve(size_t(U)));
+  HIPCHK(h->import_parts.reserve(state_norm_parts_count(n, cs)));
+  HIPCHK(h->evo_scale.reserve(cs));
+  HIPCHK(h->evo_up1.reserve(size_t(cs) * n_ops));
+  HIPCHK(h->kry_parts.reserve(krylov_coef_parts_count(n_eff, cs)));
+  HIPCHK(h->kry_norm_parts.reserve(state_norm_parts_count(n_eff, cs)));
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qhbm_describe_krylov_stream(qhbm_engine* h, int U, int m, int S, char* buf, size_t buf_len) {
+  if (!h || !buf || !buf_len) return 1;
+  if (int rc = check_krylov_stream_shape(h, U, m, S)) return rc;
+  DenseScope scope(h);
+  if (int rc = build_plans(h)) return rc;
+  const double state = double(size_t(8) << h->model.n);
+  const uint32_t cs = krylov_stream_chunk_states(h, U);
+  const int groups = (S + kKrylovBlock - 1) / kKrylovBlock;
+  std::snprintf(buf, buf_len,
+                "workspace_bytes=%.17g chunk_states=%u tridiagonal_applications=%d replay_applications=%d "
+                "tridiagonal_bytes_per_state=%.17g replay_bytes_per_state=%.17g",
+                double(kKrylovStreamBuffers) * double(cs) * double(state_bytes(h)), cs, m, (m - 1) * groups,
+                krylov_tridiagonal_sweeps(m) * state, krylov_replay_sweeps(m, S) * state);
+  return 0;
+}
+
+int qhbm_krylov_tridiagonal(qhbm_engine* h, const void* d_start_states, int U, const double* weights, int m, double* d_alpha,
+                            double* d_beta, int32_t* d_lengths, void* d_recurrence, void* stream) {
+  if (!h) return 1;
+  if (int rc = need_device(h)) return rc;
+  if (int rc = check_krylov_stream_shape(h, U, m, 1)) return rc;
+  if (int rc = check_evolve_states(h, d_start_states, U, "d_start_states")) return rc;
+  if (int rc = check_pointer(h, d_alpha, 8, "d_alpha")) return rc;
+  if (int rc = check_pointer(h, d_beta, 8, "d_beta")) return rc;
+  if (int rc = check_pointer(h, d_lengths, 4, "d_lengths")) return rc;
+  if (int rc = check_pointer(h, d_recurrence, 8, "d_recurrence")) return rc;
+  double R = 0.0;
+  if (int rc = weighted_radius(h, weights, &R)) return rc;
+  DenseScope scope(h);
+  if (int rc = upload_model(h)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  consume_workspace(h);
+  const uint32_t n = uint32_t(h->model.n), n_eff = uint32_t(h->fwd.plan.n_eff), n_ops = uint32_t(h->model.n_ops);
+  const size_t row = size_t(8) << n;
+  const uint32_t cs = krylov_stream_chunk_states(h, U);
+  if (int rc = reserve_krylov_stream(h, U, cs)) return rc;
+  if (aliases_workspace(h, d_start_states, size_t(U) * row)) return fail(h, "d_start_states lies inside the engine's workspace");
+  if (int rc = upload_evolve_weights(h, weights, 1.0, s)) return rc;
+  HIPCHK(launch_zero_fill(d_alpha, size_t(U) * size_t(m) * sizeof(double), s));
+  HIPCHK(launch_zero_fill(d_recurrence, size_t(U) * size_t(m) * 2 * sizeof(float2), s));  // (the pair of step 0 is (0, c_0))
+  const double threshold = std::ldexp(R, -16);
+  const size_t slot = size_t(cs) << n_eff;  // amplitudes from one slot of the ring to the next
+  float2* rec = static_cast<float2*>(d_recurrence);
+  float2* W = h->lam.p;
+  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += cs) {
+    const uint32_t c = std::min<uint32_t>(cs, uint32_t(U) - s0);
+    auto ring = [&](int j) { return h->kry_ring.p + size_t(j % int(kKrylovRing)) * slot; };
+    // v_0 = phi / ||phi|| into slot 0 at the workspace's pitch (zeros for norm 0 and in the padding)
+    hipEvent_t* iev = timer_begin(h, 0, s);
+    HIPCHK(launch_import_states(static_cast<const float2*>(d_start_states), n, n_eff, c, s0, ring(0), h->import_parts.p,
+                                h->import_norm2.p, s));
+    timer_end(iev, s);
+    HIPCHK(launch_krylov_init(c, h->import_norm2.p + s0, m, d_lengths + s0, h->evo_scale.p, s));
+    HIPCHK(launch_evolve_init(c, nullptr, nullptr, nullptr, h->evo_wr.p, n_ops, h->evo_up1.p, nullptr, s));
+    for (int j = 0; j < m; ++j) {
+      // w = H v_j: the ring has the workspace's pitch, so the observable kernel reads the slot itself at every n
+      if (int rc = run_observable_chunk(h, 0, c, h->evo_up1.p, false, s, true, false, ring(j), W)) return rc;
+      hipEvent_t* ev = timer_begin(h, 0, s);
+      // the step's pair in d_recurrence is the coefficient row of the project and subtract kernels: (c_{j-1}, c_j), (0, c_0)
+      float2* pair = rec + (size_t(s0) * size_t(m) + size_t(j)) * 2;
+      const uint32_t pair_pitch = 2 * uint32_t(m);
+      double* alpha_j = d_alpha + size_t(s0) * size_t(m) + size_t(j);
+      if (j == 0) {
+        HIPCHK(launch_krylov_project(W, n_eff, ring(0), 0, n_eff, c, 1, h->kry_parts.p, pair, pair_pitch, 1, 0, alpha_j, uint64_t(m), s));
+        HIPCHK(launch_krylov_subtract(W, n_eff, ring(0), 0, n_eff, c, 1, pair + 1, pair_pitch, h->kry_norm_parts.p, s));
+      } else {
+        // rows j - 1 and j in ONE launch of two rows, the launch of the stored route: where the pair wraps in the ring, row j
+        // lies two slots BELOW row j - 1 and the stride is negative
+        const int64_t stride = krylov_ring_wraps(j) ? -2 * int64_t(slot) : int64_t(slot);
+        HIPCHK(launch_krylov_project(W, n_eff, ring(j - 1), stride, n_eff, c, 2, h->kry_parts.p, pair, pair_pitch, 0, 1, alpha_j,
+                                     uint64_t(m), s));
+        HIPCHK(launch_krylov_subtract(W, n_eff, ring(j - 1), stride, n_eff, c, 2, pair, pair_pitch, h->kry_norm_parts.p, s));
+      }
+      HIPCHK(launch_krylov_norm(h->kry_norm_parts.p, n_eff, c, threshold, j, d_beta + size_t(s0) * size_t(m), uint64_t(m),
+                                d_lengths + s0, h->evo_scale.p, s));
+      // v_{j+1} = w / beta_j over v_{j-2} (scale 0 after a breakdown: zeros)
+      if (j + 1 < m) HIPCHK(launch_scale_copy_states(W, n_eff, ring(j + 1), n_eff, n, c, h->evo_scale.p, nullptr, s));
+      timer_end(ev, s);
+    }
+  }
+  return 0;
+}
+
+int qhbm_krylov_replay(qhbm_engine* h, const void* d_start_states, int U, const double* weights, int m, const double* d_beta,
+                       const int32_t* d_lengths, const void* d_recurrence, const void* d_coef, int S, void* d_out_states,
+                       void* stream) {
+  if (!h) return 1;
+  if (int rc = need_device(h)) return rc;
+  if (int rc = check_krylov_stream_shape(h, U, m, S)) return rc;
+  if (int rc = check_evolve_states(h, d_start_states, U, "d_start_states")) return rc;
+  if (int rc = check_pointer(h, d_beta, 8, "d_beta")) return rc;
+  if (int rc = check_pointer(h, d_lengths, 4, "d_lengths")) return rc;
+  if (int rc = check_pointer(h, d_recurrence, 8, "d_recurrence")) return rc;
+  if (int rc = check_pointer(h, d_coef, 8, "d_coef")) return rc;
+  if (int rc = check_pointer(h, d_out_states, 16, "d_out_states")) return rc;
+  const uint32_t n = uint32_t(h->model.n);
+  const size_t amps = size_t(1) << n, row = amps * sizeof(float2), out_bytes = size_t(U) * size_t(S) * row;
+  if (ranges_overlap(d_start_states, size_t(U) * row, d_out_states, out_bytes)) return fail(h, "d_out_states overlaps d_start_states");
+  if (aliases_workspace(h, d_out_states, out_bytes)) return fail(h, "d_out_states lies inside the engine's workspace");
+  if (weights)
+    for (int k = 0; k < h->model.n_ops; ++k)
+      if (!std::isfinite(weights[k])) return fail(h, "a weight is not finite");
+  DenseScope scope(h);
+  if (int rc = upload_model(h)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  consume_workspace(h);
+  const uint32_t n_eff = uint32_t(h->fwd.plan.n_eff), n_ops = uint32_t(h->model.n_ops);
+  const uint32_t cs = krylov_stream_chunk_states(h, U);
+  if (int rc = reserve_krylov_stream(h, U, cs)) return rc;
+  if (aliases_workspace(h, d_start_states, size_t(U) * row)) return fail(h, "d_start_states lies inside the engine's workspace");
+  if (aliases_workspace(h, d_out_states, out_bytes)) return fail(h, "d_out_states lies inside the engine's workspace");
+  if (int rc = upload_evolve_weights(h, weights, 1.0, s)) return rc;
+  const size_t slot = size_t(cs) << n_eff;
+  const float2* rec = static_cast<const float2*>(d_recurrence);
+  const float2* coef = static_cast<const float2*>(d_coef);
+  float2* out = static_cast<float2*>(d_out_states);
+  float2* W = h->lam.p;
+  for (uint32_t s0 = 0; s0 < uint32_t(U); s0 += cs) {
+    const uint32_t c = std::min<uint32_t>(cs, uint32_t(U) - s0);
+    HIPCHK(launch_evolve_init(c, nullptr, nullptr, nullptr, h->evo_wr.p, n_ops, h->evo_up1.p, nullptr, s));
+    if (m == 1) {  // out = coef[., 0] v_0: the combine kernel over the one row, imported at the caller's pitch
+      hipEvent_t* ev = timer_begin(h, 0, s);
+      HIPCHK(launch_import_states(static_cast<const float2*>(d_start_states), n, n, c, s0, h->kry_ring.p, h->import_parts.p,
+                                  h->import_norm2.p, s));
+      HIPCHK(launch_krylov_combine(h->kry_ring.p, 1, c, n, coef + size_t(s0) * size_t(S), uint32_t(S),
+                                   out + size_t(s0) * size_t(S) * amps, s));
+      timer_end(ev, s);
+      continue;
+    }
+    for (int g0 = 0; g0 < S; g0 += kKrylovBlock) {  // the recurrence runs once per group of eight outputs
+      const uint32_t sb = uint32_t(std::min(kKrylovBlock, S - g0));
+      float2 *cur = h->kry_ring.p, *nxt = h->kry_ring.p + slot;
+      hipEvent_t* iev = timer_begin(h, 0, s);
+      HIPCHK(launch_import_states(static_cast<const float2*>(d_start_states), n, n_eff, c, s0, cur, h->import_parts.p,
+                                  h->import_norm2.p, s));
+      timer_end(iev, s);
+      for (int j = 0; j + 1 < m; ++j) {
+        if (int rc = run_observable_chunk(h, 0, c, h->evo_up1.p, false, s, true, false, cur, W)) return rc;
+        hipEvent_t* ev = timer_begin(h, 0, s);
+        // w -= c_{j-1} v_{j-1} + c_j v_j by THE launch of pass one (the kernel instance decides the bits: DESIGN.md 6o), on
+        // the recorded pair; nxt holds v_{j-1}, one slot above or below cur
+        const float2* pair = rec + (size_t(s0) * size_t(m) + size_t(j)) * 2;
+        if (j == 0)
+          HIPCHK(launch_krylov_subtract(W, n_eff, cur, 0, n_eff, c, 1, pair + 1, 2 * uint32_t(m), h->kry_norm_parts.p, s));
+        else
+          HIPCHK(launch_krylov_subtract(W, n_eff, nxt, int64_t(cur - nxt), n_eff, c, 2, pair, 2 * uint32_t(m), h->kry_norm_parts.p, s));
+        HIPCHK(launch_krylov_replay(uint32_t(j), W, cur, nxt, n, n_eff, c, d_beta + size_t(s0) * size_t(m) + size_t(j), uint64_t(m),
+                                    coef + (size_t(s0) * size_t(S) + size_t(g0)) * size_t(m), uint32_t(m), uint32_t(S), sb,
+                                    out + (size_t(s0) * size_t(S) + size_t(g0)) * amps, s));
+        timer_end(ev, s);
+        std::swap(cur, nxt);  // v_{j+1} replaced v_{j-1}
+      }
+    }
+  }
   return 0;
 }
 

@@ -295,19 +295,20 @@ hipError_t launch_random_states(float2* out, uint32_t n_states, uint32_t n, uint
                                 hipStream_t stream);
 
 // ---- Lanczos bases of caller-supplied states and sums over a stored basis (krylov.hip) ----
-constexpr int kKrylovBlock = 8;  // basis rows of one project / subtract sweep, outputs of one combine sweep
+constexpr int kKrylovBlock = 8;  // basis rows of one project / subtract sweep, outputs of one combine or replay sweep
 // Doubles of scratch one project sweep (`parts`) of a chunk of c states of n qubits needs.
 size_t krylov_coef_parts_count(uint32_t n, uint32_t c);
 // scale[i] = 1, lengths[i] = m for i < c; a state with norm2[i] = 0: scale 0, length 0.
 hipError_t launch_krylov_init(uint32_t c, const double* norm2, int m, int32_t* lengths, double* scale, hipStream_t stream);
 // c_k = <v_k, w> for the nb <= 8 basis rows at `rows` (row k of the chunk's state i at rows + k row_stride_amps + i 2^n)
+// -- row_stride_amps may be negative (the ring of qhbm_krylov_tridiagonal: row k + 1 below row k in memory) --
 // and the chunk's c states w (pitch 2^n_w amplitudes), complex fp64 in a fixed order; coef[i, first + k] = c_k rounded to
 // complex64; alpha_at >= 0: alpha[i alpha_pitch] += Re c_{alpha_at}.
-hipError_t launch_krylov_project(const float2* w, uint32_t n_w, const float2* rows, uint64_t row_stride_amps, uint32_t n, uint32_t c,
+hipError_t launch_krylov_project(const float2* w, uint32_t n_w, const float2* rows, int64_t row_stride_amps, uint32_t n, uint32_t c,
                                  uint32_t nb, double* parts, float2* coef, uint32_t coef_pitch, uint32_t first, int alpha_at,
                                  double* alpha, uint64_t alpha_pitch, hipStream_t stream);
 // w -= sum_k coef[i, k] v_k over the same rows, k ascending, fp32; norm_parts (or NULL): per-workgroup sums of |w|^2.
-hipError_t launch_krylov_subtract(float2* w, uint32_t n_w, const float2* rows, uint64_t row_stride_amps, uint32_t n, uint32_t c,
+hipError_t launch_krylov_subtract(float2* w, uint32_t n_w, const float2* rows, int64_t row_stride_amps, uint32_t n, uint32_t c,
                                   uint32_t nb, const float2* coef, uint32_t coef_pitch, double* norm_parts, hipStream_t stream);
 // Per state i < c with scale[i] != 0: norm = sqrt(sum of its parts); norm <= threshold: lengths[i] = j + 1, beta 0, scale 0;
 // else beta[i beta_pitch + j] = norm, scale[i] = 1 / norm.  scale[i] = 0 stays: beta 0.
@@ -316,6 +317,16 @@ hipError_t launch_krylov_norm(const double* norm_parts, uint32_t n, uint32_t c, 
 // out[u, s] = sum_j coef[u, s, j] basis[j, u]: basis [m, U, 2^n], coef [U, S, m], out [U, S, 2^n]
 hipError_t launch_krylov_combine(const float2* basis, uint32_t m, uint32_t U, uint32_t n, const float2* coef, uint32_t S,
                                  float2* out, hipStream_t stream);
+// The scaled copy of a step of the replay of a recorded recurrence (qhbm_krylov_replay), which also accumulates: for the
+// chunk's c states, all three at a pitch of 2^n_eff amplitudes (w = H v_j - c_{j-1} v_{j-1} - c_j v_j as
+// launch_krylov_subtract left it, vcur = v_j, vnext = v_{j-1} on entry),
+//   vnext = v_{j+1} = float(double(w) f), f = 1 / beta[i beta_pitch] (0 where that is 0); zeros in the padding
+//   out[i, s] += coef[i, s, j + 1] v_{j+1} for s < sb <= 8   (j = 0: out[i, s] = coef[i, s, 0] v_0 + coef[i, s, 1] v_1)
+// beta: beta_j of the chunk's first state; coef [., S, m] and out [., S, 2^n] at the chunk's first state and the group's
+// first output.  vcur is read at j = 0 only.
+hipError_t launch_krylov_replay(uint32_t j, const float2* w, const float2* vcur, float2* vnext, uint32_t n, uint32_t n_eff,
+                                uint32_t c, const double* beta, uint64_t beta_pitch, const float2* coef, uint32_t m, uint32_t S,
+                                uint32_t sb, float2* out, hipStream_t stream);
 
 // ---- the weighted Gram matrix of M states (gram.hip) ----
 constexpr int kGramMaxStates = 1024;

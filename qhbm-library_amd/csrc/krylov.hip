@@ -17,6 +17,9 @@
 //   krylov_init_kernel           scale = 1, length = m (norm 0: scale 0, length 0) from the import's squared norms
 //   krylov_combine_kernel<SB>    out[u, s0 + s] = sum_j coef[u, s0 + s, j] basis[j, u], j ascending, fp32, s < SB <= 8:
 //                                every basis word is read once for SB outputs held in registers        m reads, SB writes
+//   krylov_replay_kernel<SB, FIRST>  the scaled copy of a step of qhbm_krylov_replay, which also accumulates:
+//                                v_{j+1} = w * scale over v_{j-1}, w as krylov_subtract_kernel left it from RECORDED
+//                                coefficients, and out_s += coef[s, j + 1] v_{j+1}, SB <= 8 outputs  1 + SB reads, 1 + SB writes
 // v_{j+1} = w * scale is import_states.hip's launch_scale_copy_states (1 read, 1 write), which also takes w from the
 // workspace's pitch to the caller's.
 //
@@ -177,6 +180,57 @@ __global__ __launch_bounds__(kSweepThreads) void krylov_combine_kernel(const flo
   }
 }
 
+// The scaled copy of a replayed step (qhbm_krylov_replay), which also accumulates: w = H v_j - c_{j-1} v_{j-1} - c_j v_j as
+// krylov_subtract_kernel left it, vnext (v_{j-1} on entry) and, FIRST only, vcur = v_0, all at a pitch of `pitch` words, the
+// first `words` of them the state; beta: the step's beta_j of the chunk's first state; cf: coef[., s0, 0] and o:
+// out[., s0, 0] of the chunk's first state.
+//   vnext = v_{j+1} = float(double(w) f), f = 1 / beta_j or 0 where beta_j = 0 (krylov_norm_kernel's scale; the expression
+//   is scale_copy_kernel's); zeros in the padding;  out_s += coef[s, j + 1] v_{j+1}, s < SB          1 + SB reads, 1 + SB writes
+// FIRST (j = 0): out_s starts as coef[s, 0] v_0 + coef[s, 1] v_1 -- no zero fill                      2 reads, 1 + SB writes
+template <uint32_t SB, bool FIRST>
+__global__ __launch_bounds__(kSweepThreads) void krylov_replay_kernel(const float4* __restrict__ w, const float4* __restrict__ vcur,
+                                                                      float4* __restrict__ vnext, uint64_t pitch, uint64_t words,
+                                                                      const double* __restrict__ beta, uint64_t beta_pitch,
+                                                                      const float2* __restrict__ coef, uint32_t m, uint32_t S,
+                                                                      uint32_t j, float4* __restrict__ out) {
+  const float4* wr = w + uint64_t(blockIdx.y) * pitch;
+  const float4* vc = vcur + uint64_t(blockIdx.y) * pitch;
+  float4* vn = vnext + uint64_t(blockIdx.y) * pitch;
+  const float2* cf = coef + uint64_t(blockIdx.y) * S * m;
+  float4* o = out + uint64_t(blockIdx.y) * S * words;
+  const double b = beta[uint64_t(blockIdx.y) * beta_pitch];
+  const double f = b != 0.0 ? 1.0 / b : 0.0;
+  float2 t0[SB], t1[SB];
+#pragma unroll
+  for (uint32_t s = 0; s < SB; ++s) {
+    t0[s] = cf[uint64_t(s) * m];  // (FIRST only)
+    t1[s] = cf[uint64_t(s) * m + j + 1];
+  }
+  for (uint64_t i = uint64_t(blockIdx.x) * kSweepThreads + threadIdx.x; i < pitch; i += uint64_t(gridDim.x) * kSweepThreads) {
+    if (i >= words) {  // (the workspace's padding: idle qubits stay |0>)
+      vn[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      continue;
+    }
+    const float4 a = wr[i];
+    const float4 v = make_float4(float(double(a.x) * f), float(double(a.y) * f), float(double(a.z) * f), float(double(a.w) * f));
+    vn[i] = v;
+    float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (FIRST) v0 = vc[i];
+#pragma unroll
+    for (uint32_t s = 0; s < SB; ++s) {
+      float4 acc;
+      if (FIRST) {
+        const float4 d = sweep_cmul(t0[s], v0);
+        acc = make_float4(0.f + d.x, 0.f + d.y, 0.f + d.z, 0.f + d.w);  // (krylov_combine_kernel starts its sum at zero)
+      } else {
+        acc = o[uint64_t(s) * words + i];
+      }
+      const float4 d = sweep_cmul(t1[s], v);
+      o[uint64_t(s) * words + i] = make_float4(acc.x + d.x, acc.y + d.y, acc.z + d.z, acc.w + d.w);
+    }
+  }
+}
+
 template <uint32_t NB>
 void kry_launch_project(dim3 grid, hipStream_t stream, const float4* w, uint64_t w_pitch, const float4* rows, uint64_t row_stride,
                         uint64_t words, double* part) {
@@ -198,6 +252,18 @@ template <uint32_t SB>
 void kry_launch_combine(dim3 grid, hipStream_t stream, const float4* basis, uint64_t row_stride, uint64_t words, uint32_t m,
                         const float2* coef, uint32_t S, float4* out) {
   hipLaunchKernelGGL((krylov_combine_kernel<SB>), grid, dim3(kSweepThreads), 0, stream, basis, row_stride, words, m, coef, S, out);
+}
+
+template <uint32_t SB>
+void kry_launch_replay(bool first, dim3 grid, hipStream_t stream, const float4* w, const float4* vcur, float4* vnext, uint64_t pitch,
+                       uint64_t words, const double* beta, uint64_t beta_pitch, const float2* coef, uint32_t m, uint32_t S, uint32_t j,
+                       float4* out) {
+  if (first)
+    hipLaunchKernelGGL((krylov_replay_kernel<SB, true>), grid, dim3(kSweepThreads), 0, stream, w, vcur, vnext, pitch, words, beta,
+                       beta_pitch, coef, m, S, j, out);
+  else
+    hipLaunchKernelGGL((krylov_replay_kernel<SB, false>), grid, dim3(kSweepThreads), 0, stream, w, vcur, vnext, pitch, words, beta,
+                       beta_pitch, coef, m, S, j, out);
 }
 
 #define KRY_DISPATCH(count, call) \
@@ -224,7 +290,7 @@ hipError_t launch_krylov_init(uint32_t c, const double* norm2, int m, int32_t* l
   return hipGetLastError();
 }
 
-hipError_t launch_krylov_project(const float2* w, uint32_t n_w, const float2* rows, uint64_t row_stride_amps, uint32_t n, uint32_t c,
+hipError_t launch_krylov_project(const float2* w, uint32_t n_w, const float2* rows, int64_t row_stride_amps, uint32_t n, uint32_t c,
                                  uint32_t nb, double* parts, float2* coef, uint32_t coef_pitch, uint32_t first, int alpha_at,
                                  double* alpha, uint64_t alpha_pitch, hipStream_t stream) {
   if (n < 1 || n_w < n || c == 0 || c > 65535u || nb < 1 || nb > kKrylovBlock || first + nb > coef_pitch) return hipErrorInvalidValue;
@@ -232,7 +298,7 @@ hipError_t launch_krylov_project(const float2* w, uint32_t n_w, const float2* ro
   const uint32_t slices = sweep_slices(words);
   const dim3 grid(slices, c);
   const float4 *w4 = reinterpret_cast<const float4*>(w), *r4 = reinterpret_cast<const float4*>(rows);
-#define KRY_CALL(NB) kry_launch_project<NB>(grid, stream, w4, w_pitch, r4, row_stride_amps / 2, words, parts)
+#define KRY_CALL(NB) kry_launch_project<NB>(grid, stream, w4, w_pitch, r4, uint64_t(row_stride_amps / 2), words, parts)
   KRY_DISPATCH(nb, KRY_CALL)
 #undef KRY_CALL
   hipLaunchKernelGGL(krylov_coef_kernel, dim3(c), dim3(kSweepThreads), 0, stream, parts, slices, nb, coef, coef_pitch, first, alpha_at,
@@ -240,14 +306,14 @@ hipError_t launch_krylov_project(const float2* w, uint32_t n_w, const float2* ro
   return hipGetLastError();
 }
 
-hipError_t launch_krylov_subtract(float2* w, uint32_t n_w, const float2* rows, uint64_t row_stride_amps, uint32_t n, uint32_t c,
+hipError_t launch_krylov_subtract(float2* w, uint32_t n_w, const float2* rows, int64_t row_stride_amps, uint32_t n, uint32_t c,
                                   uint32_t nb, const float2* coef, uint32_t coef_pitch, double* norm_parts, hipStream_t stream) {
   if (n < 1 || n_w < n || c == 0 || c > 65535u || nb < 1 || nb > kKrylovBlock) return hipErrorInvalidValue;
   const uint64_t words = uint64_t(1) << (n - 1), w_pitch = uint64_t(1) << (n_w - 1);
   const dim3 grid(sweep_slices(words), c);
   float4* w4 = reinterpret_cast<float4*>(w);
   const float4* r4 = reinterpret_cast<const float4*>(rows);
-#define KRY_CALL(NB) kry_launch_subtract<NB>(norm_parts != nullptr, grid, stream, w4, w_pitch, r4, row_stride_amps / 2, words, coef, coef_pitch, norm_parts)
+#define KRY_CALL(NB) kry_launch_subtract<NB>(norm_parts != nullptr, grid, stream, w4, w_pitch, r4, uint64_t(row_stride_amps / 2), words, coef, coef_pitch, norm_parts)
   KRY_DISPATCH(nb, KRY_CALL)
 #undef KRY_CALL
   return hipGetLastError();
@@ -277,6 +343,20 @@ hipError_t launch_krylov_combine(const float2* basis, uint32_t m, uint32_t U, ui
 #undef KRY_CALL
     }
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_krylov_replay(uint32_t j, const float2* w, const float2* vcur, float2* vnext, uint32_t n, uint32_t n_eff,
+                                uint32_t c, const double* beta, uint64_t beta_pitch, const float2* coef, uint32_t m, uint32_t S, uint32_t sb,
+                                float2* out, hipStream_t stream) {
+  if (n < 1 || n_eff < n || n_eff > 40 || c == 0 || c > 65535u || m < 2 || j + 1 >= m || sb < 1 || sb > S) return hipErrorInvalidValue;
+  const uint64_t words = uint64_t(1) << (n - 1), pitch = uint64_t(1) << (n_eff - 1);
+  const dim3 grid(sweep_slices(pitch), c);
+  const float4 *w4 = reinterpret_cast<const float4*>(w), *c4 = reinterpret_cast<const float4*>(vcur);
+  float4 *n4 = reinterpret_cast<float4*>(vnext), *o4 = reinterpret_cast<float4*>(out);
+#define KRY_CALL(SB) kry_launch_replay<SB>(j == 0, grid, stream, w4, c4, n4, pitch, words, beta, beta_pitch, coef, m, S, j, o4)
+  KRY_DISPATCH(sb, KRY_CALL)
+#undef KRY_CALL
   return hipGetLastError();
 }
 

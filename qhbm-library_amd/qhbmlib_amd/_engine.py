@@ -48,6 +48,7 @@ ABI_SYMBOLS = (
     "qhbm_describe_schedule_from_states", "qhbm_statevector_vjp_from_states",
     "qhbm_apply_observables", "qhbm_evolve_states", "qhbm_describe_evolution", "qhbm_random_states",
     "qhbm_krylov_basis", "qhbm_krylov_combine", "qhbm_describe_krylov",
+    "qhbm_krylov_tridiagonal", "qhbm_krylov_replay", "qhbm_describe_krylov_stream",
     "qhbm_gram_scratch_bytes", "qhbm_weighted_gram",
     "qhbm_reduced_density_scratch_bytes", "qhbm_reduced_density",
     "qhbm_subsystem_apply_scratch_bytes", "qhbm_subsystem_apply",
@@ -150,6 +151,9 @@ def load_library():
     lib.qhbm_krylov_basis.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]
     lib.qhbm_krylov_combine.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp]
     lib.qhbm_describe_krylov.argtypes = [vp, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
+    lib.qhbm_krylov_tridiagonal.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]
+    lib.qhbm_krylov_replay.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp]
+    lib.qhbm_describe_krylov_stream.argtypes = [vp, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
     lib.qhbm_gram_scratch_bytes.argtypes = [i32, i32, ctypes.POINTER(ctypes.c_size_t)]
     lib.qhbm_weighted_gram.argtypes = [vp, i32, i32, vp, vp, vp, vp]
     lib.qhbm_reduced_density_scratch_bytes.argtypes = [i32, i32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_size_t)]
@@ -1089,6 +1093,63 @@ class Engine:
                                               lengths.data_ptr(), self._stream()))
     norms = torch.linalg.vector_norm(torch.view_as_real(states).flatten(1), dim=1, dtype=torch.float64)
     return basis, alpha, beta, lengths, norms
+
+  def describe_krylov_stream(self, num_states, num_steps, num_outputs=1):
+    """{"workspace_bytes", "chunk_states", "tridiagonal_applications", "replay_applications", "tridiagonal_bytes_per_state",
+    "replay_bytes_per_state"} of `krylov_tridiagonal` and of a `krylov_replay` of `num_outputs` outputs per state on
+    `num_states` states; needs no device."""
+    buf = ctypes.create_string_buffer(512)
+    self._check(self._lib.qhbm_describe_krylov_stream(self._h, int(num_states), int(num_steps), int(num_outputs), buf, len(buf)))
+    fields = dict(item.split("=") for item in buf.value.decode().split())
+    return {k: float(v) if k.endswith("bytes") or k.endswith("per_state") else int(v) for k, v in fields.items()}
+
+  def krylov_tridiagonal(self, states, num_steps, weights=None):
+    """Pass one of the streamed Lanczos recurrence (include/qhbm_engine.h qhbm_krylov_tridiagonal): (alpha [batch, m], beta
+    [batch, m] float64, lengths [batch] int32, recurrence [batch, m, 2] complex64, start norms [batch] float64), all on the
+    device.  alpha, beta and lengths are bit for bit those of `krylov_basis(reorthogonalise=False)`; no basis is stored.
+    The input is never written."""
+    states, _ = self._prep_states(states, np.zeros(self.n_params, np.float32))
+    w = self._weights(weights)
+    m, num = int(num_steps), states.shape[0]
+    if not 1 <= m <= 1024:
+      raise ValueError("num_steps must be in [1, 1024]")
+    alpha = torch.empty((num, m), dtype=torch.float64, device=self.device)
+    beta = torch.empty((num, m), dtype=torch.float64, device=self.device)
+    lengths = torch.empty((num,), dtype=torch.int32, device=self.device)
+    recurrence = torch.empty((num, m, 2), dtype=torch.complex64, device=self.device)
+    self.retained = None
+    with torch.cuda.device(self.device):
+      self._check(self._lib.qhbm_krylov_tridiagonal(self._h, states.data_ptr(), num, None if w is None else w.ctypes.data, m,
+                                                    alpha.data_ptr(), beta.data_ptr(), lengths.data_ptr(),
+                                                    recurrence.data_ptr(), self._stream()))
+    norms = torch.linalg.vector_norm(torch.view_as_real(states).flatten(1), dim=1, dtype=torch.float64)
+    return alpha, beta, lengths, recurrence, norms
+
+  def krylov_replay(self, states, beta, lengths, recurrence, coef, weights=None):
+    """Pass two (qhbm_krylov_replay): out[u, s] = sum_j coef[u, s, j] v_j(u), complex64 [batch, S, 2^n], for coefficients
+    [batch, S, m]; the v_j are regenerated from the SAME `states` and `weights` and from what `krylov_tridiagonal` returned
+    for them.  The input is never written."""
+    states, _ = self._prep_states(states, np.zeros(self.n_params, np.float32))
+    w = self._weights(weights)
+    num = states.shape[0]
+    beta = torch.as_tensor(beta).to(device=self.device, dtype=torch.float64).contiguous()
+    if beta.dim() != 2 or beta.shape[0] != num or not 1 <= beta.shape[1] <= 1024:
+      raise ValueError(f"beta must have shape [{num}, m] with m in [1, 1024], got {tuple(beta.shape)}")
+    m = int(beta.shape[1])
+    lengths = torch.as_tensor(lengths).to(device=self.device, dtype=torch.int32).contiguous()
+    recurrence = torch.as_tensor(recurrence).to(device=self.device, dtype=torch.complex64).contiguous()
+    coef = torch.as_tensor(coef).to(device=self.device, dtype=torch.complex64).contiguous()
+    if tuple(lengths.shape) != (num,) or tuple(recurrence.shape) != (num, m, 2):
+      raise ValueError(f"lengths must have shape [{num}] and recurrence [{num}, {m}, 2]")
+    if coef.dim() != 3 or coef.shape[0] != num or coef.shape[1] < 1 or coef.shape[2] != m:
+      raise ValueError(f"coef must have shape [{num}, S, {m}] with S >= 1, got {tuple(coef.shape)}")
+    out = torch.empty((num, int(coef.shape[1]), 1 << self.n_qubits), dtype=torch.complex64, device=self.device)
+    self.retained = None
+    with torch.cuda.device(self.device):
+      self._check(self._lib.qhbm_krylov_replay(self._h, states.data_ptr(), num, None if w is None else w.ctypes.data, m,
+                                               beta.data_ptr(), lengths.data_ptr(), recurrence.data_ptr(), coef.data_ptr(),
+                                               int(coef.shape[1]), out.data_ptr(), self._stream()))
+    return out
 
   def sample(self, bits, params, n_shots, seed=0, shift_gate=-1, shift=0.0):
     """int8 [batch, n_shots, n_qubits]: computational-basis samples of C(params)|x_u>;

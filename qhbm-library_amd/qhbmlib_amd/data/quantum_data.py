@@ -87,7 +87,8 @@ class StateVectorData(QuantumData):
   @classmethod
   def ground_state(cls, operators, **kwargs):
     """The ground state of H = sum_k operators[k] as quantum data (one state, weight 1), without a dense matrix: the
-    lowest Ritz vector of a restarted Krylov space (`inference.ground_state(operators, **kwargs)`)."""
+    lowest Ritz vector of a restarted Krylov space (`inference.ground_state(operators, **kwargs)`; `store_basis=False`
+    keeps three vectors in memory, not the whole basis)."""
     from qhbmlib_amd.inference import krylov, thermal  # pylint: disable=import-outside-toplevel
     ops = thermal._operator_list(operators)  # pylint: disable=protected-access
     qubits = thermal._qubits_of(ops, kwargs.get("qubits"))  # pylint: disable=protected-access

@@ -6,8 +6,8 @@ from qhbmlib_amd.inference.ebm import (AnalyticEnergyInference, BernoulliEnergyI
                                        GibbsWithGradientsInference)
 from qhbmlib_amd.inference.ebm_utils import probabilities
 from qhbmlib_amd.inference.information import information_matrix, natural_gradient
-from qhbmlib_amd.inference.krylov import (KrylovSpace, ThermalSweep, ground_state, krylov_space, spectrum_extremes,
-                                          thermal_sweep)
+from qhbmlib_amd.inference.krylov import (KrylovSpace, StreamedKrylovSpace, ThermalSweep, ground_state, krylov_space,
+                                          spectrum_extremes, thermal_sweep)
 from qhbmlib_amd.inference.qhbm import QHBM
 from qhbmlib_amd.inference.qhbm_utils import density_matrix, fidelity
 from qhbmlib_amd.inference.qmhl_loss import qmhl
@@ -24,7 +24,7 @@ from qhbmlib_amd.inference.vqt_loss import vqt
 
 __all__ = ["AnalyticEnergyInference", "AnalyticQuantumInference", "BernoulliEnergyInference", "CapturedLoss",
            "EnergyInference", "EnergyInferenceBase", "GibbsWithGradientsInference", "KrylovSpace", "QHBM", "QuantumInference",
-           "SampledQuantumInference", "StateMetrics", "ThermalEnsemble", "ThermalSweep", "apply_operator", "density_matrix",
+           "SampledQuantumInference", "StateMetrics", "StreamedKrylovSpace", "ThermalEnsemble", "ThermalSweep", "apply_operator", "density_matrix",
            "fidelity", "ground_state", "imaginary_time_evolution", "information_matrix", "krylov_space", "mutual_information",
            "natural_gradient", "probabilities", "qmhl", "real_time_evolution", "reduced_density_matrix",
            "sampled_ensemble_reduced", "sampled_reduced_density_matrix", "spectrum_extremes", "state_metrics", "subsystem_entropy", "thermal_ensemble",

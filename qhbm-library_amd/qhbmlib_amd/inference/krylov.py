@@ -11,6 +11,11 @@ span{phi, H phi, ..., H^{m-1} phi} and the tridiagonal T = V^dagger H V, and eve
 (finite-temperature Lanczos: Jaklic and Prelovsek, Phys. Rev. B 49, 5065 (1994)).  Everything of size 2^n is a kernel
 of the engine over device-resident vectors; everything of size m^3 is float64 numpy on the host (`ritz`,
 `evolution_coefficients`, `ftlm_log_weights`, `ftlm_energy`: plain functions of (alpha, beta, lengths), no device).
+
+`store_basis=False` gives the same results without V in memory, m U 2^n amplitudes: pass one
+(`qhbm_krylov_tridiagonal`) runs the local recurrence on three vectors and keeps T and the coefficients it subtracted; what
+is a number is a function of T and costs nothing more; what is a vector, sum_j coef[j] v_j, costs one replay of the
+recurrence (`qhbm_krylov_replay`), which regenerates each v_j bit for bit and adds it into up to eight outputs as it passes.
 """
 import math
 
@@ -202,6 +207,62 @@ class KrylovSpace:
       return out, None
     return _normalise(out), torch.from_numpy(logs).to(out.device)
 
+  def evolve_many(self, taus, mode=0):
+    """`evolve` for every tau of `taus` from ONE sum over the space (a streamed space: one replay per eight taus): (states
+    [M, len(taus), 2^n], float64 [M, len(taus)] log norms, or None in real time)."""
+    if mode not in (0, 1):
+      raise ValueError("mode must be 0 (imaginary time) or 1 (real time)")
+    taus = np.asarray(taus, np.float64).reshape(-1)
+    if len(taus) < 1 or not np.isfinite(taus).all() or (mode == 0 and (taus < 0).any()):
+      raise ValueError(f"taus must be finite (at least one), and >= 0 in imaginary time, got {taus}")
+    norms = self.norms
+    coef = np.zeros((self.num_vectors, len(taus), self.num_steps), np.complex128)
+    logs = np.full((self.num_vectors, len(taus)), -np.inf)
+    for u, (theta, s) in enumerate(self.ritz()):
+      for t, tau in enumerate(taus):
+        coef[u, t], log_norm = evolution_coefficients(theta, s, float(tau), mode, self.num_steps)
+        if mode == 0 and len(theta):
+          logs[u, t] = log_norm + math.log(norms[u])
+        if mode == 1:
+          coef[u, t] *= norms[u]
+    out = self._combine(coef)
+    if mode == 1:
+      return out, None
+    return _normalise(out.flatten(0, 1)).reshape(out.shape), torch.from_numpy(logs).to(out.device)
+
+
+class StreamedKrylovSpace(KrylovSpace):
+  """The Lanczos spaces of M start states WITHOUT a stored basis (`krylov_space(store_basis=False)`): the
+  interface of `KrylovSpace`, `basis` is None.  `alpha`, `beta`, `lengths`, `norms`, `radius`, `ritz()` and `residuals()`
+  come from pass one alone.  `ritz_states`, `evolve` and `evolve_many` cost one replay of the recurrence per eight outputs:
+  the space keeps the start states, the operators and the weights, and opens an engine per replay."""
+
+  def __init__(self, operators, weights, qubits, starts, alpha, beta, lengths, recurrence, norms, radius):
+    super().__init__(operators, weights, qubits, None, alpha, beta, lengths, norms, radius)
+    self.starts = starts
+    self.recurrence = recurrence
+    self.replays = 0  # replays of the recurrence this space has paid for
+
+  @property
+  def num_steps(self):
+    return int(self._device[0].shape[1])
+
+  @property
+  def num_vectors(self):
+    return int(self._device[0].shape[0])
+
+  def _combine(self, coef):
+    coef = torch.from_numpy(np.ascontiguousarray(coef.astype(np.complex64)))
+    eng = thermal._engine_for(self.operators, self.qubits)  # pylint: disable=protected-access
+    try:
+      _, beta, lengths, _ = self._device
+      out = eng.krylov_replay(self.starts, beta, lengths, self.recurrence, coef, self.operator_weights)
+      torch.cuda.current_stream(eng.device).synchronize()  # (the engine's workspace goes with it)
+    finally:
+      eng.close()
+    self.replays += 1
+    return out
+
 
 def _starts(eng, n, states, num_vectors, seed):
   if states is not None:
@@ -218,16 +279,35 @@ def _radius(operators, qubits, weights):
   return float(sum(abs(float(w)) * s for w, s in zip(weights, sums)))
 
 
+def _reorthogonalise(reorthogonalise, store_basis):
+  """None: full with a stored basis, local without one; full reorthogonalisation needs the stored basis."""
+  if reorthogonalise is None:
+    return bool(store_basis)
+  if reorthogonalise and not store_basis:
+    raise ValueError("store_basis=False runs the local recurrence: full reorthogonalisation (reorthogonalise=True) needs "
+                     "the stored basis")
+  return bool(reorthogonalise)
+
+
 def krylov_space(operators, states=None, num_steps=DEFAULT_STEPS, num_vectors=None, seed=None, weights=None, qubits=None,
-                 reorthogonalise=True):
+                 reorthogonalise=None, store_basis=True):
   """The `KrylovSpace` of H = sum_k weights[k] operators[k] from `states` [M, 2^n], or (states=None) from `num_vectors`
   (default 16) random-sign vectors of the engine's generator under `seed` (default 0): the vectors `thermal_ensemble`
   draws for the same seed.  `reorthogonalise`: full (two rounds of classical Gram-Schmidt against every stored vector) or
-  local (the three-term recurrence)."""
+  local (the three-term recurrence); None: full with a stored basis, local without.  `store_basis=False`: a
+  `StreamedKrylovSpace` -- no basis in memory, vectors by a replay of the recurrence (local only)."""
+  reorthogonalise = _reorthogonalise(reorthogonalise, store_basis)
   operators = thermal._operator_list(operators)  # pylint: disable=protected-access
   qubits = thermal._qubits_of(operators, qubits)  # pylint: disable=protected-access
   eng = thermal._engine_for(operators, qubits)  # pylint: disable=protected-access
   starts = _starts(eng, len(qubits), states, num_vectors, seed)
+  if not store_basis:
+    alpha, beta, lengths, recurrence, norms = eng.krylov_tridiagonal(starts, int(num_steps), weights)
+    torch.cuda.current_stream(eng.device).synchronize()  # (the engine's workspace goes with it)
+    eng.close()
+    starts = torch.as_tensor(starts).to(device=alpha.device, dtype=torch.complex64)
+    return StreamedKrylovSpace(operators, None if weights is None else [float(w) for w in weights], qubits, starts, alpha, beta,
+                               lengths, recurrence, norms, _radius(operators, qubits, weights))
   basis, alpha, beta, lengths, norms = eng.krylov_basis(starts, int(num_steps), weights, reorthogonalise)
   torch.cuda.current_stream(eng.device).synchronize()  # (the engine's workspace goes with it)
   eng.close()
@@ -267,10 +347,12 @@ class ThermalSweep:
 
 
 def thermal_sweep(operators, betas, num_vectors=None, num_steps=DEFAULT_STEPS, seed=None, start="random", qubits=None,
-                  weights=None, reorthogonalise=True):
+                  weights=None, reorthogonalise=None, store_basis=True):
   """The `ThermalSweep` of H = sum_k weights[k] operators[k] over `betas`.  start="random": `num_vectors` (default 16)
   random-sign vectors, the ones `thermal_ensemble` draws for the same `seed`; start="basis": all 2^n basis states (exact
-  once the spaces are exhausted, at most 14 qubits)."""
+  once the spaces are exhausted, at most 14 qubits).  `store_basis=False`: log Z, <H> and S from pass one alone, no basis in
+  memory; `ensemble(beta)` then costs one replay."""
+  _reorthogonalise(reorthogonalise, store_basis)
   operators = thermal._operator_list(operators)  # pylint: disable=protected-access
   qubits = thermal._qubits_of(operators, qubits)  # pylint: disable=protected-access
   betas = np.asarray(betas, np.float64).reshape(-1)
@@ -287,21 +369,23 @@ def thermal_sweep(operators, betas, num_vectors=None, num_steps=DEFAULT_STEPS, s
   elif start != "random":
     raise ValueError(f"start must be 'random' or 'basis', got {start!r}")
   space = krylov_space(operators, states, min(int(num_steps), 1 << n) if start == "basis" else num_steps, num_vectors, seed,
-                       weights, qubits, reorthogonalise)
+                       weights, qubits, reorthogonalise, store_basis)
   return ThermalSweep(space, betas, start)
 
 
 def ground_state(operators, num_steps=24, max_restarts=8, tolerance=2.0**-20, state=None, seed=None, weights=None, qubits=None,
-                 reorthogonalise=True):
+                 reorthogonalise=None, store_basis=True):
   """(E_0 float64, state [2^n] complex64 on the device, residual, restarts): the lowest Ritz pair of a space of
   `num_steps`, restarted from its Ritz vector until residual = ||H y - theta y|| <= tolerance R or `max_restarts` restarts
-  are spent.  Starts from `state` or from a random-sign vector under `seed`."""
+  are spent.  Starts from `state` or from a random-sign vector under `seed`.  `store_basis=False`: one pass and one replay
+  per restart, three vectors in memory."""
+  _reorthogonalise(reorthogonalise, store_basis)
   operators = thermal._operator_list(operators)  # pylint: disable=protected-access
   qubits = thermal._qubits_of(operators, qubits)  # pylint: disable=protected-access
   current = None if state is None else torch.as_tensor(state).reshape(1, -1)
   restarts = 0
   while True:
-    space = krylov_space(operators, current, num_steps, 1, seed, weights, qubits, reorthogonalise)
+    space = krylov_space(operators, current, num_steps, 1, seed, weights, qubits, reorthogonalise, store_basis)
     theta, _ = space.ritz()[0]
     if len(theta) == 0:
       raise ValueError("the start state has norm 0")
@@ -312,11 +396,13 @@ def ground_state(operators, num_steps=24, max_restarts=8, tolerance=2.0**-20, st
     restarts += 1
 
 
-def spectrum_extremes(operators, num_steps=DEFAULT_STEPS, seed=None, weights=None, qubits=None, state=None, reorthogonalise=True):
+def spectrum_extremes(operators, num_steps=DEFAULT_STEPS, seed=None, weights=None, qubits=None, state=None, reorthogonalise=None,
+                      store_basis=True):
   """((theta_min, residual), (theta_max, residual)) of one Krylov space from `state` (default: a random-sign vector):
-  Ritz values lie inside [E_min, E_max] and converge to its ends first."""
+  Ritz values lie inside [E_min, E_max] and converge to its ends first.  `store_basis=False`: pass one alone, no replay."""
+  _reorthogonalise(reorthogonalise, store_basis)
   space = krylov_space(operators, None if state is None else torch.as_tensor(state).reshape(1, -1), num_steps, 1, seed, weights,
-                       qubits, reorthogonalise)
+                       qubits, reorthogonalise, store_basis)
   theta, _ = space.ritz()[0]
   if len(theta) == 0:
     raise ValueError("the start state has norm 0")

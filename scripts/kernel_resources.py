@@ -1,4 +1,4 @@
-"""Register / LDS / occupancy table of the pass, observable, Gibbs-With-Gradients, parity-table, shot-parity, Krylov, Gram, Gram-VJP and reduced-density kernels as hipcc reports them, and WHERE their spills sit
+"""Register / LDS / occupancy table of the pass, observable, Gibbs-With-Gradients, parity-table, shot-parity, Krylov (with the streamed replay), Gram, Gram-VJP and reduced-density kernels as hipcc reports them, and WHERE their spills sit
 (developer tool and CPU test, no GPU needed):
     python scripts/kernel_resources.py            # the table, then every spill site with its loop context
 `check()` is what tests/test_scripts_cpu.py runs: a kernel the DEFAULT planner can select must not spill a VGPR at all and
