@@ -121,7 +121,7 @@ struct qhbm_engine {
   int opt_adj_stop_early = -1; // frozen parameters: the backward sweep stops at the first live gate (-1: if the time model says that is cheaper)
   int opt_adj_plan_search = 1; // adjoint: build the scheduler's best few pass orders and keep the one with the fewest model flops
   int opt_wide_last = -1;      // forward: the last gate pass may take a tile one or two bits wider (-1: unless tile_qubits is set)
-  int opt_fwd_move_low = 1;    // forward: a pass may move four of its bits onto the 128-byte line positions (schedule.h build_plan move_low_bits)
+  int opt_fwd_move_low = 1;    // forward: a pass may move four of its bits onto the 128-byte line positions (schedule.h PlanOptions::move_low_bits)
   int opt_fwd_pair = 1;        // dense lean forward passes run on pairs of states, tiles in registers (pass_fwd2_kernel)
   int opt_shift_prefix = 1;    // parameter shift: a shifted program starts at the pass that holds its gate, from the base program's state
   int opt_adj_relabel = 1;     // adjoint plans move finished index bits out of the 128-byte lines (schedule.h Pass)
@@ -534,9 +534,15 @@ int build_plans(qhbm_engine* h) {
   std::string err;
   if (!h->plans_valid) {  // (a change of the gradient mask alone keeps the forward plan: it does not depend on it)
     h->adj_cache.clear();
-    if (!build_plan(h->model, h->opt_tile, h->opt_round, false, &h->fwd.plan, &err, h->opt_full_fwd, h->opt_meas_tile,
-                    h->opt_cph_wave_bits != 0, false, h->opt_wide_last, nullptr, h->opt_fwd_move_low))
-      return fail(h, "forward plan: " + err);
+    PlanOptions fo;
+    fo.tile_bits = h->opt_tile;
+    fo.round_bits = h->opt_round;
+    fo.full_threshold = h->opt_full_fwd;
+    fo.meas_tile_bits = h->opt_meas_tile;
+    fo.cph_wave_bits = h->opt_cph_wave_bits != 0;
+    fo.wide_last_pass = h->opt_wide_last;
+    fo.move_low_bits = h->opt_fwd_move_low;
+    if (!build_plan(h->model, fo, &h->fwd.plan, &err)) return fail(h, "forward plan: " + err);
     if (!forward_layouts_chain(h->fwd.plan)) return fail(h, "internal: the forward passes' layouts do not chain to the identity");
     h->fwd.uploaded = false;
     ++h->fwd_plans_built;
@@ -550,15 +556,21 @@ int build_plans(qhbm_engine* h) {
   //    prune early (config 3: + 8 %).
   const bool relabel = h->opt_adj_relabel != 0 && h->opt_adj_exchange != 0;
   auto plan_adjoint_of = [&](const Model& model, int tile, Plan* out, double* seconds, std::string* e) {
-    if (!build_plan(model, tile, 0, true, out, e, h->opt_full_adj, 0, h->opt_cph_wave_bits != 0, relabel)) return false;
+    PlanOptions ao;
+    ao.tile_bits = tile;
+    ao.adjoint = true;
+    ao.full_threshold = h->opt_full_adj;
+    ao.cph_wave_bits = h->opt_cph_wave_bits != 0;
+    ao.relabel = relabel;
+    if (!build_plan(model, ao, out, e)) return false;
     *seconds = adjoint_plan_seconds(*out, model);
     if (!h->opt_adj_plan_search) return true;
     const std::vector<std::vector<uint32_t>> orders = out->candidate_orders;
     for (const std::vector<uint32_t>& order : orders) {
       Plan alt;
       std::string e2;
-      if (!build_plan(model, tile, 0, true, &alt, &e2, h->opt_full_adj, 0, h->opt_cph_wave_bits != 0, relabel, -1, &order))
-        continue;
+      ao.forced_order = &order;
+      if (!build_plan(model, ao, &alt, &e2)) continue;
       const double f = adjoint_plan_seconds(alt, model);
       if (std::getenv("QHBM_PLAN_DEBUG"))
         std::fprintf(stderr, "[plan] tile %d candidate with %zu passes: %.4g ms per state (kept so far: %zu passes, %.4g ms)\n", tile,
@@ -1787,7 +1799,10 @@ int qhbm_set_circuit(qhbm_engine* h, int n_qubits, int n_gates, const qhbm_gate*
   Model no_obs = m;
   no_obs.terms.clear();
   no_obs.n_ops = 0;
-  if (!build_plan(no_obs, h->opt_tile, h->opt_round, false, &probe, &err)) return fail(h, err);
+  PlanOptions po;
+  po.tile_bits = h->opt_tile;
+  po.round_bits = h->opt_round;
+  if (!build_plan(no_obs, po, &probe, &err)) return fail(h, err);
   h->model = std::move(m);
   h->have_circuit = true;
   invalidate_plans(h);

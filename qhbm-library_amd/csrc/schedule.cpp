@@ -363,10 +363,47 @@ struct Instance {
   Entry mat[5], ph1[5], ph2[10], cph[10];
 };
 
+// Developer knobs of the planner (scripts/experiments/plan_constants_probe.sh), read once per build_plan call -- per call,
+// not per process: tests build two plans in one process with the environment changed in between.
+struct PlanKnobs {
+  // QHBM_PLAN_KFIXED, QHBM_PLAN_KMEMORY: the adjoint search's cost per pass, in units of one unpruned gate (config 3: 24.6 ms
+  // of tile I/O against 1.4 ms per gate; the fixed part 3, 5 and 7 measured alike, 10 and 16 worse)
+  double k_fixed = 6.0, k_memory = 17.0;
+  size_t beam = 0;                 // QHBM_PLAN_BEAM: the width of both searches (0: their own, by the number of ops)
+  bool debug = false;              // QHBM_PLAN_DEBUG: the searches report to stderr
+  bool no_wide_last_pass = false;  // QHBM_NO_WIDE_LAST_PASS
+  bool no_wht = false;             // QHBM_NO_WHT: no group is measured through the tile's Walsh-Hadamard transform
+  // QHBM_ADJ_SETS / QHBM_FWD_SETS=hex,hex,... force the local sets of the first passes
+  bool has_adj_sets = false, has_fwd_sets = false;
+  std::vector<uint32_t> adj_sets, fwd_sets;
+
+  PlanKnobs() {
+    if (const char* e = std::getenv("QHBM_PLAN_KFIXED")) k_fixed = std::atof(e);
+    if (const char* e = std::getenv("QHBM_PLAN_KMEMORY")) k_memory = std::atof(e);
+    if (const char* e = std::getenv("QHBM_PLAN_BEAM")) beam = size_t(std::max(1, std::atoi(e)));
+    debug = std::getenv("QHBM_PLAN_DEBUG") != nullptr;
+    no_wide_last_pass = std::getenv("QHBM_NO_WIDE_LAST_PASS") != nullptr;
+    no_wht = std::getenv("QHBM_NO_WHT") != nullptr;
+    has_adj_sets = parse_sets(std::getenv("QHBM_ADJ_SETS"), &adj_sets);
+    has_fwd_sets = parse_sets(std::getenv("QHBM_FWD_SETS"), &fwd_sets);
+  }
+  static bool parse_sets(const char* env, std::vector<uint32_t>* sets) {
+    if (!env) return false;
+    for (const char* q = env; *q;) {
+      char* end = nullptr;
+      const unsigned long v = std::strtoul(q, &end, 16);
+      if (end == q) break;
+      sets->push_back(uint32_t(v));
+      q = *end ? end + 1 : end;
+    }
+    return true;
+  }
+};
+
 class Builder {
  public:
-  Builder(const Model& m, int K, int R, int n_eff, bool adjoint, Plan* plan)
-      : m_(m), K_(K), R_(R), n_eff_(n_eff), adjoint_(adjoint), plan_(plan) {}
+  Builder(const Model& m, int K, int R, int n_eff, bool adjoint, Plan* plan, const PlanKnobs& knobs)
+      : m_(m), K_(K), R_(R), n_eff_(n_eff), adjoint_(adjoint), plan_(plan), no_wht_(knobs.no_wht) {}
 
   // `phys[b]`: physical position of logical index bit b in the layout the pass loads (null: identity).
   Pass begin_pass(uint32_t S, const std::vector<int>* phys = nullptr) {
@@ -789,7 +826,7 @@ class Builder {
       // measuring pass is the wide one, e.g. 38 Z-string shards at 19 qubits)
       const int Kp = p->K;
       const bool wht = g.x == 0 && g.terms.size() >= kWhtMinTerms && R_ == kRoundBits && Kp - R_ >= 6 &&
-                       size_t(m_.n_ops) * 8 + (size_t(4) << (Kp - R_)) <= size_t(8) * kMaxOps && !std::getenv("QHBM_NO_WHT");
+                       size_t(m_.n_ops) * 8 + (size_t(4) << (Kp - R_)) <= size_t(8) * kMaxOps && !no_wht_;
       if (!wht) { which.push_back(gi); continue; }
       std::vector<std::pair<uint32_t, int>> order;  // (class, term)
       for (int ti : g.terms) order.push_back({to_local(*p, m_.terms[ti].z & S) >> (Kp - R_), ti});
@@ -837,9 +874,10 @@ class Builder {
   int K_, R_, n_eff_;
   bool adjoint_;
   Plan* plan_;
+  bool no_wht_;
 };
 
-// Forward plans that move the low index bits (schedule.h build_plan `move_low_bits`): one searched pass.
+// Forward plans that move the low index bits (schedule.h PlanOptions::move_low_bits): one searched pass.
 struct FwdStep {
   uint32_t S = 0;    // local set, logical bits
   int K = 0;         // tile size of the pass (the last pass may be one bit wider)
@@ -887,87 +925,211 @@ void move_low_after(uint32_t S, uint32_t low, int n_eff, std::vector<int>* ph) {
     if (homeless >> b & 1u) { const int pos = __builtin_ctz(owned); (*ph)[size_t(b)] = pos; owned &= owned - 1u; }
 }
 
-bool build_plan_impl(const Model& m, int tile_bits, int round_bits, bool adjoint, Plan* plan, std::string* err,
-                     int full_threshold, int meas_tile_bits, bool cph_wave_bits, bool relabel, int wide_last_pass,
-                     const std::vector<uint32_t>* forced_order, int moving) {
+// Tile geometry and validation: resets `plan` and fills its header.
+bool plan_geometry(const Model& m, const PlanOptions& opt, Plan* plan, std::string* err) {
   *plan = Plan();
-  plan->full_threshold = full_threshold;
-  plan->cph_wave_bits = cph_wave_bits;
-  plan->tail_tiles = cph_wave_bits;  // (one developer switch for the scheduler's round-2 layout choices)
+  plan->full_threshold = opt.full_threshold;
+  plan->cph_wave_bits = opt.cph_wave_bits;
+  plan->tail_tiles = opt.cph_wave_bits;  // (one developer switch for the scheduler's round-2 layout choices)
   if (m.n < 1 || m.n > kMaxQubits - 1) { *err = "n_qubits must be in [1, 31]"; return false; }
   const int n_eff = std::max(m.n, kMinTileBits);
-  const int k_cap = adjoint ? kMaxTileBits - 1 : kMaxTileBits;
+  const int k_cap = opt.adjoint ? kMaxTileBits - 1 : kMaxTileBits;
   int K;
-  if (tile_bits == 0) {
+  if (opt.tile_bits == 0) {
     // Tiles of 2^12 amplitudes (four 256-thread workgroups per CU) are best for the adjoint sweep (the
     // engine tries 2^13 against the model, engine.cpp) and for the forward sweep up to 21 qubits; from 22
     // on the forward's extra passes cost more than the smaller tiles save.  XXZ chain, depth 16, forward ms
     // with 2^12 / 2^13 (round 4): 20 qubits 97.2 / 123.4 per 4096 states, 21: 109.4 / 108.9 per 2048,
     // 22: 7.1 / 6.7 per 64, 23: 16.0 / 15.7, 24 (config 4's lean passes): 2793 / 2639 per 4546 programs.
-    K = n_eff <= k_cap ? n_eff : (adjoint || n_eff <= 21 ? 12 : 13);
+    K = n_eff <= k_cap ? n_eff : (opt.adjoint || n_eff <= 21 ? 12 : 13);
   } else {
-    if (tile_bits < kMinTileBits || tile_bits > k_cap) {
+    if (opt.tile_bits < kMinTileBits || opt.tile_bits > k_cap) {
       *err = "tile_qubits out of range";
       return false;
     }
-    K = std::min(n_eff, tile_bits);
+    K = std::min(n_eff, opt.tile_bits);
   }
-  const int R = kRoundBits;
-  if (round_bits != 0 && round_bits != kRoundBits) {
+  if (opt.round_bits != 0 && opt.round_bits != kRoundBits) {
     *err = "round_qubits must be 4";
     return false;
   }
   plan->n = m.n;
   plan->n_eff = n_eff;
   plan->K = K;
-  plan->R = R;
-  plan->adjoint = adjoint;
+  plan->R = kRoundBits;
+  plan->adjoint = opt.adjoint;
   plan->dense_input = m.dense_input;
+  return true;
+}
 
+// Builds one plan on the geometry of plan_geometry: everything the steps of build_plan_impl share.
+struct Planner {
+  const Model& m;
+  const PlanOptions& opt;
+  const PlanKnobs& knobs;
+  const int moving;  // the forward plan moves its low bits: its passes are searched (PlanOptions::move_low_bits 1 or 2), else 0
+  Plan* const plan;
+  std::string* const err;
+  const bool adjoint;
+  const int n_eff, K, R, c_min;
+  const uint32_t all_bits, home_low;  // every index bit; the bits whose home is a position inside the 128-byte line
+  Builder b;
+  uint32_t always_pending = 0;  // index bits that never finish (the sweep ends at no basis state)
+  uint32_t ever_mat = 0;        // bits some non-diagonal op acts on (the others are idle: exact zeros of psi off the input bit)
   std::vector<LoweredOp> ops;
-  if (!lower(m, &ops, err, &plan->const_phase, &plan->gate_phases)) return false;
-  // Frozen parameters (Model::param_frozen): the backward sweep un-applies the circuit from its end and may stop
-  // at the first gate, in circuit order, whose parameter wants a gradient -- everything before it only moves
-  // (psi, lambda) further back for nobody.  What is left of psi there is not a basis state: every index bit
-  // stays "pending" for good (`always_pending`), so no tile, wave or line is ever pruned.
-  uint32_t always_pending = 0;
-  if (adjoint && !m.param_frozen.empty() && m.stop_at_first_live_gate) {
-    size_t first = 0;
-    while (first < ops.size() && (m.gates[size_t(ops[first].gate)].param_idx < 0 || m.frozen(m.gates[size_t(ops[first].gate)].param_idx))) ++first;
-    bool mixes = false;  // (dropping diagonal gates alone leaves psi a basis state times a phase)
-    for (size_t i = 0; i < first; ++i) mixes |= ops[i].type != LOW_DIAG;
-    if (first > 0) {
-      ops.erase(ops.begin(), ops.begin() + long(first));
-      if (mixes) { always_pending = (1u << std::max(m.n, kMinTileBits)) - 1u; plan->dense_tail = true; }
-    }
-  }
-  // A caller-supplied start state (Model::dense_input) is no basis state either, wherever the sweep stops.
-  if (adjoint && m.dense_input) { always_pending = (1u << std::max(m.n, kMinTileBits)) - 1u; plan->dense_tail = true; }
-  std::vector<int> order(ops.size());
-  for (size_t i = 0; i < ops.size(); ++i) order[i] = adjoint ? int(ops.size() - 1 - i) : int(i);
-
-  const uint32_t all_bits = (1u << n_eff) - 1;
-  const int c_min = std::min(K, 4);
-  Builder b(m, K, R, n_eff, adjoint, plan);
+  std::vector<int> order;          // the ops in the order of the sweep
+  std::vector<MeasGroup> groups;   // forward: terms of equal X-mask share conj(psi[l ^ x]) psi[l]
+  std::vector<int> high_bits;      // the index bits above the line bits, ascending
+  std::vector<uint32_t> blocks;    // tiled plans: the line bits plus every contiguous window of K - c_min bits
+  // emission state
+  std::vector<char> done;
+  std::vector<int> op_pass;  // pass that executes each lowered op
+  size_t n_done = 0;
   // Relabeling adjoint plans (schedule.h Pass): the physical position of every logical index bit, and the
   // bits already finished and moved.  A finished bit is moved by the pass that finishes it, within the
   // positions that pass's tile owns (in place: a workgroup still writes only where it read).
-  plan->relabel = relabel && adjoint && K < n_eff && plan->tail_tiles;
-  uint32_t ever_mat = always_pending;  // bits some non-diagonal op acts on (the others are idle: exact zeros of psi off the input bit)
-  for (const LoweredOp& op : ops) if (op.type != LOW_DIAG) ever_mat |= op.bits;
   std::vector<int> phys;
-  for (int i = 0; i < n_eff; ++i) phys.push_back(i);
   uint32_t frozen = 0;
-  auto pending_mat_of = [&](const std::vector<char>& dn) {
+  std::vector<uint32_t> planned;  // local sets of the first passes, in order (empty: grown greedily)
+  std::vector<FwdStep> steps;     // `moving`: every pass
+
+  Planner(const Model& model, const PlanOptions& options, const PlanKnobs& kn, int moving_, Plan* out, std::string* e)
+      : m(model), opt(options), knobs(kn), moving(moving_), plan(out), err(e), adjoint(options.adjoint), n_eff(out->n_eff), K(out->K),
+        R(out->R), c_min(std::min(out->K, 4)), all_bits((1u << out->n_eff) - 1), home_low((1u << std::min(out->K, 4)) - 1u),
+        b(model, out->K, out->R, out->n_eff, options.adjoint, out, kn) {}
+
+  // ---- small pieces, one definition each ---------------------------------------------------------------------------------
+  // index bits some undone non-diagonal op still acts on
+  uint32_t pending_mat(const std::vector<char>& dn) const {
     uint32_t pend = always_pending;
     for (size_t oi = 0; oi < ops.size(); ++oi) if (!dn[oi] && ops[oi].type != LOW_DIAG) pend |= ops[oi].bits;
     return pend;
-  };
+  }
+  uint32_t finished_bits(const std::vector<char>& dn) const { return all_bits & ~pending_mat(dn); }
+  size_t mats_left(const std::vector<char>& dn) const {
+    size_t left = 0;
+    for (size_t oi = 0; oi < ops.size(); ++oi) left += !dn[oi] && ops[oi].type != LOW_DIAG;
+    return left;
+  }
+  // The bits an op asks a local set S for: a non-diagonal op all of its bits, a diagonal op one of them (none if S has one).
+  static uint32_t need_of(const LoweredOp& op, uint32_t S) {
+    return op.type == LOW_DIAG ? (op.bits & S ? 0u : (op.bits & (0u - op.bits))) : op.bits;
+  }
+  // ... a diagonal op its lowest LIVE bit, if one of its bits is live
+  static uint32_t diag_need_live(const LoweredOp& op, uint32_t S, uint32_t live) {
+    if (op.bits & S) return 0u;
+    return op.bits & live ? (op.bits & live) & (0u - (op.bits & live)) : op.bits & (0u - op.bits);
+  }
+  // `seed` plus what every op left asks for, in order; false as soon as that needs more than `cap` bits
+  bool set_of_all_left(const std::vector<char>& dn, uint32_t seed, int cap, uint32_t* out) const {
+    uint32_t S = seed;
+    for (int oi : order) {
+      if (dn[size_t(oi)]) continue;
+      const uint32_t need = need_of(ops[size_t(oi)], S);
+      if (popc(S | need) > cap) return false;
+      S |= need;
+    }
+    *out = S;
+    return true;
+  }
+  uint32_t fill_high(uint32_t S, int Kp) const {  // the highest free bits, up to Kp bits
+    for (int bit = n_eff - 1; bit >= 0 && popc(S) < Kp; --bit) if (!(S >> bit & 1u)) S |= 1u << bit;
+    return S;
+  }
+  // `low` plus every run of h consecutive entries of `bits` from entry `first` on
+  static void windows(uint32_t low, const std::vector<int>& bits, size_t h, std::vector<uint32_t>* out, size_t first = 0) {
+    for (size_t p0 = first; p0 + h <= bits.size(); ++p0) {
+      uint32_t S = low;
+      for (size_t k = 0; k < h; ++k) S |= 1u << bits[p0 + k];
+      out->push_back(S);
+    }
+  }
+  // Demand-driven local set: `seed` plus the bits of the earliest ready ops, non-diagonal ones only or (`with_diag`) all.
+  // `live` (relabeling plans): a diagonal op asks for its lowest live bit only, or for one bit if none of them is live any more.
+  uint32_t demand_set(const std::vector<char>& dn, uint32_t seed, bool with_diag, const uint32_t* live) const {
+    uint32_t S = seed, blocked = 0;
+    for (int oi : order) {
+      if (dn[size_t(oi)]) continue;
+      const LoweredOp& op = ops[size_t(oi)];
+      if (op.bits & blocked) { blocked |= op.bits; continue; }
+      if (op.type == LOW_DIAG && !with_diag) continue;
+      const uint32_t need = op.type == LOW_DIAG && live ? diag_need_live(op, S, *live) : op.bits;
+      if (popc(S | need) <= K) S |= need; else blocked |= op.bits;
+    }
+    return S;
+  }
+  // The OR-decomposable table of a store that permutes: bit j of the out-index o stands for local index bit pairs[j].first
+  // and lands on physical position pairs[j].second; [2 o] = local index, [2 o + 1] = out offset.
+  static std::vector<uint32_t> store_table(const std::vector<std::pair<int, int>>& pairs) {
+    const uint32_t nb = uint32_t(pairs.size());
+    std::vector<uint32_t> tab(size_t(2) << nb);
+    for (uint32_t o = 0; o < (1u << nb); ++o) {
+      uint32_t l = 0, off = 0;
+      for (uint32_t j = 0; j < nb; ++j)
+        if (o >> j & 1u) { l |= 1u << pairs[j].first; off |= 1u << pairs[j].second; }
+      tab[2 * size_t(o)] = l;
+      tab[2 * size_t(o) + 1] = off;
+    }
+    return tab;
+  }
+  uint32_t low_of(const std::vector<int>& ph) const {  // the logical bits on the line positions
+    uint32_t L = 0;
+    for (int bb = 0; bb < n_eff; ++bb) if (ph[size_t(bb)] < c_min) L |= 1u << bb;
+    return L;
+  }
+  bool is_identity(const std::vector<int>& ph) const {
+    for (int bb = 0; bb < n_eff; ++bb) if (ph[size_t(bb)] != bb) return false;
+    return true;
+  }
+  // (not against an explicit tile size unless asked for: wide_last_pass = 1)
+  bool may_widen() const { return (opt.wide_last_pass > 0 || (opt.wide_last_pass < 0 && opt.tile_bits == 0)) && !knobs.no_wide_last_pass; }
+
+  // ---- lowering ------------------------------------------------------------------------------------------------------------
+  bool lower_circuit() {
+    if (!lower(m, &ops, err, &plan->const_phase, &plan->gate_phases)) return false;
+    // Frozen parameters (Model::param_frozen): the backward sweep un-applies the circuit from its end and may stop
+    // at the first gate, in circuit order, whose parameter wants a gradient -- everything before it only moves
+    // (psi, lambda) further back for nobody.  What is left of psi there is not a basis state: every index bit
+    // stays "pending" for good (`always_pending`), so no tile, wave or line is ever pruned.
+    if (adjoint && !m.param_frozen.empty() && m.stop_at_first_live_gate) {
+      size_t first = 0;
+      while (first < ops.size() && (m.gates[size_t(ops[first].gate)].param_idx < 0 || m.frozen(m.gates[size_t(ops[first].gate)].param_idx))) ++first;
+      bool mixes = false;  // (dropping diagonal gates alone leaves psi a basis state times a phase)
+      for (size_t i = 0; i < first; ++i) mixes |= ops[i].type != LOW_DIAG;
+      if (first > 0) {
+        ops.erase(ops.begin(), ops.begin() + long(first));
+        if (mixes) { always_pending = all_bits; plan->dense_tail = true; }
+      }
+    }
+    // A caller-supplied start state (Model::dense_input) is no basis state either, wherever the sweep stops.
+    if (adjoint && m.dense_input) { always_pending = all_bits; plan->dense_tail = true; }
+    order.resize(ops.size());
+    for (size_t i = 0; i < ops.size(); ++i) order[i] = adjoint ? int(ops.size() - 1 - i) : int(i);
+    plan->relabel = opt.relabel && adjoint && K < n_eff && plan->tail_tiles;
+    ever_mat = always_pending;
+    for (const LoweredOp& op : ops) if (op.type != LOW_DIAG) ever_mat |= op.bits;
+    for (int i = 0; i < n_eff; ++i) phys.push_back(i);
+    for (int bit = c_min; bit < n_eff; ++bit) high_bits.push_back(bit);
+    if (K < n_eff) windows(home_low, high_bits, size_t(K - c_min), &blocks);
+    done.assign(ops.size(), 0);
+    op_pass.assign(ops.size(), 0);
+    if (!adjoint) {
+      for (size_t ti = 0; ti < m.terms.size(); ++ti) {
+        const uint32_t x = m.terms[ti].x;
+        auto it = std::find_if(groups.begin(), groups.end(), [&](const MeasGroup& g) { return g.x == x; });
+        if (it == groups.end()) { groups.push_back(MeasGroup{x, {}}); it = groups.end() - 1; }
+        it->terms.push_back(int(ti));
+      }
+    }
+    return true;
+  }
+
+  // ---- what a pass can be ----------------------------------------------------------------------------------------------
   // The layout after a pass with local set S has run to the state `dn_after`: the bits of S that have no
   // non-diagonal op left (and are not moved yet) go to the highest positions the tile owns, the tile's other
   // bits close up below them in their old order.  Returns the newly moved bits.
-  auto relabel_after = [&](uint32_t S, const std::vector<char>& dn_after, std::vector<int>* ph, uint32_t* frz) {
-    const uint32_t f_new = S & all_bits & ~pending_mat_of(dn_after) & ~*frz & ever_mat;
+  uint32_t relabel_after(uint32_t S, const std::vector<char>& dn_after, std::vector<int>* ph, uint32_t* frz) const {
+    const uint32_t f_new = S & all_bits & ~pending_mat(dn_after) & ~*frz & ever_mat;
     if (!f_new) return 0u;
     std::vector<std::pair<int, int>> tile;  // (physical position, logical bit)
     for (int bb = 0; bb < n_eff; ++bb) if (S >> bb & 1u) tile.push_back({(*ph)[size_t(bb)], bb});
@@ -979,56 +1141,20 @@ bool build_plan_impl(const Model& m, int tile_bits, int round_bits, bool adjoint
     for (const auto& e : tile) if (f_new >> e.second & 1u) (*ph)[size_t(e.second)] = pos[next++];
     *frz |= f_new;
     return f_new;
-  };
-  std::vector<char> done(ops.size(), 0);
-  std::vector<int> op_pass(ops.size(), 0);  // pass that executes each lowered op
-  size_t n_done = 0;
-
-  // Measurement groups: terms of equal X-mask share conj(psi[l ^ x]) psi[l].
-  std::vector<MeasGroup> groups;
-  if (!adjoint) {
-    for (size_t ti = 0; ti < m.terms.size(); ++ti) {
-      const uint32_t x = m.terms[ti].x;
-      auto it = std::find_if(groups.begin(), groups.end(), [&](const MeasGroup& g) { return g.x == x; });
-      if (it == groups.end()) { groups.push_back(MeasGroup{x, {}}); it = groups.end() - 1; }
-      it->terms.push_back(int(ti));
-    }
   }
-  // First pass after which group gi may be measured: every op that does not commute with one of
-  // its terms has run (ops on disjoint bits commute; so does a diagonal op that meets the term
-  // only where the term is Z).  Ops not yet scheduled count as running in pass `pending_pass`.
-  auto group_ready = [&](size_t gi, int pending_pass) {
-    int ready = 0;
-    for (int ti : groups[gi].terms) {
-      const uint32_t supp = m.terms[size_t(ti)].x | m.terms[size_t(ti)].z;
-      for (size_t oi = 0; oi < ops.size(); ++oi) {
-        if (!(ops[oi].bits & supp)) continue;
-        if (ops[oi].type == LOW_DIAG && !(ops[oi].bits & m.terms[size_t(ti)].x)) continue;
-        ready = std::max(ready, done[oi] ? op_pass[oi] : pending_pass);
-      }
-    }
-    return ready;
-  };
-  auto pass_set = [&](const Pass& q) {
-    uint32_t S = 0;
-    for (int bb : q.local_pos) S |= 1u << bb;
-    return S;
-  };
-
   // Candidate local sets of the next pass, given the ops already done (and, in relabeling plans, the
   // physical layout `ph`: the tiles are built from the LIVE bits -- those with a non-diagonal op left --
   // in the order of their physical positions, the four lowest of which are in every tile).
-  auto gen_cands = [&](const std::vector<char>& dn, const std::vector<int>& ph) {
-    // ---- candidate local sets -------------------------------------------------
+  std::vector<uint32_t> candidate_sets(const std::vector<char>& dn, const std::vector<int>& ph) const {
     std::vector<uint32_t> cands;
     if (K >= n_eff) {
       cands.push_back(all_bits);
     } else if (plan->relabel) {
-      const uint32_t pending_mat = pending_mat_of(dn);
+      const uint32_t pending = pending_mat(dn);
       std::vector<int> live, rest;  // by physical position
       {
         std::vector<std::pair<int, int>> a, r;
-        for (int bit = 0; bit < n_eff; ++bit) (pending_mat >> bit & 1u ? a : r).push_back({ph[size_t(bit)], bit});
+        for (int bit = 0; bit < n_eff; ++bit) (pending >> bit & 1u ? a : r).push_back({ph[size_t(bit)], bit});
         std::sort(a.begin(), a.end());
         std::sort(r.begin(), r.end());
         for (const auto& e : a) live.push_back(e.second);
@@ -1041,76 +1167,31 @@ bool build_plan_impl(const Model& m, int tile_bits, int round_bits, bool adjoint
       };
       uint32_t low = 0;
       for (size_t i = 0; i < live.size() && int(i) < c_min; ++i) low |= 1u << live[i];
-      if (int(live.size()) <= K) {
-        cands.push_back(fill(0u));
-      } else {
-        const size_t h = size_t(K - c_min);
-        for (size_t p0 = size_t(c_min); p0 + h <= live.size(); ++p0) {
-          uint32_t S = low;
-          for (size_t k = 0; k < h; ++k) S |= 1u << live[p0 + k];
-          cands.push_back(S);
-        }
-      }
-      // demand-driven: bits of the earliest ready ops (non-diagonal first); a diagonal op asks for its live
-      // bits, or for one bit if none of them is live any more
-      for (int with_diag = 0; with_diag < 2; ++with_diag) {
-        uint32_t S = low, blocked = 0;
-        for (int oi : order) {
-          if (dn[oi]) continue;
-          const LoweredOp& op = ops[oi];
-          if (op.bits & blocked) { blocked |= op.bits; continue; }
-          if (op.type == LOW_DIAG && !with_diag) continue;
-          uint32_t need = op.bits;
-          if (op.type == LOW_DIAG) {
-            if (op.bits & S) continue;
-            need = op.bits & pending_mat ? (op.bits & pending_mat) & (0u - (op.bits & pending_mat)) : op.bits & (0u - op.bits);
-          }
-          if (popc(S | need) <= K) S |= need; else blocked |= op.bits;
-        }
-        cands.push_back(fill(S));
-      }
+      if (int(live.size()) <= K) cands.push_back(fill(0u));
+      else windows(low, live, size_t(K - c_min), &cands, size_t(c_min));
+      for (int with_diag = 0; with_diag < 2; ++with_diag) cands.push_back(fill(demand_set(dn, low, with_diag != 0, &pending)));
     } else {
-      const uint32_t low = (1u << c_min) - 1;
-      const int h = K - c_min;
-      for (int p = c_min; p + h <= n_eff; ++p) cands.push_back(low | (((1u << h) - 1) << p));
+      cands = blocks;
       // Adjoint tail: once no non-diagonal op is left on one of the low c_min bits, psi is zero wherever
       // it differs from the input bitstring, and a tile that still holds it spends twice the work on
       // zeros.  Tiles over the bits that still have gates (8-byte HBM accesses when index bit 0 is
       // gone: kernels.hip prefetch_tile / store_tile with c == 0) touch the same lines for a half, a
       // quarter, ... a sixteenth of the work.
       if (adjoint && plan->tail_tiles) {
-        uint32_t pending_mat = always_pending;
-        for (size_t oi = 0; oi < ops.size(); ++oi) if (!dn[oi] && ops[oi].type != LOW_DIAG) pending_mat |= ops[oi].bits;
-        const uint32_t low_live = low & pending_mat;  // the low bits that still have gates stay in every tile
-        if (low_live != low) {
-          const int h2 = K - popc(low_live);
+        const uint32_t pending = pending_mat(dn);
+        const uint32_t low_live = home_low & pending;  // the low bits that still have gates stay in every tile
+        if (low_live != home_low) {
           std::vector<int> ub;
-          for (int bit = c_min; bit < n_eff; ++bit) if (pending_mat >> bit & 1u) ub.push_back(bit);
-          for (size_t p0 = 0; p0 + size_t(h2) <= ub.size(); ++p0) {
-            uint32_t S = low_live;
-            for (int k = 0; k < h2; ++k) S |= 1u << ub[p0 + size_t(k)];
-            cands.push_back(S);
-          }
+          for (int bit : high_bits) if (pending >> bit & 1u) ub.push_back(bit);
+          windows(low_live, ub, size_t(K - popc(low_live)), &cands);
         }
       }
-      // demand-driven: bits of the earliest ready ops (non-diagonal first)
-      for (int with_diag = 0; with_diag < 2; ++with_diag) {
-        uint32_t S = low, blocked = 0;
-        for (int oi : order) {
-          if (dn[oi]) continue;
-          const LoweredOp& op = ops[oi];
-          if (op.bits & blocked) { blocked |= op.bits; continue; }
-          if (op.type == LOW_DIAG && !with_diag) continue;
-          if (popc(S | op.bits) <= K) S |= op.bits; else blocked |= op.bits;
-        }
-        for (int bit = n_eff - 1; bit >= 0 && popc(S) < K; --bit) if (!(S >> bit & 1)) S |= 1u << bit;
-        cands.push_back(S);
-      }
+      for (int with_diag = 0; with_diag < 2; ++with_diag) cands.push_back(fill_high(demand_set(dn, home_low, with_diag != 0, nullptr), K));
     }
     return cands;
-  };
+  }
   // What a pass with local set S absorbs (adjoint: cut where its gradient slots run out).
-  auto absorb_capped = [&](const std::vector<char>& dn, uint32_t S, int* n_mat) {
+  std::vector<int> absorb_capped(const std::vector<char>& dn, uint32_t S, int* n_mat) const {
     std::vector<int> lst = absorb(ops, order, dn, S, all_bits, n_mat);
     if (adjoint) {  // bound the gradient slots one pass owns (LDS accumulators)
       size_t keep = 0;
@@ -1124,30 +1205,22 @@ bool build_plan_impl(const Model& m, int tile_bits, int round_bits, bool adjoint
       }
     }
     return lst;
-  };
+  }
 
+  // ---- adjoint plans: the order of the passes ------------------------------------------------------------------------------
+  typedef std::vector<std::pair<double, std::vector<uint32_t>>> CompleteOrders;  // (proxy cost, local sets in order)
+  struct AdjNode { std::vector<char> dn; size_t n_done; double cost; std::vector<uint32_t> sets; std::vector<int> phys; uint32_t frozen; };
   // Adjoint plans: the ORDER of the passes is searched, not grown greedily.  A pass costs about
   // (fixed + gates) x (share of its tiles that is not pruned), at least the HBM time of the lines it
   // touches, and tiles are pruned on every finished bit outside the tile (engine.cpp zero_mask, tail tiles): getting the first bits finished early
   // -- by smaller passes that build the staircase the low bits need -- makes every later gate several
   // times cheaper.  Beam search over pass sequences on that model (config 3: the first four, unpruned
-  // passes carry 184 gates instead of 220).
-  std::vector<uint32_t> planned;  // local sets of the passes, in order (empty: greedy)
-  std::vector<std::pair<double, std::vector<uint32_t>>> complete;  // every complete order the search reached
-  if (forced_order) planned = *forced_order;
-  if (adjoint && K < n_eff && plan->tail_tiles && !forced_order) {
-    struct Node { std::vector<char> dn; size_t n_done; double cost; std::vector<uint32_t> sets; std::vector<int> phys; uint32_t frozen; };
-    double kFixed = 6.0, kMemory = 17.0;
-    if (const char* e = std::getenv("QHBM_PLAN_KFIXED")) kFixed = std::atof(e);    // developer knobs (scripts/plan_constants_probe.sh)
-    if (const char* e = std::getenv("QHBM_PLAN_KMEMORY")) kMemory = std::atof(e);  // per pass, in units of one unpruned gate (config 3: 24.6 ms of tile I/O against 1.4 ms per gate; the fixed part 3, 5 and 7 measured alike, 10 and 16 worse)
-    size_t kBeam = ops.size() <= 4000 ? 16 : (ops.size() <= 12000 ? 8 : 4);  // planning time stays well below a second
-    if (const char* e = std::getenv("QHBM_PLAN_BEAM")) kBeam = size_t(std::max(1, std::atoi(e)));
-    auto finished_bits = [&](const std::vector<char>& dn) {
-      uint32_t pend = always_pending;
-      for (size_t oi = 0; oi < ops.size(); ++oi) if (!dn[oi] && ops[oi].type != LOW_DIAG) pend |= ops[oi].bits;
-      return all_bits & ~pend;
-    };
-    std::vector<Node> beam(1);
+  // passes carry 184 gates instead of 220).  Sets `planned` to the best complete order, returns every complete order reached.
+  CompleteOrders search_adjoint_order() {
+    CompleteOrders complete;
+    const double kFixed = knobs.k_fixed, kMemory = knobs.k_memory;
+    const size_t kBeam = knobs.beam ? knobs.beam : (ops.size() <= 4000 ? 16 : (ops.size() <= 12000 ? 8 : 4));  // planning time stays well below a second
+    std::vector<AdjNode> beam(1);
     beam[0].dn = done;
     beam[0].n_done = n_done;
     beam[0].cost = 0.0;
@@ -1155,17 +1228,17 @@ bool build_plan_impl(const Model& m, int tile_bits, int round_bits, bool adjoint
     beam[0].frozen = frozen;
     double best_cost = -1.0;
     for (int depth = 0; depth < 256 && !beam.empty(); ++depth) {
-      std::vector<Node> next;
-      for (const Node& nd : beam) {
+      std::vector<AdjNode> next;
+      for (const AdjNode& nd : beam) {
         const uint32_t fin = finished_bits(nd.dn);
-        std::vector<uint32_t> cs = gen_cands(nd.dn, nd.phys);
+        std::vector<uint32_t> cs = candidate_sets(nd.dn, nd.phys);
         std::sort(cs.begin(), cs.end());
         cs.erase(std::unique(cs.begin(), cs.end()), cs.end());
         for (uint32_t S : cs) {
           int n_mat = 0;
           std::vector<int> lst = absorb_capped(nd.dn, S, &n_mat);
           if (lst.empty()) continue;
-          Node c;
+          AdjNode c;
           c.dn = nd.dn;
           for (int oi : lst) c.dn[size_t(oi)] = 1;
           c.n_done = nd.n_done + lst.size();
@@ -1185,7 +1258,7 @@ bool build_plan_impl(const Model& m, int tile_bits, int round_bits, bool adjoint
             if (best_cost < 0.0 || c.cost < best_cost) {
               best_cost = c.cost;
               planned = c.sets;
-              if (std::getenv("QHBM_PLAN_DEBUG")) {
+              if (knobs.debug) {
                 std::fprintf(stderr, "[plan] complete at depth %d cost %.2f:", depth, c.cost);
                 for (uint32_t st : c.sets) std::fprintf(stderr, " %x", st);
                 std::fprintf(stderr, "\n");
@@ -1194,19 +1267,17 @@ bool build_plan_impl(const Model& m, int tile_bits, int round_bits, bool adjoint
             continue;
           }
           bool dup = false;
-          for (Node& o : next)
+          for (AdjNode& o : next)
             if (o.n_done == c.n_done && o.dn == c.dn) { dup = true; if (c.cost < o.cost) o = c; break; }
           if (!dup) next.push_back(std::move(c));
         }
       }
-      auto rank = [&](const Node& nd) {
-        size_t mats_left = 0;
-        for (size_t oi = 0; oi < ops.size(); ++oi) mats_left += !nd.dn[oi] && ops[oi].type != LOW_DIAG;
+      auto rank = [&](const AdjNode& nd) {
         const int nfin = std::min(4, popc(finished_bits(nd.dn) & ((1u << m.n) - 1u)));
-        return nd.cost + double(mats_left) / double(1 << nfin);
+        return nd.cost + double(mats_left(nd.dn)) / double(1 << nfin);
       };
-      std::sort(next.begin(), next.end(), [&](const Node& x, const Node& y) { return rank(x) < rank(y); });
-      if (std::getenv("QHBM_PLAN_DEBUG"))
+      std::sort(next.begin(), next.end(), [&](const AdjNode& x, const AdjNode& y) { return rank(x) < rank(y); });
+      if (knobs.debug)
         for (size_t i = 0; i < next.size() && i < 20; ++i) {
           std::fprintf(stderr, "[plan] depth %d #%zu cost %.2f rank %.2f done %zu frozen %x:", depth, i, next[i].cost, rank(next[i]), next[i].n_done, next[i].frozen);
           for (uint32_t st : next[i].sets) std::fprintf(stderr, " %x", st);
@@ -1214,26 +1285,24 @@ bool build_plan_impl(const Model& m, int tile_bits, int round_bits, bool adjoint
         }
       if (next.size() > kBeam) next.resize(kBeam);
       if (best_cost >= 0.0) {  // drop what cannot beat the best complete sequence
-        next.erase(std::remove_if(next.begin(), next.end(), [&](const Node& nd) { return nd.cost >= best_cost; }), next.end());
+        next.erase(std::remove_if(next.begin(), next.end(), [&](const AdjNode& nd) { return nd.cost >= best_cost; }), next.end());
       }
       beam.swap(next);
     }
+    return complete;
   }
-  if (!planned.empty() && !forced_order) {
-    // The model knows nothing of how well a pass packs into rounds and instances: a searched order with
-    // clearly MORE passes than the greedy one (deep circuits on many qubits, where no bit finishes
-    // early anyway: config 5, 24 against 21) measured slower, so the greedy order stands there.
+  // The order grown greedily, a pass at a time by the most non-diagonal ops; false if it gets stuck.
+  bool greedy_order(std::vector<uint32_t>* sets) const {
     std::vector<char> dn(done);
     std::vector<int> gphys(phys);
     uint32_t gfrozen = frozen;
-    size_t left = ops.size() - n_done, greedy_passes = 0;
-    std::vector<uint32_t> greedy_sets;
+    size_t left = ops.size() - n_done;
     while (left) {
       int best_mat = -1;
       size_t best_total = 0;
       uint32_t best_set = 0;
       std::vector<int> best;
-      for (uint32_t S : gen_cands(dn, gphys)) {
+      for (uint32_t S : candidate_sets(dn, gphys)) {
         int n_mat = 0;
         std::vector<int> lst = absorb_capped(dn, S, &n_mat);
         if (n_mat > best_mat || (n_mat == best_mat && lst.size() > best_total)) { best_mat = n_mat; best_total = lst.size(); best_set = S; best.swap(lst); }
@@ -1241,120 +1310,115 @@ bool build_plan_impl(const Model& m, int tile_bits, int round_bits, bool adjoint
       if (best.empty()) break;
       for (int oi : best) dn[size_t(oi)] = 1;
       left -= best.size();
-      ++greedy_passes;
-      greedy_sets.push_back(best_set);
+      sets->push_back(best_set);
       if (plan->relabel && left) relabel_after(best_set, dn, &gphys, &gfrozen);
     }
-    // (relabeling plans: a pruned pass moves only its live lines, so more, smaller tail passes are cheap -- the
-    // searched order stands unless the greedy one has FAR fewer passes)
+    return left == 0;
+  }
+  // `planned`: the forced order, or the searched one unless the greedy order is clearly shorter; Plan::candidate_orders.
+  void choose_adjoint_order() {
+    if (opt.forced_order) { planned = *opt.forced_order; return; }
+    if (!(adjoint && K < n_eff && plan->tail_tiles)) return;
+    CompleteOrders complete = search_adjoint_order();
+    if (planned.empty()) return;
+    // The model knows nothing of how well a pass packs into rounds and instances: a searched order with
+    // clearly MORE passes than the greedy one (deep circuits on many qubits, where no bit finishes
+    // early anyway: config 5, 24 against 21) measured slower, so the greedy order stands there.
+    std::vector<uint32_t> greedy_sets;
+    const bool greedy_completes = greedy_order(&greedy_sets);
     // the candidates handed to the caller: the searched orders by proxy cost (the chosen one excluded), the greedy one
     std::sort(complete.begin(), complete.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
     for (const auto& c : complete) {
       if (plan->candidate_orders.size() >= 6) break;
       if (c.second != planned) plan->candidate_orders.push_back(c.second);
     }
-    if (left == 0) plan->candidate_orders.push_back(greedy_sets);
-    if (left == 0 && planned.size() > greedy_passes + (plan->relabel ? 4 : 1)) planned.clear();
+    if (greedy_completes) plan->candidate_orders.push_back(greedy_sets);
+    // (relabeling plans: a pruned pass moves only its live lines, so more, smaller tail passes are cheap -- the
+    // searched order stands unless the greedy one has FAR fewer passes)
+    if (greedy_completes && planned.size() > greedy_sets.size() + (plan->relabel ? 4 : 1)) planned.clear();
   }
-  // Forward plans that move the low index bits.  With logical = physical, every tile is the four low bits plus an
-  // eight-bit window: two light cones of width 4 and 8.  Letting a pass leave any four of its bits on positions 0..3
-  // makes tiles of twelve contiguous logical bits possible -- one light cone of width 12 -- at the same whole-line
-  // accesses.  The first pass loads nothing, so the layout it starts from is free; the last one restores the identity.
-  // Beam search over (local set, next low bits) on fwd_pass_cost.
-  std::vector<FwdStep> steps;
-  if (moving) {
+  // developer knobs: QHBM_ADJ_SETS / QHBM_FWD_SETS replace whatever order was planned
+  void apply_forced_sets() {
+    if (adjoint ? knobs.has_adj_sets : knobs.has_fwd_sets) planned = adjoint ? knobs.adj_sets : knobs.fwd_sets;
+  }
+
+  // ---- forward plans that move the low index bits ----------------------------------------------------------------------
+  struct FwdNode { std::vector<char> dn; size_t n_done; double cost; std::vector<FwdStep> steps; std::vector<int> phys; std::vector<int> phys0; uint32_t touched; };
+  struct FwdCand { uint32_t S; int K; std::vector<int> ph; };  // local set, tile size, layout at load
+  // The passes a node of the search may go on with.  `K_wide`: the tile size the last pass may take.
+  std::vector<FwdCand> forward_candidates(const FwdNode& nd, int depth, int K_wide) const {
+    std::vector<FwdCand> cs;
+    auto add = [&](uint32_t S, int Kp, const std::vector<int>& ph) {
+      if (popc(S) != Kp) return;
+      for (const FwdCand& c : cs) if (c.S == S && c.ph == ph) return;
+      cs.push_back(FwdCand{S, Kp, ph});
+    };
+    if (depth == 0) {
+      // the start layout is free: any four consecutive bits of a contiguous window on positions 0..3
+      for (int p0 = 0; p0 + K <= n_eff; ++p0)
+        for (int l0 = p0; l0 + c_min <= p0 + K; ++l0) {
+          const uint32_t S = ((1u << K) - 1u) << p0, L0 = home_low << l0;
+          std::vector<int> ph = nd.phys;
+          move_low_after(L0 | home_low, L0, n_eff, &ph);
+          add(S, K, ph);
+        }
+      for (uint32_t S : candidate_sets(nd.dn, nd.phys)) add(S, K, nd.phys);
+      return cs;
+    }
+    const uint32_t Lc = low_of(nd.phys);
+    std::vector<int> others;
+    for (int bb = 0; bb < n_eff; ++bb) if (!(Lc >> bb & 1u)) others.push_back(bb);
+    std::vector<uint32_t> sets;
+    windows(Lc, others, size_t(K - c_min), &sets);
+    for (int with_diag = 0; with_diag < 2; ++with_diag) sets.push_back(fill_high(demand_set(nd.dn, Lc, with_diag != 0, nullptr), K));
+    for (uint32_t S : sets) add(S, K, nd.phys);
+    // the pass that takes all that is left and restores the layout: the low bits, every bit that is not at
+    // home, the home bits 0..3 and the bits of the ops left
+    uint32_t S = Lc | home_low;
+    for (int bb = 0; bb < n_eff; ++bb) if (nd.phys[size_t(bb)] != bb) S |= 1u << bb;
+    if (set_of_all_left(nd.dn, S, K_wide, &S)) {
+      const int Kp = popc(S) <= K ? K : K_wide;
+      add(fill_high(S, Kp), Kp, nd.phys);
+    }
+    return cs;
+  }
+  // The low bits after a pass: as they are (first), home, or four consecutive bits of the set.
+  std::vector<uint32_t> low_choices(const FwdCand& cd) const {
+    std::vector<uint32_t> lows;
+    lows.push_back(low_of(cd.ph));
+    if ((home_low & ~cd.S) == 0) lows.push_back(home_low);
+    std::vector<int> sb;
+    for (int bb = 0; bb < n_eff; ++bb) if (cd.S >> bb & 1u) sb.push_back(bb);
+    windows(0u, sb, size_t(c_min), &lows);
+    std::sort(lows.begin() + 1, lows.end());
+    lows.erase(std::unique(lows.begin() + 1, lows.end()), lows.end());
+    return lows;
+  }
+  // With logical = physical, every tile is the four low bits plus an eight-bit window: two light cones of width 4 and 8.
+  // Letting a pass leave any four of its bits on positions 0..3 makes tiles of twelve contiguous logical bits possible -- one
+  // light cone of width 12 -- at the same whole-line accesses.  The first pass loads nothing, so the layout it starts from is
+  // free; the last one restores the identity.  Beam search over (local set, next low bits) on fwd_pass_cost: fills `steps`
+  // and sets `phys` to the start layout.
+  bool search_forward_steps() {
     // (the wide last pass under the conditions of the plain plans; 13: the paired forward kernel's largest tile)
-    const bool widen_ok = (wide_last_pass > 0 || (wide_last_pass < 0 && tile_bits == 0)) && !std::getenv("QHBM_NO_WIDE_LAST_PASS");
-    const int K_wide = widen_ok && K + 1 <= std::min(n_eff, 13) ? K + 1 : K;
-    struct Node { std::vector<char> dn; size_t n_done; double cost; std::vector<FwdStep> steps; std::vector<int> phys; std::vector<int> phys0; uint32_t touched; };
-    auto low_of = [&](const std::vector<int>& ph) {
-      uint32_t L = 0;
-      for (int bb = 0; bb < n_eff; ++bb) if (ph[size_t(bb)] < c_min) L |= 1u << bb;
-      return L;
-    };
-    auto is_identity = [&](const std::vector<int>& ph) {
-      for (int bb = 0; bb < n_eff; ++bb) if (ph[size_t(bb)] != bb) return false;
-      return true;
-    };
-    auto mats_left = [&](const std::vector<char>& dn) {
-      size_t left = 0;
-      for (size_t oi = 0; oi < ops.size(); ++oi) left += !dn[oi] && ops[oi].type != LOW_DIAG;
-      return left;
-    };
-    size_t kBeam = ops.size() <= 4000 ? 96 : (ops.size() <= 12000 ? 24 : 8);
-    if (const char* e = std::getenv("QHBM_PLAN_BEAM")) kBeam = size_t(std::max(1, std::atoi(e)));
-    const uint32_t home_low = (1u << c_min) - 1u;
-    std::vector<Node> beam(1);
+    const int K_wide = may_widen() && K + 1 <= std::min(n_eff, 13) ? K + 1 : K;
+    const size_t kBeam = knobs.beam ? knobs.beam : (ops.size() <= 4000 ? 96 : (ops.size() <= 12000 ? 24 : 8));
+    std::vector<FwdNode> beam(1);
     beam[0].dn = done;
     beam[0].n_done = 0;
     beam[0].cost = 0.0;
     beam[0].phys = phys;
     beam[0].touched = 0;
     double best_cost = -1.0;
-    size_t most_in_a_pass = 1;
+    size_t most_in_a_pass = 1;  // (search state, not node state: across the nodes of a depth, and before the cut)
     for (int depth = 0; depth < 64 && !beam.empty(); ++depth) {
-      std::vector<Node> next;
-      for (const Node& nd : beam) {
-        // ---- candidate (local set, tile size, layout at load) ----
-        struct Cand { uint32_t S; int K; std::vector<int> ph; };
-        std::vector<Cand> cs;
-        auto add = [&](uint32_t S, int Kp, const std::vector<int>& ph) {
-          if (popc(S) != Kp) return;
-          for (const Cand& c : cs) if (c.S == S && c.ph == ph) return;
-          cs.push_back(Cand{S, Kp, ph});
-        };
-        if (depth == 0) {
-          // the start layout is free: any four consecutive bits of a contiguous window on positions 0..3
-          for (int p0 = 0; p0 + K <= n_eff; ++p0)
-            for (int l0 = p0; l0 + c_min <= p0 + K; ++l0) {
-              const uint32_t S = ((1u << K) - 1u) << p0, L0 = home_low << l0;
-              std::vector<int> ph = nd.phys;
-              move_low_after(L0 | home_low, L0, n_eff, &ph);
-              add(S, K, ph);
-            }
-          for (uint32_t S : gen_cands(nd.dn, nd.phys)) add(S, K, nd.phys);
-        } else {
-          const uint32_t Lc = low_of(nd.phys);
-          std::vector<int> others;
-          for (int bb = 0; bb < n_eff; ++bb) if (!(Lc >> bb & 1u)) others.push_back(bb);
-          const size_t hh = size_t(K - c_min);
-          for (size_t p0 = 0; p0 + hh <= others.size(); ++p0) {
-            uint32_t S = Lc;
-            for (size_t k = 0; k < hh; ++k) S |= 1u << others[p0 + k];
-            add(S, K, nd.phys);
-          }
-          for (int with_diag = 0; with_diag < 2; ++with_diag) {  // demand-driven, as gen_cands
-            uint32_t S = Lc, blocked = 0;
-            for (int oi : order) {
-              if (nd.dn[size_t(oi)]) continue;
-              const LoweredOp& op = ops[size_t(oi)];
-              if (op.bits & blocked) { blocked |= op.bits; continue; }
-              if (op.type == LOW_DIAG && !with_diag) continue;
-              if (popc(S | op.bits) <= K) S |= op.bits; else blocked |= op.bits;
-            }
-            for (int bit = n_eff - 1; bit >= 0 && popc(S) < K; --bit) if (!(S >> bit & 1u)) S |= 1u << bit;
-            add(S, K, nd.phys);
-          }
-          // the pass that takes all that is left and restores the layout: the low bits, every bit that is not at
-          // home, the home bits 0..3 and the bits of the ops left
-          uint32_t S = Lc | home_low;
-          for (int bb = 0; bb < n_eff; ++bb) if (nd.phys[size_t(bb)] != bb) S |= 1u << bb;
-          for (int oi : order) {
-            if (nd.dn[size_t(oi)]) continue;
-            const LoweredOp& op = ops[size_t(oi)];
-            S |= op.type == LOW_DIAG ? (op.bits & S ? 0u : (op.bits & (0u - op.bits))) : op.bits;
-          }
-          if (popc(S) <= K_wide) {
-            const int Kp = popc(S) <= K ? K : K_wide;
-            for (int bit = n_eff - 1; bit >= 0 && popc(S) < Kp; --bit) if (!(S >> bit & 1u)) S |= 1u << bit;
-            add(S, Kp, nd.phys);
-          }
-        }
-        for (const Cand& cd : cs) {
+      std::vector<FwdNode> next;
+      for (const FwdNode& nd : beam) {
+        for (const FwdCand& cd : forward_candidates(nd, depth, K_wide)) {
           int n_mat = 0;
           std::vector<int> lst = absorb(ops, order, nd.dn, cd.S, all_bits, &n_mat);
           if (lst.empty()) continue;
-          Node c;
+          FwdNode c;
           c.dn = nd.dn;
           for (int oi : lst) c.dn[size_t(oi)] = 1;
           c.n_done = nd.n_done + lst.size();
@@ -1380,29 +1444,15 @@ bool build_plan_impl(const Model& m, int tile_bits, int round_bits, bool adjoint
             continue;
           }
           if (cd.K != K) continue;  // (the wide tile is for the last pass only)
-          // ---- the low bits after this pass: as they are, home, or four consecutive bits of the set ----
-          std::vector<uint32_t> lows;
-          lows.push_back(low_of(cd.ph));
-          if ((home_low & ~cd.S) == 0) lows.push_back(home_low);
-          {
-            std::vector<int> sb;
-            for (int bb = 0; bb < n_eff; ++bb) if (cd.S >> bb & 1u) sb.push_back(bb);
-            for (size_t p0 = 0; p0 + size_t(c_min) <= sb.size(); ++p0) {
-              uint32_t L = 0;
-              for (int k = 0; k < c_min; ++k) L |= 1u << sb[p0 + size_t(k)];
-              lows.push_back(L);
-            }
-          }
-          std::sort(lows.begin() + 1, lows.end());
-          lows.erase(std::unique(lows.begin() + 1, lows.end()), lows.end());
+          const std::vector<uint32_t> lows = low_choices(cd);
           for (size_t li = 0; li < lows.size(); ++li) {
             if (li > 0 && lows[li] == lows[0]) continue;
-            Node c2 = c;
+            FwdNode c2 = c;
             c2.phys = cd.ph;
             if (li > 0) move_low_after(cd.S, lows[li], n_eff, &c2.phys);  // (li == 0: the pass stores in place)
             c2.steps.push_back(FwdStep{cd.S, cd.K, lows[li]});
             bool dup = false;
-            for (Node& o : next)
+            for (FwdNode& o : next)
               if (o.n_done == c2.n_done && o.phys == c2.phys && o.dn == c2.dn) { dup = true; if (c2.cost < o.cost) o = c2; break; }
             if (!dup) next.push_back(std::move(c2));
           }
@@ -1410,7 +1460,7 @@ bool build_plan_impl(const Model& m, int tile_bits, int round_bits, bool adjoint
       }
       // (what is left costs at least its X ops and the fixed part of the passes that must hold them: no pass has absorbed
       // more non-diagonal ops than `most_in_a_pass` so far)
-      auto rank = [&](const Node& nd) {
+      auto rank = [&](const FwdNode& nd) {
         const size_t left = mats_left(nd.dn);
         return nd.cost + kFwdPerX * double(left) + (kFwdFixed + fwd_per_pass()) * double((left + most_in_a_pass - 1) / most_in_a_pass);
       };
@@ -1418,17 +1468,17 @@ bool build_plan_impl(const Model& m, int tile_bits, int round_bits, bool adjoint
       for (size_t i = 0; i < next.size(); ++i) keyed.push_back({rank(next[i]), i});
       std::stable_sort(keyed.begin(), keyed.end());
       // (at most nine layouts per set of done ops: the beam must not fill up with one prefix under many layouts)
-      std::vector<Node> kept;
+      std::vector<FwdNode> kept;
       for (const auto& kv : keyed) {
         if (kept.size() >= kBeam) break;
-        const Node& nd = next[kv.second];
+        const FwdNode& nd = next[kv.second];
         if (best_cost >= 0.0 && nd.cost >= best_cost) continue;
         size_t same = 0;
-        for (const Node& o : kept) same += o.n_done == nd.n_done && o.dn == nd.dn;
+        for (const FwdNode& o : kept) same += o.n_done == nd.n_done && o.dn == nd.dn;
         if (same >= 9) continue;
         kept.push_back(nd);
       }
-      if (std::getenv("QHBM_PLAN_DEBUG"))
+      if (knobs.debug)
         for (size_t i = 0; i < kept.size() && i < 8; ++i) {
           std::fprintf(stderr, "[fwd plan] depth %d #%zu cost %.3f done %zu:", depth, i, kept[i].cost, kept[i].n_done);
           for (const FwdStep& st : kept[i].steps) std::fprintf(stderr, " %x/%x", st.S, st.low);
@@ -1437,105 +1487,78 @@ bool build_plan_impl(const Model& m, int tile_bits, int round_bits, bool adjoint
       beam.swap(kept);
     }
     if (steps.empty()) { *err = "no forward plan that moves the low bits"; return false; }
-    if (std::getenv("QHBM_PLAN_DEBUG")) {
+    if (knobs.debug) {
       std::fprintf(stderr, "[fwd plan] chosen, cost %.3f:", best_cost);
       for (const FwdStep& st : steps) std::fprintf(stderr, " %x/%x(K=%d)", st.S, st.low, st.K);
       std::fprintf(stderr, "\n");
     }
-  }
-  size_t planned_i = 0;
-  {  // developer knobs: QHBM_ADJ_SETS / QHBM_FWD_SETS=hex,hex,... force the local sets of the first passes
-    if (const char* env = std::getenv(adjoint ? "QHBM_ADJ_SETS" : "QHBM_FWD_SETS")) {
-      planned.clear();
-      for (const char* q = env; *q;) {
-        char* end = nullptr;
-        const unsigned long v = std::strtoul(q, &end, 16);
-        if (end == q) break;
-        planned.push_back(uint32_t(v));
-        q = *end ? end + 1 : end;
-      }
-    }
+    return true;
   }
 
-  while (n_done < ops.size()) {
-    const FwdStep* step = nullptr;  // the searched pass of a plan that moves the low bits
-    if (moving) {
-      if (plan->passes.size() >= steps.size()) { *err = "internal: the searched forward plan leaves ops undone"; return false; }
-      step = &steps[plan->passes.size()];
-    }
-    std::vector<uint32_t> cands = step ? std::vector<uint32_t>{step->S}
-                                       : (planned_i < planned.size() ? std::vector<uint32_t>{planned[planned_i++]} : gen_cands(done, phys));
-    // A WIDER last pass: when everything that is left needs one or two index bits more than a tile has, the
-    // last gate pass takes a tile of 2^(K+1) or 2^(K+2) amplitudes instead of leaving a pass of its own to a
-    // handful of gates (config 3: 33 gates on 13 bits were 32 + 1 in two passes, the second a full read and
-    // write of the state for ONE gate: 14 of the forward sweep's 110 ms).
-    int wide_K = 0;
-    uint32_t wide_S = 0;
-    // (not for the first pass, and not against an explicit tile size unless asked for: wide_last_pass = 1)
-    const bool widen = wide_last_pass > 0 || (wide_last_pass < 0 && tile_bits == 0);
-    if (!step && !adjoint && K < n_eff && plan->tail_tiles && widen && !plan->passes.empty() && !std::getenv("QHBM_NO_WIDE_LAST_PASS")) {
-      uint32_t S = (1u << c_min) - 1;
-      for (int oi : order) {
-        if (done[oi]) continue;
-        const LoweredOp& op = ops[oi];
-        S |= op.type == LOW_DIAG ? (op.bits & S ? 0u : (op.bits & (0u - op.bits))) : op.bits;
-      }
-      const int need = popc(S);
-      if (need > K && need <= std::min(K + 2, std::min(n_eff, 13))) {  // (13: the paired forward kernel's largest tile)
-        wide_K = need;
-        wide_S = S;
+  // ---- the gate passes -----------------------------------------------------------------------------------------------------
+  // First pass after which group gi may be measured: every op that does not commute with one of
+  // its terms has run (ops on disjoint bits commute; so does a diagonal op that meets the term
+  // only where the term is Z).  Ops not yet scheduled count as running in pass `pending_pass`.
+  int group_ready(size_t gi, int pending_pass) const {
+    int ready = 0;
+    for (int ti : groups[gi].terms) {
+      const uint32_t supp = m.terms[size_t(ti)].x | m.terms[size_t(ti)].z;
+      for (size_t oi = 0; oi < ops.size(); ++oi) {
+        if (!(ops[oi].bits & supp)) continue;
+        if (ops[oi].type == LOW_DIAG && !(ops[oi].bits & m.terms[size_t(ti)].x)) continue;
+        ready = std::max(ready, done[oi] ? op_pass[oi] : pending_pass);
       }
     }
-    if (!step && !adjoint && K < n_eff && !groups.empty()) {
-      // If one tile can hold every remaining op, this is the last gate pass: spend its spare local
-      // bits on the X-masks of the groups no earlier pass can measure, so that the measurement
-      // needs no pass (a full read of the state) of its own -- only if ALL of them fit (a
-      // scattered local set that still leaves a measurement pass costs more than it saves).
-      // Listed first: ties go to it.
-      uint32_t S = (1u << c_min) - 1;
-      bool fits = true;
-      for (int oi : order) {
-        if (done[oi]) continue;
-        const LoweredOp& op = ops[oi];
-        const uint32_t need = op.type == LOW_DIAG ? (op.bits & S ? 0u : (op.bits & (0u - op.bits))) : op.bits;
-        if (popc(S | need) > K) { fits = false; break; }
-        S |= need;
-      }
-      if (fits) {
-        const int here = int(plan->passes.size());
-        for (size_t gi = 0; gi < groups.size() && fits; ++gi) {
-          const int ready = group_ready(gi, here);
-          bool earlier = false;
-          for (int pi = ready; pi < here && !earlier; ++pi) earlier = (groups[gi].x & ~pass_set(plan->passes[size_t(pi)])) == 0;
-          if (earlier) continue;
-          if (popc(S | groups[gi].x) <= K) S |= groups[gi].x; else fits = false;  // all or nothing
-        }
-      }
-      if (fits) {
-        for (int bit = n_eff - 1; bit >= 0 && popc(S) < K; --bit) if (!(S >> bit & 1)) S |= 1u << bit;
-        cands.insert(cands.begin(), S);
-      }
+    return ready;
+  }
+  // A WIDER last pass: when everything that is left needs one or two index bits more than a tile has, the
+  // last gate pass takes a tile of 2^(K+1) or 2^(K+2) amplitudes instead of leaving a pass of its own to a
+  // handful of gates (config 3: 33 gates on 13 bits were 32 + 1 in two passes, the second a full read and
+  // write of the state for ONE gate: 14 of the forward sweep's 110 ms).  Returns the tile size, 0 for none.
+  int wide_last_pass_set(uint32_t* wide_S) const {
+    // (not for the first pass)
+    if (adjoint || K >= n_eff || !plan->tail_tiles || !may_widen() || plan->passes.empty()) return 0;
+    uint32_t S = 0;
+    set_of_all_left(done, home_low, 32, &S);
+    const int need = popc(S);
+    if (need <= K || need > std::min(K + 2, std::min(n_eff, 13))) return 0;  // (13: the paired forward kernel's largest tile)
+    *wide_S = S;
+    return need;
+  }
+  // If one tile can hold every remaining op, this is the last gate pass: spend its spare local
+  // bits on the X-masks of the groups no earlier pass can measure, so that the measurement
+  // needs no pass (a full read of the state) of its own -- only if ALL of them fit (a
+  // scattered local set that still leaves a measurement pass costs more than it saves).
+  bool measurement_fitting_set(uint32_t* fit_S) const {
+    if (adjoint || K >= n_eff || groups.empty()) return false;
+    uint32_t S = 0;
+    if (!set_of_all_left(done, home_low, K, &S)) return false;
+    const int here = int(plan->passes.size());
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+      const int ready = group_ready(gi, here);
+      bool earlier = false;
+      for (int pi = ready; pi < here && !earlier; ++pi) earlier = (groups[gi].x & ~Builder::local_set_mask(plan->passes[size_t(pi)])) == 0;
+      if (earlier) continue;
+      if (popc(S | groups[gi].x) > K) return false;  // all or nothing
+      S |= groups[gi].x;
     }
-    uint32_t best_S = 0;
+    *fit_S = fill_high(S, K);
+    return true;
+  }
+  // One pass of lookahead: a tile is ranked by the non-diagonal ops it absorbs PLUS the most a
+  // following contiguous-block tile could absorb (a pass is a full read and write of the state).
+  // Forward plans only: measured on the adjoint plan it saves a pass but costs two rounds (+6 %).
+  // Ties go to the set that absorbs more ops, then to the earlier one.
+  void pick_by_lookahead(const std::vector<uint32_t>& cands, uint32_t* best_S, std::vector<int>* best_list) const {
     int best_mat = -1;
     size_t best_total = 0;
-    std::vector<int> best_list;
-    // One pass of lookahead: a tile is ranked by the non-diagonal ops it absorbs PLUS the most a
-    // following contiguous-block tile could absorb (a pass is a full read and write of the state).
-    // Forward plans only: measured on the adjoint plan it saves a pass but costs two rounds (+6 %).
-    std::vector<uint32_t> blocks;
-    if (K < n_eff) {
-      const uint32_t low = (1u << c_min) - 1;
-      const int h = K - c_min;
-      for (int pp = c_min; pp + h <= n_eff; ++pp) blocks.push_back(low | (((1u << h) - 1) << pp));
-    }
     for (uint32_t S : cands) {
       int n_mat = 0;
       std::vector<int> lst = absorb_capped(done, S, &n_mat);
       int next_best = 0;
       if (!adjoint && !blocks.empty() && n_done + lst.size() < ops.size()) {
         std::vector<char> done2(done);
-        for (int oi : lst) done2[oi] = 1;
+        for (int oi : lst) done2[size_t(oi)] = 1;
         for (uint32_t S2 : blocks) {
           int m2 = 0;
           absorb(ops, order, done2, S2, all_bits, &m2);
@@ -1544,111 +1567,124 @@ bool build_plan_impl(const Model& m, int tile_bits, int round_bits, bool adjoint
       }
       const int score = n_mat + next_best;
       if (score > best_mat || (score == best_mat && lst.size() > best_total)) {
-        best_mat = score; best_total = lst.size(); best_S = S; best_list.swap(lst);
+        best_mat = score; best_total = lst.size(); *best_S = S; best_list->swap(lst);
       }
     }
-    if (best_list.empty()) { *err = "scheduler made no progress"; return false; }
-    Builder wide(m, step ? step->K : (wide_K ? wide_K : K), R, n_eff, adjoint, plan);
-    Builder* bp = step && step->K != K ? &wide : &b;
-    if (wide_K) {  // does the wider tile really take everything that is left?
-      int n_mat = 0;
-      std::vector<int> all_left = absorb(ops, order, done, wide_S, all_bits, &n_mat);
-      if (all_left.size() == ops.size() - n_done) {
-        best_S = wide_S;
-        best_list.swap(all_left);
-        bp = &wide;
-      }
+  }
+  // Relabeling adjoint plans: the store of a pass that finishes index bits (`done` already holds the pass).
+  void relabeling_store(Pass* p, uint32_t S) {
+    const uint32_t f_new = relabel_after(S, done, &phys, &frozen);
+    if (!f_new) return;
+    p->flags |= PASS_RELABEL;
+    p->frozen_new_local = Builder::to_local(*p, f_new);
+    std::vector<std::pair<int, int>> live;  // local index bits that stay, in ascending physical (= local) order, and where they go
+    for (int i = 0; i < K; ++i) {
+      p->store_local_phys.push_back(phys[size_t(p->local_pos[size_t(i)])]);
+      if (!(p->frozen_new_local >> i & 1u)) live.push_back({i, p->store_local_phys.back()});
     }
-    Pass p = bp->begin_pass(best_S, &phys);
-    p.frozen_old_local = Builder::to_local(p, frozen & best_S);
+    p->relabel_tab = store_table(live);
+  }
+  // The store that moves the low bits: a relabeling store with no finished bit.  Out-index o counts the positions
+  // the tile owns in ascending order (o bit 0 = address bit 0: consecutive o are adjacent amplitudes, 16-byte stores
+  // of whole lines); the table is OR-decomposable in o as the adjoint's is.
+  bool moving_store(Pass* p, uint32_t S, const FwdStep& step) {
+    if (n_done == ops.size() && plan->passes.size() + 1 != steps.size()) { *err = "internal: the searched forward plan has passes left over"; return false; }
+    const std::vector<int> before(phys);
+    if (step.low != low_of(phys) || n_done == ops.size()) move_low_after(S, step.low, n_eff, &phys);
+    if (phys != before) {
+      const int Kp = p->K;
+      p->flags |= PASS_RELABEL;
+      std::vector<int> by_pos(size_t(n_eff), -1);  // position at the store -> local index bit
+      for (int i = 0; i < Kp; ++i) {
+        p->store_local_phys.push_back(phys[size_t(p->local_pos[size_t(i)])]);
+        by_pos[size_t(p->store_local_phys.back())] = i;
+      }
+      std::vector<std::pair<int, int>> pairs;  // per bit of o: (local index bit, position)
+      for (int q = 0; q < n_eff; ++q) if (by_pos[size_t(q)] >= 0) pairs.push_back({by_pos[size_t(q)], q});
+      if (int(pairs.size()) != Kp || pairs[0].second != 0) { *err = "internal: the moving store is not a permutation of the tile"; return false; }
+      p->relabel_tab = store_table(pairs);
+    }
+    if (n_done == ops.size() && !is_identity(phys)) { *err = "internal: the last forward pass does not restore the layout"; return false; }
+    return true;
+  }
+  // One gate pass with local set S over the ops `list`, built by `bp`.
+  bool emit_pass(Builder* bp, uint32_t S, const std::vector<int>& list, const FwdStep* step) {
+    Pass p = bp->begin_pass(S, &phys);
+    p.frozen_old_local = Builder::to_local(p, frozen & S);
     p.slot_base = int(plan->slot_gate.size());
     {
-      std::vector<char> here(ops.size(), 0);
-      for (int oi : best_list) here[size_t(oi)] = 1;
-      uint32_t pend = always_pending;
-      for (size_t oi = 0; oi < ops.size(); ++oi)
-        if (!done[oi] && !here[oi] && ops[oi].type != LOW_DIAG) pend |= ops[oi].bits;
-      bp->pending_mat_outside_ = pend;
+      std::vector<char> after(done);
+      for (int oi : list) after[size_t(oi)] = 1;
+      bp->pending_mat_outside_ = pending_mat(after);
     }
-    if (!bp->emit_ops(&p, ops, best_list, err)) return false;
+    if (!bp->emit_ops(&p, ops, list, err)) return false;
     {
       // The zero-tile / dead-wave pruning (engine.cpp fill_args, emit_round's dead masks) is sound only
       // if Pass::mat_bits lists EVERY index bit a non-diagonal op of the pass acts on: a new lowered op
       // kind that mixes the two halves of a bit without reporting it would be pruned wrongly.
       uint32_t mixed = 0;
-      for (int oi : best_list) if (ops[size_t(oi)].type != LOW_DIAG) mixed |= ops[size_t(oi)].bits;
+      for (int oi : list) if (ops[size_t(oi)].type != LOW_DIAG) mixed |= ops[size_t(oi)].bits;
       static_assert(LOW_MAT2 == 3, "a new LoweredType must be classified here: diagonal, or reported in mat_bits");
       if (mixed != p.mat_bits) { *err = "internal: a non-diagonal op of the pass is missing from mat_bits"; return false; }
     }
-    for (int oi : best_list) { done[oi] = 1; op_pass[oi] = int(plan->passes.size()); ++n_done; }
-    if (plan->relabel && n_done < ops.size()) {  // (the last pass stores nothing)
-      const std::vector<int> before(phys);
-      const uint32_t f_new = relabel_after(best_S, done, &phys, &frozen);
-      if (f_new) {
-        p.flags |= PASS_RELABEL;
-        p.frozen_new_local = Builder::to_local(p, f_new);
-        std::vector<int> live_bits;  // local index bits that stay, in ascending physical (= local) order
-        for (int i = 0; i < K; ++i) {
-          p.store_local_phys.push_back(phys[size_t(p.local_pos[size_t(i)])]);
-          if (!(p.frozen_new_local >> i & 1u)) live_bits.push_back(i);
-        }
-        const uint32_t n_live = uint32_t(live_bits.size());
-        p.relabel_tab.resize(size_t(2) << n_live);
-        for (uint32_t o = 0; o < (1u << n_live); ++o) {
-          uint32_t l = 0, off = 0;
-          for (uint32_t j = 0; j < n_live; ++j)
-            if (o >> j & 1u) { l |= 1u << live_bits[j]; off |= 1u << p.store_local_phys[size_t(live_bits[j])]; }
-          p.relabel_tab[2 * size_t(o)] = l;
-          p.relabel_tab[2 * size_t(o) + 1] = off;
-        }
-      }
-    }
-    if (step) {
-      // The store that moves the low bits: a relabeling store with no finished bit.  Out-index o counts the positions
-      // the tile owns in ascending order (o bit 0 = address bit 0: consecutive o are adjacent amplitudes, 16-byte stores
-      // of whole lines); the table is OR-decomposable in o as the adjoint's is.
-      if (n_done == ops.size() && plan->passes.size() + 1 != steps.size()) { *err = "internal: the searched forward plan has passes left over"; return false; }
-      uint32_t low_now = 0;
-      for (int bb = 0; bb < n_eff; ++bb) if (phys[size_t(bb)] < c_min) low_now |= 1u << bb;
-      const std::vector<int> before(phys);
-      if (step->low != low_now || n_done == ops.size()) move_low_after(best_S, step->low, n_eff, &phys);
-      if (phys != before) {
-        const int Kp = p.K;
-        p.flags |= PASS_RELABEL;
-        std::vector<int> by_pos(size_t(n_eff), -1);  // position at the store -> local index bit
-        for (int i = 0; i < Kp; ++i) {
-          p.store_local_phys.push_back(phys[size_t(p.local_pos[size_t(i)])]);
-          by_pos[size_t(p.store_local_phys.back())] = i;
-        }
-        std::vector<int> src, pos;  // per bit of o
-        for (int q = 0; q < n_eff; ++q) if (by_pos[size_t(q)] >= 0) { src.push_back(by_pos[size_t(q)]); pos.push_back(q); }
-        if (int(src.size()) != Kp || pos[0] != 0) { *err = "internal: the moving store is not a permutation of the tile"; return false; }
-        p.relabel_tab.resize(size_t(2) << Kp);
-        for (uint32_t o = 0; o < (1u << Kp); ++o) {
-          uint32_t l = 0, off = 0;
-          for (int j = 0; j < Kp; ++j)
-            if (o >> j & 1u) { l |= 1u << src[size_t(j)]; off |= 1u << pos[size_t(j)]; }
-          p.relabel_tab[2 * size_t(o)] = l;
-          p.relabel_tab[2 * size_t(o) + 1] = off;
-        }
-      }
-      if (n_done == ops.size())
-        for (int bb = 0; bb < n_eff; ++bb)
-          if (phys[size_t(bb)] != bb) { *err = "internal: the last forward pass does not restore the layout"; return false; }
-    }
+    for (int oi : list) { done[size_t(oi)] = 1; op_pass[size_t(oi)] = int(plan->passes.size()); ++n_done; }
+    if (plan->relabel && n_done < ops.size()) relabeling_store(&p, S);  // (the last pass stores nothing)
+    if (step && !moving_store(&p, S, *step)) return false;
     plan->passes.push_back(std::move(p));
+    return true;
   }
-
-  {  // the kernels prefetch one record past the last one of a round
+  bool emit_gate_passes() {
+    size_t planned_i = 0;
+    while (n_done < ops.size()) {
+      const FwdStep* step = nullptr;  // the searched pass of a plan that moves the low bits
+      if (moving) {
+        if (plan->passes.size() >= steps.size()) { *err = "internal: the searched forward plan leaves ops undone"; return false; }
+        step = &steps[plan->passes.size()];
+      }
+      std::vector<uint32_t> cands = step ? std::vector<uint32_t>{step->S}
+                                         : (planned_i < planned.size() ? std::vector<uint32_t>{planned[planned_i++]} : candidate_sets(done, phys));
+      uint32_t wide_S = 0, fit_S = 0;
+      const int wide_K = step ? 0 : wide_last_pass_set(&wide_S);
+      if (!step && measurement_fitting_set(&fit_S)) cands.insert(cands.begin(), fit_S);  // listed first: ties go to it
+      uint32_t best_S = 0;
+      std::vector<int> best_list;
+      pick_by_lookahead(cands, &best_S, &best_list);
+      if (best_list.empty()) { *err = "scheduler made no progress"; return false; }
+      Builder wide(m, step ? step->K : (wide_K ? wide_K : K), R, n_eff, adjoint, plan, knobs);
+      Builder* bp = step && step->K != K ? &wide : &b;
+      if (wide_K) {  // does the wider tile really take everything that is left?
+        int n_mat = 0;
+        std::vector<int> all_left = absorb(ops, order, done, wide_S, all_bits, &n_mat);
+        if (all_left.size() == ops.size() - n_done) {
+          best_S = wide_S;
+          best_list.swap(all_left);
+          bp = &wide;
+        }
+      }
+      if (!emit_pass(bp, best_S, best_list, step)) return false;
+    }
+    // the kernels prefetch one record past the last one of a round
     const RecordLayout L(R, adjoint);
     plan->coef_init.resize(plan->coef_init.size() + size_t(L.words()) + 64, 0u);
     plan->n_coef_floats = int(plan->coef_init.size());
+    return true;
   }
-  if (adjoint) {
+
+  // ---- the ends --------------------------------------------------------------------------------------------------------
+  bool finish_adjoint() {
     if (plan->relabel) {  // the relabeling store exists in the exchange-layout kernel only (lean programs)
       bool general = false;
       for (const Pass& p : plan->passes) general |= (p.flags & PASS_GENERAL) != 0;
-      if (general) return build_plan(m, tile_bits, round_bits, adjoint, plan, err, full_threshold, meas_tile_bits, cph_wave_bits, false, wide_last_pass);
+      if (general) {
+        // The rebuild drops the caller's forced order together with the relabeling, as it always has (the positional call
+        // this replaces left the argument out): a forced order that meets a general pass gives the searched plan.  Kept as
+        // found, not fixed (HISTORY round 17).
+        PlanOptions plain = opt;
+        plain.relabel = false;
+        plain.forced_order = nullptr;
+        plain.move_low_bits = 0;
+        return build_plan(m, plain, plan, err);
+      }
     }
     for (Pass& p : plan->passes) {
       p.flags |= PASS_ADJOINT | PASS_STORE;
@@ -1657,111 +1693,125 @@ bool build_plan_impl(const Model& m, int tile_bits, int round_bits, bool adjoint
     if (!plan->passes.empty()) plan->passes.back().flags &= ~PASS_STORE;
     return true;
   }
-
-  // ---- forward: measurement --------------------------------------------------
-  if (plan->passes.empty()) {
-    const uint32_t S = K >= n_eff ? all_bits : ((1u << K) - 1);
-    plan->passes.push_back(b.begin_pass(S));
-  }
-  // (Model::dense_input: the first pass loads the caller's state like any later pass, every tile of it, and no
-  // pass may count on zeros off the input bitstring -- none of the flags and masks below)
-  if (!m.dense_input) plan->passes.front().flags |= PASS_INIT_BASIS;
-  plan->passes.back().completes_circuit = true;
-  // The first pass writes the basis state: ONE tile per state is not zero.  If every index bit is acted on
-  // by some non-diagonal gate, the other tiles need not be written at all: a later pass skips the tiles that
-  // differ from the input on a bit nothing has acted on yet (engine.cpp fill_args: zero_mask), and clears,
-  // when it loads a tile, the amplitudes that differ on such a bit among its LOCAL bits -- the only places
-  // never written before.  (With an idle bit the final state would keep unwritten regions: zeros are filled.)
-  if (!m.dense_input && plan->passes.size() > 1 && ever_mat == all_bits) {
-    plan->passes.front().flags |= PASS_NO_ZERO_FILL;
-    uint32_t touched = plan->passes.front().mat_bits;
-    for (size_t i = 1; i < plan->passes.size(); ++i) {
-      Pass& q = plan->passes[i];
-      q.frozen_old_local = Builder::to_local(q, pass_set(q) & ~touched);
-      touched |= q.mat_bits;
-    }
-  }
-
-  std::vector<char> gdone(groups.size(), 0);
-  size_t g_left = groups.size();
-  // Each X-mask group goes to the earliest pass after its last non-commuting op whose tile holds
-  // its flipped bits -- usually a pass that exists anyway.
-  {
-    std::vector<std::vector<int>> early(plan->passes.size());
-    for (size_t gi = 0; gi < groups.size(); ++gi) {
-      const int ready = group_ready(gi, int(plan->passes.size()) - 1);
-      for (size_t pi = size_t(ready); pi + 1 < plan->passes.size(); ++pi) {  // the last pass is handled below
-        if ((groups[gi].x & ~pass_set(plan->passes[pi])) == 0) {
-          early[pi].push_back(int(gi));
-          gdone[gi] = 1;
-          --g_left;
-          break;
-        }
+  // Forward: the flags of the first pass, and what each later pass must clear at load.
+  void mark_basis_start() {
+    // (Model::dense_input: the first pass loads the caller's state like any later pass, every tile of it, and no
+    // pass may count on zeros off the input bitstring -- none of the flags and masks below)
+    if (!m.dense_input) plan->passes.front().flags |= PASS_INIT_BASIS;
+    // The first pass writes the basis state: ONE tile per state is not zero.  If every index bit is acted on
+    // by some non-diagonal gate, the other tiles need not be written at all: a later pass skips the tiles that
+    // differ from the input on a bit nothing has acted on yet (engine.cpp fill_args: zero_mask), and clears,
+    // when it loads a tile, the amplitudes that differ on such a bit among its LOCAL bits -- the only places
+    // never written before.  (With an idle bit the final state would keep unwritten regions: zeros are filled.)
+    if (!m.dense_input && plan->passes.size() > 1 && ever_mat == all_bits) {
+      plan->passes.front().flags |= PASS_NO_ZERO_FILL;
+      uint32_t touched = plan->passes.front().mat_bits;
+      for (size_t i = 1; i < plan->passes.size(); ++i) {
+        Pass& q = plan->passes[i];
+        q.frozen_old_local = Builder::to_local(q, Builder::local_set_mask(q) & ~touched);
+        touched |= q.mat_bits;
       }
     }
-    for (size_t pi = 0; pi < early.size(); ++pi)
-      if (!early[pi].empty()) b.emit_measure(&plan->passes[pi], groups, early[pi]);
   }
-  auto take = [&](Pass* p) {
-    uint32_t S = 0;
-    for (int bb : p->local_pos) S |= 1u << bb;
-    std::vector<int> which;
-    for (size_t gi = 0; gi < groups.size(); ++gi) {
-      if (!gdone[gi] && (groups[gi].x & ~S) == 0) { which.push_back(int(gi)); gdone[gi] = 1; --g_left; }
+  // Forward: where every X-mask group is measured.
+  void place_measurements() {
+    if (plan->passes.empty()) {
+      const uint32_t S = K >= n_eff ? all_bits : ((1u << K) - 1);
+      plan->passes.push_back(b.begin_pass(S));
     }
-    b.emit_measure(p, groups, which);
-  };
-  take(&plan->passes.back());
-  // Measurement-only passes (a full read of the state each): the largest tile the forward kernel
-  // has (2^14 amplitudes) holds the most X-masks, and the low four index bits stay local so that a
-  // tile is made of >= 128-byte contiguous pieces -- with scattered 16-byte pieces (c = 1) these
-  // passes ran at a quarter of the HBM rate.  Groups too wide for that get a second chance with
-  // only bit 0 pinned; what still does not fit goes to the strided-gather kernel.
-  const int K_meas = std::min(n_eff, std::max(K, meas_tile_bits > 0 ? meas_tile_bits : kMaxTileBits));
-  Builder bm(m, K_meas, R, n_eff, adjoint, plan);
-  for (int c_pin : {c_min, 1}) {
-    const uint32_t pinned = (1u << std::min(c_pin, K_meas)) - 1u;
-    for (;;) {
-      // the x-bits of as many groups as fit (fewest new bits first), then low bits
-      uint32_t S = pinned;
-      bool any = false;
+    mark_basis_start();
+    plan->passes.back().completes_circuit = true;
+    std::vector<char> gdone(groups.size(), 0);
+    size_t g_left = groups.size();
+    // Each X-mask group goes to the earliest pass after its last non-commuting op whose tile holds
+    // its flipped bits -- usually a pass that exists anyway.
+    {
+      std::vector<std::vector<int>> early(plan->passes.size());
+      for (size_t gi = 0; gi < groups.size(); ++gi) {
+        const int ready = group_ready(gi, int(plan->passes.size()) - 1);
+        for (size_t pi = size_t(ready); pi + 1 < plan->passes.size(); ++pi) {  // the last pass is handled below
+          if ((groups[gi].x & ~Builder::local_set_mask(plan->passes[pi])) == 0) {
+            early[pi].push_back(int(gi));
+            gdone[gi] = 1;
+            --g_left;
+            break;
+          }
+        }
+      }
+      for (size_t pi = 0; pi < early.size(); ++pi)
+        if (!early[pi].empty()) b.emit_measure(&plan->passes[pi], groups, early[pi]);
+    }
+    auto take = [&](Pass* p) {
+      const uint32_t S = Builder::local_set_mask(*p);
+      std::vector<int> which;
+      for (size_t gi = 0; gi < groups.size(); ++gi) {
+        if (!gdone[gi] && (groups[gi].x & ~S) == 0) { which.push_back(int(gi)); gdone[gi] = 1; --g_left; }
+      }
+      b.emit_measure(p, groups, which);
+    };
+    take(&plan->passes.back());
+    // Measurement-only passes (a full read of the state each): the largest tile the forward kernel
+    // has (2^14 amplitudes) holds the most X-masks, and the low four index bits stay local so that a
+    // tile is made of >= 128-byte contiguous pieces -- with scattered 16-byte pieces (c = 1) these
+    // passes ran at a quarter of the HBM rate.  Groups too wide for that get a second chance with
+    // only bit 0 pinned; what still does not fit goes to the strided-gather kernel.
+    const int K_meas = std::min(n_eff, std::max(K, opt.meas_tile_bits > 0 ? opt.meas_tile_bits : kMaxTileBits));
+    Builder bm(m, K_meas, R, n_eff, adjoint, plan, knobs);
+    for (int c_pin : {c_min, 1}) {
+      const uint32_t pinned = (1u << std::min(c_pin, K_meas)) - 1u;
       for (;;) {
-        int best_add = 1 << 30;
-        size_t best = groups.size();
-        for (size_t gi = 0; gi < groups.size(); ++gi) {
-          if (gdone[gi] || (groups[gi].x & ~S) == 0) continue;
-          if (popc(S | groups[gi].x) > K_meas) continue;
-          const int add = popc(groups[gi].x & ~S);
-          if (add < best_add) { best_add = add; best = gi; }
+        // the x-bits of as many groups as fit (fewest new bits first), then low bits
+        uint32_t S = pinned;
+        bool any = false;
+        for (;;) {
+          int best_add = 1 << 30;
+          size_t best = groups.size();
+          for (size_t gi = 0; gi < groups.size(); ++gi) {
+            if (gdone[gi] || (groups[gi].x & ~S) == 0) continue;
+            if (popc(S | groups[gi].x) > K_meas) continue;
+            const int add = popc(groups[gi].x & ~S);
+            if (add < best_add) { best_add = add; best = gi; }
+          }
+          if (best == groups.size()) break;
+          S |= groups[best].x;
+          any = true;
         }
-        if (best == groups.size()) break;
-        S |= groups[best].x;
-        any = true;
+        if (!any) {  // nothing left whose bits can be added: either all covered by `pinned`, or too wide
+          bool covered = false;
+          for (size_t gi = 0; gi < groups.size(); ++gi) covered |= !gdone[gi] && (groups[gi].x & ~S) == 0;
+          if (!covered) break;
+        }
+        for (int bit = 0; bit < n_eff && popc(S) < K_meas; ++bit) if (!(S >> bit & 1)) S |= 1u << bit;
+        Pass p = bm.begin_pass(S);
+        p.is_measure_only = true;
+        const size_t before = g_left;
+        take(&p);
+        if (g_left == before) break;
+        plan->passes.push_back(std::move(p));
       }
-      if (!any) {  // nothing left whose bits can be added: either all covered by `pinned`, or too wide
-        bool covered = false;
-        for (size_t gi = 0; gi < groups.size(); ++gi) covered |= !gdone[gi] && (groups[gi].x & ~S) == 0;
-        if (!covered) break;
-      }
-      for (int bit = 0; bit < n_eff && popc(S) < K_meas; ++bit) if (!(S >> bit & 1)) S |= 1u << bit;
-      Pass p = bm.begin_pass(S);
-      p.is_measure_only = true;
-      const size_t before = g_left;
-      take(&p);
-      if (g_left == before) break;
-      plan->passes.push_back(std::move(p));
+      if (!g_left) break;
     }
-    if (!g_left) break;
+    // What is left flips more qubits than a tile holds: those terms are measured by the
+    // strided-gather kernel on the final state in HBM (kernels.hip measure_global_kernel).
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+      if (gdone[gi]) continue;
+      for (int ti : groups[gi].terms) plan->global_terms.push_back(ti);
+    }
+    for (Pass& p : plan->passes) p.prog.push_back(OP_END);
   }
-  // What is left flips more qubits than a tile holds: those terms are measured by the
-  // strided-gather kernel on the final state in HBM (kernels.hip measure_global_kernel).
-  for (size_t gi = 0; gi < groups.size(); ++gi) {
-    if (gdone[gi]) continue;
-    for (int ti : groups[gi].terms) plan->global_terms.push_back(ti);
-    gdone[gi] = 1;
-    --g_left;
-  }
-  for (Pass& p : plan->passes) p.prog.push_back(OP_END);
+};
+
+// One plan: `moving` = 0, or the forward plan whose passes are searched with the freedom to move the low bits.
+bool build_plan_impl(const Model& m, const PlanOptions& opt, const PlanKnobs& knobs, int moving, Plan* plan, std::string* err) {
+  if (!plan_geometry(m, opt, plan, err)) return false;
+  Planner pl(m, opt, knobs, moving, plan, err);
+  if (!pl.lower_circuit()) return false;
+  pl.choose_adjoint_order();
+  if (moving && !pl.search_forward_steps()) return false;
+  pl.apply_forced_sets();
+  if (!pl.emit_gate_passes()) return false;
+  if (opt.adjoint) return pl.finish_adjoint();
+  pl.place_measurements();
   return true;
 }
 
@@ -1784,26 +1834,21 @@ double forward_plan_cost(const Plan& p) {
   return cost;
 }
 
-bool build_plan(const Model& m, int tile_bits, int round_bits, bool adjoint, Plan* plan, std::string* err,
-                int full_threshold, int meas_tile_bits, bool cph_wave_bits, bool relabel, int wide_last_pass,
-                const std::vector<uint32_t>* forced_order, int move_low_bits) {
-  if (!build_plan_impl(m, tile_bits, round_bits, adjoint, plan, err, full_threshold, meas_tile_bits, cph_wave_bits, relabel,
-                       wide_last_pass, forced_order, 0))
-    return false;
+bool build_plan(const Model& m, const PlanOptions& opt, Plan* plan, std::string* err) {
+  const PlanKnobs knobs;
+  if (!build_plan_impl(m, opt, knobs, 0, plan, err)) return false;
   // Forward plans that move the low bits: only where the plan is the scheduler's own choice throughout (no start state
   // of the caller's, no explicit tile size, no forced order), lean (the moving store exists in the lean kernels' epilogue
   // only), tiled, and complete without zero-filling (pruning is what the early, small passes are cheap by).
   // (`move_low_bits` 2, for tests: with an explicit tile size too, and whenever a plan that permutes exists)
-  const bool forced = move_low_bits == 2;
-  if (!move_low_bits || adjoint || m.dense_input || (tile_bits != 0 && !forced) || forced_order || std::getenv("QHBM_FWD_SETS") ||
+  const bool forced = opt.move_low_bits == 2;
+  if (!opt.move_low_bits || opt.adjoint || m.dense_input || (opt.tile_bits != 0 && !forced) || opt.forced_order || knobs.has_fwd_sets ||
       plan->K >= plan->n_eff || !plan->tail_tiles || plan->passes.size() < 2 || !(plan->passes[0].flags & PASS_NO_ZERO_FILL))
     return true;
   for (const Pass& p : plan->passes) if (p.flags & PASS_GENERAL) return true;
   Plan moved;
   std::string e2;
-  if (!build_plan_impl(m, tile_bits, round_bits, adjoint, &moved, &e2, full_threshold, meas_tile_bits, cph_wave_bits, relabel,
-                       wide_last_pass, nullptr, forced ? 2 : 1))
-    return true;
+  if (!build_plan_impl(m, opt, knobs, forced ? 2 : 1, &moved, &e2)) return true;
   bool permutes = false;
   size_t meas_only = 0, meas_only_moved = 0;
   for (const Pass& p : plan->passes) meas_only += p.is_measure_only;
@@ -1815,7 +1860,7 @@ bool build_plan(const Model& m, int tile_bits, int round_bits, bool adjoint, Pla
   // (the model knows the gate passes; a plan that needs more measurement passes or global terms loses on what it leaves out)
   if (!permutes) return true;
   if (!forced && (meas_only_moved > meas_only || moved.global_terms.size() > plan->global_terms.size())) return true;
-  if (std::getenv("QHBM_PLAN_DEBUG"))
+  if (knobs.debug)
     std::fprintf(stderr, "[fwd plan] modelled cost %.3f moving, %.3f without\n", forward_plan_cost(moved), forward_plan_cost(*plan));
   // (by a tenth at least: the model does not resolve less -- three plans of the headline circuit that it priced within 2 %
   // of each other measured 4 % apart, in another order -- and a plan that gains nothing must be the plan of before, bit

@@ -70,7 +70,7 @@ struct Pass {
   // finishes an index bit stores its tiles with that bit moved to the highest position the tile owns, so
   // that in every later pass the live half of the state (finished bit == input bit) is made of WHOLE
   // 128-byte lines instead of every other amplitude of every line.
-  // Forward plans that move the low bits (build_plan `move_low_bits`) use the same fields with no finished bit: a pass
+  // Forward plans that move the low bits (PlanOptions::move_low_bits) use the same fields with no finished bit: a pass
   // stores its tile with four bits of its choice on positions 0..3, and the last gate pass restores the identity.
   std::vector<int> local_pos;
   std::vector<int> nonlocal_pos;
@@ -146,21 +146,31 @@ struct Model {
   bool dense_input = false;
 };
 
-// Tile geometry for a given tile size.
+// What build_plan is asked for; the defaults are the engine's.
+struct PlanOptions {
+  int tile_bits = 0;    // tile size, 2^tile_bits amplitudes (0 selects automatically)
+  int round_bits = 0;   // register bits of a round: 0 or kRoundBits
+  bool adjoint = false; // the backward plan over (psi, lambda) tile pairs, not the forward plan (circuit passes + measurement)
+  int full_threshold = 60;    // Plan::full_threshold
+  int meas_tile_bits = 0;     // tile size of measurement-only passes (0 = the largest the forward kernel has)
+  bool cph_wave_bits = true;  // Plan::cph_wave_bits, and the adjoint tail tiles with it (Plan::tail_tiles)
+  bool relabel = false;       // adjoint: Plan::relabel (dropped, by a rebuild, if the plan turns out not to be lean)
+  // forward: the last gate pass may take a tile one or two bits wider instead of leaving a pass of its own to a handful of
+  // gates: 1 = yes, 0 = no, -1 = unless the tile size is explicit
+  int wide_last_pass = -1;
+  // adjoint: the local sets of the passes, in order (an entry of Plan::candidate_orders), in place of the search
+  const std::vector<uint32_t>* forced_order = nullptr;
+  // forward: a pass may choose which four of its local logical bits sit on physical positions 0..3 after its store
+  // (Pass::store_local_phys with no finished bit), so that a tile can be twelve CONTIGUOUS logical bits; the plan is searched
+  // on the per-pass cost model of forward_plan_cost and kept only if that model prices it a tenth below the plan built
+  // without the freedom and it needs no further measurement pass or global term (1), or whenever such a plan exists, an
+  // explicit tile size included (2: for tests of the moving store at small sizes).  The pass that completes the circuit
+  // restores logical = physical.
+  int move_low_bits = 0;
+};
 
-// Builds the forward plan (circuit passes + measurement) or, with adjoint =
-// true, the backward plan over (psi, lambda) tile pairs.  `tile_bits` = 0
-// selects automatically.  Returns false and fills `err` on failure.
-// `meas_tile_bits`: tile size of measurement-only passes (0 = the largest the forward kernel has).
-// `move_low_bits` (forward plans): a pass may choose which four of its local logical bits sit on physical positions
-// 0..3 after its store (Pass::store_local_phys with no finished bit), so that a tile can be twelve CONTIGUOUS logical
-// bits; the plan is searched on the per-pass cost model of forward_plan_cost and kept only if that model prices it a
-// tenth below the plan built without the freedom and it needs no further measurement pass or global term (1), or
-// whenever such a plan exists, an explicit tile size included (2: for tests of the moving store at small sizes).  The pass that completes the circuit restores logical = physical.
-bool build_plan(const Model& m, int tile_bits, int round_bits, bool adjoint, Plan* out,
-                std::string* err, int full_threshold = 60, int meas_tile_bits = 0, bool cph_wave_bits = true,
-                bool relabel = false, int wide_last_pass = -1, const std::vector<uint32_t>* forced_order = nullptr,
-                int move_low_bits = 0);
+// Builds the plan `opt` describes.  Returns false and fills `err` on failure.
+bool build_plan(const Model& m, const PlanOptions& opt, Plan* out, std::string* err);
 
 std::string describe_plan(const Plan& p);
 

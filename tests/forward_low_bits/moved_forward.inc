@@ -1,5 +1,5 @@
 // moved_forward.inc -- plan_emulate.cpp's forward executor with the store of forward plans that move the low index bits
-// (schedule.h build_plan `move_low_bits`): a pass flagged PASS_RELABEL stores its tile through its relabel table, and the
+// (schedule.h PlanOptions::move_low_bits): a pass flagged PASS_RELABEL stores its tile through its relabel table, and the
 // final state is read at logical = physical addresses.  Included by moved_plan_check.cpp inside namespace emu, after
 // plan_emulate.cpp (whose helpers it uses); everything else is that executor, statement for statement.
 bool emu_forward_moved(Emulation* e, uint32_t basis, bool skip_measure, ForwardResult* out, int* n_moving) {

@@ -87,8 +87,11 @@ void run_case(std::mt19937_64& rng, int n, int layers, bool inverted, int tile) 
   std::snprintf(name, sizeof name, "n=%d layers=%d%s tile=%d", n, layers, inverted ? " inverted" : "", tile);
   Plan plain, moved;
   std::string err;
-  expect(build_plan(m, tile, 0, false, &plain, &err), std::string(name) + ": plain plan: " + err);
-  expect(build_plan(m, tile, 0, false, &moved, &err, 60, 0, true, false, -1, nullptr, 2), std::string(name) + ": moving plan: " + err);
+  PlanOptions o;
+  o.tile_bits = tile;
+  expect(build_plan(m, o, &plain, &err), std::string(name) + ": plain plan: " + err);
+  o.move_low_bits = 2;
+  expect(build_plan(m, o, &moved, &err), std::string(name) + ": moving plan: " + err);
   if (g_failures) return;
   for (const Pass& p : plain.passes) expect(!(p.flags & PASS_RELABEL), std::string(name) + ": the default plan moves");
   int flagged = 0;

@@ -89,14 +89,23 @@ Model make_model(int n, int layers, int idle, int diagonal, std::mt19937_64& rng
   return m;
 }
 
+// forward, or adjoint and relabeling
+PlanOptions options(int tile, bool adjoint) {
+  PlanOptions o;
+  o.tile_bits = tile;
+  o.adjoint = adjoint;
+  o.relabel = adjoint;
+  return o;
+}
+
 void check_structure(const Model& dense, int tile) {
   Model basis = dense;
   basis.dense_input = false;
   std::string err;
   for (int adjoint = 0; adjoint < 2; ++adjoint) {
     Plan pd, pb;
-    expect(build_plan(dense, tile, 0, adjoint != 0, &pd, &err, 60, 0, true, adjoint != 0), "dense plan builds: " + err);
-    expect(build_plan(basis, tile, 0, adjoint != 0, &pb, &err, 60, 0, true, adjoint != 0), "basis plan builds: " + err);
+    expect(build_plan(dense, options(tile, adjoint != 0), &pd, &err), "dense plan builds: " + err);
+    expect(build_plan(basis, options(tile, adjoint != 0), &pb, &err), "basis plan builds: " + err);
     std::vector<PassArgs> ad, ab;
     std::vector<uint32_t> prog, tables;
     fill_args(pd, dense, &ad, &prog, &tables);
@@ -120,7 +129,7 @@ void check_structure(const Model& dense, int tile) {
 void check_gradient(const Model& m, int tile, std::mt19937_64& rng, const char* what) {
   std::string err;
   Plan plan;
-  if (!build_plan(m, tile, 0, true, &plan, &err, 60, 0, true, true)) { expect(false, std::string(what) + ": " + err); return; }
+  if (!build_plan(m, options(tile, true), &plan, &err)) { expect(false, std::string(what) + ": " + err); return; }
   std::uniform_real_distribution<float> P(-1.f, 1.f);
   std::normal_distribution<double> G;
   std::vector<double> params, up;

@@ -37,6 +37,23 @@
 
 using namespace qhbm;
 
+// build_plan's options, spelled in one line (round_bits = kRoundBits throughout)
+static PlanOptions plan_options(int tile, bool adjoint, int full_threshold = 60, int meas_tile = 0, bool wave_bits = true, bool relabel = false,
+                                int wide = -1, const std::vector<uint32_t>* forced = nullptr, int move_low_bits = 0) {
+  PlanOptions o;
+  o.tile_bits = tile;
+  o.round_bits = kRoundBits;
+  o.adjoint = adjoint;
+  o.full_threshold = full_threshold;
+  o.meas_tile_bits = meas_tile;
+  o.cph_wave_bits = wave_bits;
+  o.relabel = relabel;
+  o.wide_last_pass = wide;
+  o.forced_order = forced;
+  o.move_low_bits = move_low_bits;
+  return o;
+}
+
 static int g_failures = 0;
 static double g_oracle_seconds = 0.0, g_forward_seconds = 0.0, g_adjoint_seconds = 0.0;  // where an emulation run spends its time
 static const int kEmulateCases = 360;  // default of --emulate: the floors of kFeatureFloors are set for it
@@ -380,7 +397,7 @@ static int fuzz_one(std::mt19937_64& rng, int n, int index) {
       Plan plan;
       std::string err;
       const int tb = adjoint ? std::min(tile, 13) : tile;  // (adjoint kernels exist for 2^10 .. 2^13)
-      const bool ok = build_plan(c.m, tb, kRoundBits, adjoint != 0, &plan, &err, full_threshold, 0, wave_bits, adjoint && relabel, wide, nullptr);
+      const bool ok = build_plan(c.m, plan_options(tb, adjoint != 0, full_threshold, 0, wave_bits, adjoint && relabel, wide), &plan, &err);
       CHECK(ok, "build_plan: %s", err.c_str());
       if (!ok) continue;
       check_plan(c.m, plan);
@@ -657,13 +674,13 @@ static OptionSet draw_options(std::mt19937_64& rng, int os, int n_eff) {
 
 static bool plan_forward(const Model& m, const OptionSet& o, Plan* plan) {
   std::string err;
-  const bool ok = build_plan(m, o.tile, kRoundBits, false, plan, &err, o.full_threshold, o.meas_tile, o.wave_bits, false, o.wide, nullptr);
+  const bool ok = build_plan(m, plan_options(o.tile, false, o.full_threshold, o.meas_tile, o.wave_bits, false, o.wide), plan, &err);
   CHECK(ok, "build_plan: %s", err.c_str());
   return ok;
 }
 static bool plan_adjoint(const Model& m, const OptionSet& o, Plan* plan, const std::vector<uint32_t>* forced = nullptr) {
   std::string err;
-  const bool ok = build_plan(m, std::min(o.tile, 13), kRoundBits, true, plan, &err, o.full_threshold, 0, o.wave_bits, o.relabel, forced ? -1 : o.wide, forced);
+  const bool ok = build_plan(m, plan_options(std::min(o.tile, 13), true, o.full_threshold, 0, o.wave_bits, o.relabel, forced ? -1 : o.wide, forced), plan, &err);
   if (!forced) CHECK(ok, "build_plan: %s", err.c_str());  // (engine.cpp build_plans skips a candidate order that does not plan)
   return ok;
 }
@@ -904,8 +921,8 @@ static int self_test_emulation() {
   const CaseRun run = make_run(rng, m);
   std::string err;
   Plan fwd, adj, rel;
-  if (!build_plan(m, 10, kRoundBits, false, &fwd, &err) || !build_plan(m, 10, kRoundBits, true, &adj, &err) ||
-      !build_plan(m, 10, kRoundBits, true, &rel, &err, 60, 0, true, true)) {
+  if (!build_plan(m, plan_options(10, false), &fwd, &err) || !build_plan(m, plan_options(10, true), &adj, &err) ||
+      !build_plan(m, plan_options(10, true, 60, 0, true, true), &rel, &err)) {
     std::fprintf(stderr, "self test: %s\n", err.c_str());
     return 1;
   }
@@ -1149,7 +1166,7 @@ static int self_test_emulation() {
     const CaseRun run2 = make_run(rng, m2);
     setenv("QHBM_NO_LEAN_CLIFFORD", "1", 1);
     Plan g;
-    const bool ok = build_plan(m2, 10, kRoundBits, false, &g, &err);
+    const bool ok = build_plan(m2, plan_options(10, false), &g, &err);
     unsetenv("QHBM_NO_LEAN_CLIFFORD");
     bool done = false;
     if (ok && forward_disagreement(m2, g, run2, false, CMP_ALL, nullptr).empty())
@@ -1190,7 +1207,7 @@ static int self_test_emulation() {
     mb.terms.push_back(PauliTerm{1.f, 0x7ffu, 0x3fu << 3, 6, 1});
     const CaseRun rb = make_run(rng, mb);
     Plan pa, pb;
-    if (!build_plan(ma, 10, kRoundBits, false, &pa, &err) || !build_plan(mb, 10, kRoundBits, false, &pb, &err, 60, 10)) { std::printf("self test: %s\n", err.c_str()); return 1; }
+    if (!build_plan(ma, plan_options(10, false), &pa, &err) || !build_plan(mb, plan_options(10, false, 60, 10), &pb, &err)) { std::printf("self test: %s\n", err.c_str()); return 1; }
     const std::string da = forward_disagreement(ma, pa, ra, false, CMP_ALL, nullptr), db = forward_disagreement(mb, pb, rb, false, CMP_ALL, nullptr);
     std::printf("self test: folded lowering constant next to an offset that is no float plus 1/2: %s\n", da.empty() ? "agrees" : da.c_str());
     std::printf("self test: strided-gather terms with five and six Y factors (%zu global terms): %s\n", pb.global_terms.size(), db.empty() ? "agrees" : db.c_str());
@@ -1370,7 +1387,7 @@ static int self_test() {
   c.m.n_ops = 1;
   Plan plan;
   std::string err;
-  if (!build_plan(c.m, 10, kRoundBits, true, &plan, &err)) { std::fprintf(stderr, "self test: %s\n", err.c_str()); return 1; }
+  if (!build_plan(c.m, plan_options(10, true), &plan, &err)) { std::fprintf(stderr, "self test: %s\n", err.c_str()); return 1; }
   g_context = "self test";
   int missed = 0;
   auto expect_failure = [&](const char* what, Plan q) {
@@ -1397,7 +1414,193 @@ static int self_test() {
   return missed;
 }
 
+// ---- --digest-plans: one line per plan, a 64-bit FNV-1a over every field ---------------------------------------------------
+// For refactors of the scheduler that must not change a plan: run `plan_fuzz --digest-plans CASES SEED OUT` before and
+// after, compare the files.  Nothing pins the digests -- the next scheduler feature is meant to change them.  The plans:
+// the generator's cases under their three option sets (forward at move_low_bits 0, 1, 2; adjoint, and every entry of its
+// candidate_orders forced), three hardware-efficient circuits whose plans move their low bits, a 24- and a 28-qubit case,
+// gradient masks that freeze leading gates, a dense start.  A failed build writes its error string.  The case with the
+// most gates is also written to OUT.largest_case.json in the C ABI's form, for timing the planner on it.
+struct Fnv {
+  uint64_t h = 1469598103934665603ull;
+  void bytes(const void* p, size_t n) {
+    const unsigned char* b = static_cast<const unsigned char*>(p);
+    for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; }
+  }
+  template <class T> void pod(T v) { bytes(&v, sizeof v); }
+  template <class T> void vec(const std::vector<T>& v) { pod(uint64_t(v.size())); if (!v.empty()) bytes(v.data(), v.size() * sizeof(T)); }
+};
+static uint64_t plan_digest(const Plan& p) {
+  Fnv f;
+  f.pod(p.n); f.pod(p.n_eff); f.pod(p.K); f.pod(p.R);
+  f.pod(char(p.adjoint)); f.pod(p.n_coef_floats); f.pod(p.full_threshold);
+  f.pod(char(p.tail_tiles)); f.pod(char(p.relabel)); f.pod(char(p.cph_wave_bits)); f.pod(char(p.dense_tail)); f.pod(char(p.dense_input));
+  f.pod(p.const_phase);
+  f.pod(uint64_t(p.gate_phases.size()));
+  for (const auto& gp : p.gate_phases) { f.pod(gp.first); f.pod(gp.second); }
+  f.pod(uint64_t(p.jobs.size()));
+  for (const CoefJob& j : p.jobs) {
+    f.pod(j.op_kind); f.pod(j.mop); f.pod(j.gate); f.pod(j.param_idx); f.pod(j.scalar); f.pod(j.offset); f.pod(j.out_off);
+    f.pod(j.swap); f.pod(j.dagger); f.pod(j.mult); f.pod(j.add_offset); f.pod(j.x_full);
+  }
+  f.vec(p.coef_init); f.vec(p.record_offsets); f.vec(p.global_terms); f.vec(p.slot_gate); f.vec(p.slot_factor);
+  f.pod(uint64_t(p.candidate_orders.size()));
+  for (const auto& o : p.candidate_orders) f.vec(o);
+  f.pod(uint64_t(p.passes.size()));
+  for (const Pass& q : p.passes) {
+    f.pod(q.K); f.pod(q.R); f.pod(q.c); f.pod(q.flags);
+    f.vec(q.local_pos); f.vec(q.nonlocal_pos); f.vec(q.local_phys); f.vec(q.nonlocal_phys); f.vec(q.phys_of); f.vec(q.store_local_phys);
+    f.pod(q.frozen_new_local); f.pod(q.frozen_old_local);
+    f.vec(q.relabel_tab); f.vec(q.prog); f.vec(q.spread); f.vec(q.round_tl);
+    f.pod(char(q.is_measure_only)); f.pod(char(q.completes_circuit));
+    f.pod(q.n_mat_ops); f.pod(q.n_diag_terms); f.pod(q.n_rounds); f.pod(q.n_instances);
+    f.vec(q.round_regmasks); f.vec(q.round_wavemasks); f.vec(q.round_words);
+    f.pod(q.n_meas_groups); f.pod(q.n_meas_terms); f.pod(q.slot_base); f.pod(q.n_slots); f.pod(q.mat_bits);
+  }
+  return f.h;
+}
+
+struct DigestRun {
+  std::FILE* out = nullptr;
+  long plans = 0, failed = 0, fwd_moving = 0, adj_relabel = 0;
+  size_t largest_gates = 0;
+  int largest_case = -1, largest_n = 0;
+};
+// the one place of this mode that calls build_plan
+static bool digest_build(const Model& m, int tile, bool adjoint, int full_threshold, int meas_tile, bool wave_bits, bool relabel, int wide,
+                         const std::vector<uint32_t>* forced, int move_low_bits, Plan* plan, std::string* err) {
+  return build_plan(m, plan_options(tile, adjoint, full_threshold, meas_tile, wave_bits, relabel, wide, forced, move_low_bits), plan, err);
+}
+// builds, writes the line; returns whether a plan came out
+static bool digest_one(DigestRun* r, const std::string& ctx, const Model& m, int tile, bool adjoint, int full_threshold, int meas_tile, bool wave_bits,
+                       bool relabel, int wide, const std::vector<uint32_t>* forced, int move_low_bits, Plan* plan) {
+  std::string err;
+  const bool ok = digest_build(m, tile, adjoint, full_threshold, meas_tile, wave_bits, relabel, wide, forced, move_low_bits, plan, &err);
+  ++r->plans;
+  if (!ok) { ++r->failed; std::fprintf(r->out, "%s : error: %s\n", ctx.c_str(), err.c_str()); return false; }
+  if (adjoint) r->adj_relabel += plan->relabel;
+  else {
+    bool moving = false;
+    for (const Pass& p : plan->passes) moving |= (p.flags & PASS_RELABEL) != 0;
+    r->fwd_moving += moving;
+  }
+  std::fprintf(r->out, "%s : passes=%zu %016llx\n", ctx.c_str(), plan->passes.size(), (unsigned long long)plan_digest(*plan));
+  return true;
+}
+// forward at move_low_bits 0, 1, 2; adjoint, and every entry of its candidate_orders as a forced order
+static void digest_option_set(DigestRun* r, const std::string& ctx, const Model& m, int tile, int full_threshold, int meas_tile, bool wave_bits, bool relabel,
+                              int wide) {
+  Plan plan;
+  for (int mv = 0; mv < 3; ++mv)
+    digest_one(r, ctx + " fwd move=" + std::to_string(mv), m, tile, false, full_threshold, meas_tile, wave_bits, false, wide, nullptr, mv, &plan);
+  const int tb = std::min(tile, 13);  // (adjoint kernels exist for 2^10 .. 2^13)
+  if (!digest_one(r, ctx + " adj", m, tb, true, full_threshold, 0, wave_bits, relabel, wide, nullptr, 0, &plan)) return;
+  const std::vector<std::vector<uint32_t>> orders = plan.candidate_orders;
+  for (size_t k = 0; k < orders.size(); ++k) {
+    Plan alt;
+    digest_one(r, ctx + " adj forced=" + std::to_string(k), m, tb, true, full_threshold, 0, wave_bits, relabel, -1, &orders[k], 0, &alt);
+  }
+}
+// X**t, Z**t on every qubit, CZ**t on pairs (0,1),(2,3).. then (1,2),(3,4)..; the open XXZ chain XX + YY + Z Z / 2
+static Model hea_xxz_model(int n, int layers) {
+  Model m;
+  m.n = n;
+  for (int l = 0; l < layers; ++l) {
+    for (int q = 0; q < n; ++q) {
+      m.gates.push_back(Gate{QHBM_GATE_XPOW, q, -1, m.n_params++, 1.f, 0.f, 0.f});
+      m.gates.push_back(Gate{QHBM_GATE_ZPOW, q, -1, m.n_params++, 1.f, 0.f, 0.f});
+    }
+    for (int start = 0; start < 2; ++start)
+      for (int q = start; q + 1 < n; q += 2) m.gates.push_back(Gate{QHBM_GATE_CZPOW, q, q + 1, m.n_params++, 1.f, 0.f, 0.f});
+  }
+  m.n_ops = 1;
+  for (int q = 0; q + 1 < n; ++q) {
+    const uint32_t pair = (1u << (n - 1 - q)) | (1u << (n - 2 - q));
+    m.terms.push_back(PauliTerm{1.f, pair, 0u, 0, 0});
+    m.terms.push_back(PauliTerm{1.f, pair, pair, 2, 0});
+    m.terms.push_back(PauliTerm{0.5f, 0u, pair, 0, 0});
+  }
+  return m;
+}
+
+static int digest_main(int cases, uint64_t seed, const char* path) {
+  DigestRun r;
+  r.out = std::fopen(path, "w");
+  if (!r.out) { std::fprintf(stderr, "cannot write %s\n", path); return 1; }
+  std::mt19937_64 rng(seed);
+  auto U = [&](int lo, int hi) { return int(std::uniform_int_distribution<int>(lo, hi)(rng)); };
+  char ctx[160];
+  Case largest;
+  for (int i = 0; i < cases; ++i) {  // the generator's cases and option sets, as fuzz_one draws them
+    int n = 3 + int(rng() % 26u);
+    if (n > 20 && (rng() & 3)) n = 3 + int(rng() % 18);
+    Case c = random_case(rng, n);
+    fill_terms(&c);
+    if (c.m.gates.size() > r.largest_gates) { r.largest_gates = c.m.gates.size(); r.largest_case = i; r.largest_n = n; largest = c; }
+    const int n_eff = std::max(n, kMinTileBits);
+    for (int os = 0; os < 3; ++os) {
+      const int tile = os == 0 ? 0 : std::min(n_eff, U(kMinTileBits, kMaxTileBits - 1));
+      const bool relabel = U(0, 1), wave_bits = U(0, 3) != 0;
+      const int full_threshold = (const int[]){0, 60, 60, 100000}[U(0, 3)];
+      const int wide = U(-1, 1);
+      std::snprintf(ctx, sizeof ctx, "case %d n=%d gates=%zu tile=%d relabel=%d wave=%d full=%d wide=%d", i, n, c.m.gates.size(), tile, int(relabel),
+                    int(wave_bits), full_threshold, wide);
+      digest_option_set(&r, ctx, c.m, tile, full_threshold, 0, wave_bits, relabel, wide);
+    }
+  }
+  // hardware-efficient circuits whose forward plans move their low bits (tests/test_forward_low_bits_cpu.py)
+  static const int kHea[3][3] = {{20, 16, 0}, {16, 16, 0}, {14, 5, 10}};  // qubits, layers, tile
+  for (const auto& hc : kHea) {
+    const Model m = hea_xxz_model(hc[0], hc[1]);
+    std::snprintf(ctx, sizeof ctx, "hea n=%d layers=%d tile=%d", hc[0], hc[1], hc[2]);
+    digest_option_set(&r, ctx, m, hc[2], 60, 0, true, true, -1);
+  }
+  for (int n : {24, 28}) {  // large registers, default options
+    Case c = random_case(rng, n);
+    fill_terms(&c);
+    std::snprintf(ctx, sizeof ctx, "large n=%d gates=%zu", n, c.m.gates.size());
+    digest_option_set(&r, ctx, c.m, 0, 60, 0, true, false, -1);
+  }
+  {  // a gradient mask that freezes the parameters of the leading third of the gates (dense_tail); a caller-supplied start state
+    Model m = hea_xxz_model(14, 4);
+    m.param_frozen.assign(size_t(m.n_params), 0);
+    for (size_t g = 0; g < m.gates.size() / 3; ++g) m.param_frozen[size_t(m.gates[g].param_idx)] = 1;
+    Plan plan;
+    for (int stop = 0; stop < 2; ++stop)
+      for (int relabel = 0; relabel < 2; ++relabel) {
+        m.stop_at_first_live_gate = stop != 0;
+        std::snprintf(ctx, sizeof ctx, "masked n=14 layers=4 tile=10 stop=%d relabel=%d adj", stop, relabel);
+        const bool ok = digest_one(&r, ctx, m, 10, true, 60, 0, true, relabel != 0, -1, nullptr, 0, &plan);
+        if (ok && stop && !plan.dense_tail) { std::fprintf(stderr, "--digest-plans: the masked model gives no dense_tail plan\n"); ++g_failures; }
+      }
+    Model d = hea_xxz_model(14, 4);
+    d.dense_input = true;
+    digest_option_set(&r, "dense_input n=14 layers=4 tile=10", d, 10, 60, 0, true, true, -1);
+  }
+  std::fclose(r.out);
+  if (std::FILE* f = std::fopen((std::string(path) + ".largest_case.json").c_str(), "w")) {  // for timing the planner on it (ABI form)
+    std::fprintf(f, "{\"n\": %d, \"n_params\": %d, \"gates\": [", largest.m.n, largest.m.n_params);
+    for (size_t g = 0; g < largest.abi_gates.size(); ++g) {
+      const qhbm_gate& G = largest.abi_gates[g];
+      std::fprintf(f, "%s[%d, %d, %d, %d, %.9g, %.9g]", g ? ", " : "", G.kind, G.q0, G.q1, G.param_idx, double(G.scalar), double(G.offset));
+    }
+    std::fprintf(f, "],\n \"term_offsets\": [");
+    for (size_t k = 0; k < largest.term_offsets.size(); ++k) std::fprintf(f, "%s%d", k ? ", " : "", largest.term_offsets[k]);
+    std::fprintf(f, "],\n \"terms\": [");
+    for (size_t k = 0; k < largest.coeffs.size(); ++k)
+      std::fprintf(f, "%s[%.9g, %llu, %llu]", k ? ", " : "", double(largest.coeffs[k]), (unsigned long long)largest.xs[k], (unsigned long long)largest.zs[k]);
+    std::fprintf(f, "]}\n");
+    std::fclose(f);
+  }
+  std::printf("plan_digest: %d cases (seed %llu), %ld plans (%ld did not build), forward plans with a moving store %ld, adjoint plans that relabel %ld\n",
+              cases, (unsigned long long)seed, r.plans, r.failed, r.fwd_moving, r.adj_relabel);
+  std::printf("plan_digest: largest generator case: %d (n=%d, %zu gates)\n", r.largest_case, r.largest_n, r.largest_gates);
+  if (r.fwd_moving == 0 || r.adj_relabel == 0) { std::fprintf(stderr, "--digest-plans: a count is zero\n"); return 1; }
+  return g_failures ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 4 && std::string(argv[1]) == "--digest-plans") return digest_main(std::atoi(argv[2]), std::strtoull(argv[3], nullptr, 10), argv[4]);
   if (self_test()) { std::printf("plan_fuzz: self test FAILED\n"); return 2; }
   if (argc > 2 && std::string(argv[1]) == "--self-test-without") {  // what only one comparison catches (by hand)
     const std::string w(argv[2]);
