@@ -9,7 +9,8 @@ on the GPU, against the complex128 restatement of tests/reduced_d
    (Abar phibar)[a, b] with Abar = |Re A| + |Im A|, phibar likewise, in ANY summation order, and it is asserted
    elementwise; `dots`, summed in float64 from the unscaled f32 outputs, is held to the same bound summed against phibar.
    Shapes: those of the issue, both sides of the vector / matrix switch (k = 3 and k = 4), a vector shape of several
-   slices and a matrix shape of several column tiles.
+   slices and a matrix shape of several column tiles, and one of each with 512 partials per state and component (n = 20
+   and 19: the second trip of `subsys_dots_finish`'s row sums; tests/test_wide_states_cpu.py asserts the count).
 2. Gradients through the mirror: a depth-2 HEA at 6 qubits (k = 2: the vector kernel) and 12 qubits (k = 5: the matrix
    kernel), `final_states_from_states` -> `reduced_density_matrix(differentiable=True)` -> the three losses, against the
    restatement composed with `tests/final_states_ref.vjp`, at the bar of DESIGN.md 6f / 6l, 1e-4 max(1, ||grad||_inf).
@@ -50,6 +51,8 @@ SHAPES = [
     (14, (0, 1, 2, 4, 5, 6, 8, 9, 10, 12), 3),        # several environment blocks
     (12, (3,), 2),                                    # the vector kernel over two slices
     (12, (0, 3, 7, 11), 2),                           # the matrix kernel over four column tiles
+    (20, (7,), 2),                                    # the vector kernel over 512 slices: `subsys_dots_finish` sums in two trips
+    (19, (0, 6, 12, 18), 2),                          # the matrix kernel, one row tile and 512 column tiles: two trips again
 ]
 SCALES = ["null", "scaled"]
 
