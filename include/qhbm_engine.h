@@ -556,6 +556,44 @@ int qhbm_gram_vjp_scratch_bytes(int M, int n_qubits, size_t* out);
 int qhbm_weighted_gram_vjp(const void* d_states, int M, int n_qubits, const float* d_table, const void* d_cotangent,
                            void* d_out_states, double* d_table_grad, void* d_scratch, void* stream);
 
+/* ---- The cross-Gram matrix of two ensembles: overlap, fidelity and trace distance of state ensembles ----
+ * Added WITHIN ABI version 5: purely additive, QHBM_ABI_VERSION stays 5.
+ *
+ *   C[i, j] = sum_x t(x) conj(a_i(x)) b_j(x)
+ * for M bras a_i and K kets b_j of 2^n_qubits amplitudes, in two buffers, and a real table t over the bitstrings.  For
+ * sigma = sum_m w_m |a_m><a_m| and tau = sum_k v_k |b_k><b_k|, X = W^1/2 C V^1/2 with t = 1: tr(sigma tau) = ||X||_F^2; the
+ * Uhlmann fidelity is (sum of the singular values of X)^2; the non-zero spectrum of sigma - tau is that of J Gamma, Gamma
+ * the Gram matrix of the M + K scaled states (blocks G_A, X, X^H, G_B; the diagonal blocks from qhbm_weighted_gram) and
+ * J = diag(1_M, -1_K).
+ *
+ *   qhbm_cross_gram          d_bras [M, 2^n_qubits] and d_kets [K, 2^n_qubits] complex64, interleaved, 16-byte aligned; both
+ *                            are only read and may alias or overlap; d_table [2^n_qubits] float32, 8-byte aligned, indexed
+ *                            like the amplitudes, or NULL for t = 1; d_out [M, K, 2] float64 (re, im), row-major; all on
+ *                            the device.  No engine: the current device.  Asynchronous on `stream`; allocates nothing,
+ *                            synchronises nothing.  d_scratch: qhbm_cross_gram_scratch_bytes bytes, 8-byte aligned, which
+ *                            may hold anything (every partial that is read is written first).
+ *                            Order of additions: qhbm_weighted_gram's own.  A product is float x float in float64 (exact),
+ *                            the column operand b_j times t first (exact); a thread adds its words in word order with
+ *                            the same eight fused multiply-adds per word and pair, the 64 lanes of a wave meet in the
+ *                            same shuffle tree, the waves add in wave order and the slices in slice order in a second
+ *                            kernel; no floating-point atomics.  The slices are qhbm_weighted_gram's and depend on
+ *                            n_qubits alone, so C[i, j] depends neither on M, nor on K, nor on which other states share
+ *                            the call, and two calls give the same bits.  Every (i, j) is summed on its own: nothing is
+ *                            mirrored, nothing is forced to zero.
+ *                            Equality with qhbm_weighted_gram: with d_bras == d_kets (and M == K) C[i, j] has the bits of
+ *                            G[i, j] for j > i, both parts, and Re C[i, i] those of Re G[i, i]; Im C[i, i] is what the
+ *                            roundings leave (G writes 0) and C[j, i] for j > i is conj(G[i, j]) within the bound only.
+ *                            Error, per part and to first order: |dC[i, j]| <= 2 (2^n_qubits + 4) 2^-53
+ *                            sum_x |t| |a_i| |b_j|.
+ *                            Refused, each with a message and before anything is launched: M or K outside [1, 1024];
+ *                            n_qubits outside [1, 31]; d_bras, d_kets, d_scratch or d_out NULL; a misaligned pointer
+ *                            (states 16 bytes; table, scratch and out 8).
+ *   qhbm_cross_gram_scratch_bytes  *out = the bytes of d_scratch such a call needs: 16 M K min(2^n_qubits / 2048, 256), at
+ *                            least 16 M K; needs no device.  Refused: M, K or n_qubits as above, out NULL. */
+int qhbm_cross_gram_scratch_bytes(int M, int K, int n_qubits, size_t* out);
+int qhbm_cross_gram(const void* d_bras, int M, const void* d_kets, int K, int n_qubits, const float* d_table, void* d_scratch,
+                    double* d_out, void* stream);
+
 /* Computational-basis samples of the final states (tfq.layers.Sample as used at
  * qhbmlib/inference/qnn.py:169,177-181,286-291):
  *   d_out_samples [U, n_shots, n_qubits] int8 (device); shot j of state u is drawn from

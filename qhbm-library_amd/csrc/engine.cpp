@@ -2794,6 +2794,37 @@ int qhbm_weighted_gram(const void* d_states, int M, int n_qubits, const float* d
   return 0;
 }
 
+// ---- the cross-Gram matrix of two ensembles (include/qhbm_engine.h; cross_gram.hip) ----
+static int check_cross_gram_shape(int M, int K, int n_qubits) {
+  if (M < 1 || M > kGramMaxStates) return fail(nullptr, "M must be in [1, " + std::to_string(kGramMaxStates) + "]");
+  if (K < 1 || K > kGramMaxStates) return fail(nullptr, "K must be in [1, " + std::to_string(kGramMaxStates) + "]");
+  if (n_qubits < 1 || n_qubits > 31) return fail(nullptr, "n_qubits must be in [1, 31]");
+  return 0;
+}
+
+int qhbm_cross_gram_scratch_bytes(int M, int K, int n_qubits, size_t* out) {
+  if (!out) return fail(nullptr, "out is NULL");
+  if (int rc = check_cross_gram_shape(M, K, n_qubits)) return rc;
+  *out = cross_gram_parts_count(uint32_t(n_qubits), uint32_t(M), uint32_t(K)) * sizeof(double);
+  return 0;
+}
+
+int qhbm_cross_gram(const void* d_bras, int M, const void* d_kets, int K, int n_qubits, const float* d_table, void* d_scratch,
+                    double* d_out, void* stream) {
+  if (int rc = check_cross_gram_shape(M, K, n_qubits)) return rc;
+  if (int rc = check_pointer(nullptr, d_bras, 16, "d_bras")) return rc;
+  if (int rc = check_pointer(nullptr, d_kets, 16, "d_kets")) return rc;
+  if (d_table)
+    if (int rc = check_pointer(nullptr, d_table, 8, "d_table")) return rc;
+  if (int rc = check_pointer(nullptr, d_scratch, 8, "d_scratch")) return rc;
+  if (int rc = check_pointer(nullptr, d_out, 8, "d_out")) return rc;
+  hipError_t e = launch_cross_gram(static_cast<const float2*>(d_bras), uint32_t(M), static_cast<const float2*>(d_kets), uint32_t(K),
+                                   uint32_t(n_qubits), d_table, static_cast<double*>(d_scratch), d_out,
+                                   static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, std::string("qhbm_cross_gram: ") + hipGetErrorString(e));
+  return 0;
+}
+
 // ---- the reduced density matrix of M states (include/qhbm_engine.h; reduced.hip, rdm_index.h) ----
 static int check_reduced_shape(int M, int n_qubits, uint64_t keep_mask) {
   if (M < 1 || M > kRdmMaxStates) return fail(nullptr, "M must be in [1, 65536]");

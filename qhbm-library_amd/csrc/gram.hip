@@ -24,8 +24,6 @@
 // every rounding is one of the additions' -- |dG[i, j]| <= 2 (2^n + 4) 2^-53 sum_x |t| |s_i| |s_j| per part to first order.
 //
 // (a translation unit of its own in the source tree, compiled as part of states.hip; it uses no name of another .hip file)
-#include <algorithm>
-
 #include "kernels.h"
 #include "state_sweep.h"
 
@@ -33,10 +31,8 @@ namespace qhbm {
 namespace {
 
 constexpr uint32_t kGramTile = 4;           // state pairs along one edge of a full tile
-constexpr uint32_t kGramSlices = 256;       // at most this many slices (from n = 20 on a thread takes more than 4 words)
 constexpr uint32_t kGramTriangle = ~0u;     // j_fixed: blockIdx.x counts the tiles j0 >= i0 of `tile_rows` tile rows
-
-uint32_t gram_slices(uint64_t words) { return std::min<uint32_t>(sweep_slices(words), kGramSlices); }
+// (the slice count is state_sweep.h's gram_slices: at most kGramSlices, shared with cross_gram.hip)
 
 // states [M, words]; tile row r of the launch starts at state i_first + 4 r; its column at j_fixed, or (kGramTriangle)
 // the launch covers the upper triangle of tile_rows x tile_rows tiles that starts at (i_first, i_first), row-major;

@@ -1,5 +1,5 @@
 // kernels.h -- launch entry points of the kernel objects (host side): kernels.hip (the pass kernels, with gwg.hip and
-// parity_table.hip), observable.hip (with energy_table.hip, cotangent.hip, subsystem_apply.hip and gram_vjp.hip) and states.hip (import_states.hip, thermal.hip, krylov.hip,
+// parity_table.hip), observable.hip (with energy_table.hip, cotangent.hip, subsystem_apply.hip, gram_vjp.hip and cross_gram.hip) and states.hip (import_states.hip, thermal.hip, krylov.hip,
 // gram.hip, reduced.hip).  A .hip file reaches another one's kernels through these declarations only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -336,6 +336,15 @@ size_t gram_parts_count(uint32_t n, uint32_t M);
 // states [M, 2^n]; M in [1, kGramMaxStates], n in [1, 31].  Every partial that is read is written first: `parts` may hold anything.
 hipError_t launch_weighted_gram(const float2* states, uint32_t M, uint32_t n, const float* table, double* parts, double* gram,
                                 hipStream_t stream);
+
+// ---- the cross-Gram matrix of M bras and K kets (cross_gram.hip) ----
+// Doubles of scratch (`parts`) one cross-Gram matrix of M x K states of n qubits needs.
+size_t cross_gram_parts_count(uint32_t n, uint32_t M, uint32_t K);
+// out[i, j] = sum_x table[x] conj(bras[i, x]) kets[j, x] (table NULL: 1), complex fp64 in launch_weighted_gram's order of
+// additions, [M, K, 2], every entry summed on its own; bras [M, 2^n], kets [K, 2^n], both only read (they may overlap);
+// M, K in [1, kGramMaxStates], n in [1, 31].  Every partial that is read is written first: `parts` may hold anything.
+hipError_t launch_cross_gram(const float2* bras, uint32_t M, const float2* kets, uint32_t K, uint32_t n, const float* table,
+                             double* parts, double* out, hipStream_t stream);
 
 // ---- the reduced density matrix of M states (reduced.hip; the plan is rdm_index.h's) ----
 // rho[a, a'] = sum_m weights[m] sum_b phi_m(a, b) conj(phi_m(a', b)) (weights NULL: 1), complex fp64 in a fixed order,

@@ -703,3 +703,8 @@ hipError_t launch_observable_blocks(int mode, int block_bits, const float2* psi,
 // The VJP of the weighted Gram matrix -- the cotangents of the states and of the table of a state metric -- likewise (its
 // plan is gram_vjp_plan.h's, and it shares no name with any other .hip file).
 #include "gram_vjp.hip"
+
+// The cross-Gram matrix of two ensembles likewise: states.hip's list of files is fixed, and this object is built with the
+// same flags, so the thread's chain of fused multiply-adds comes out as gram.hip's does there (it shares state_sweep.h with
+// gram.hip and no name with any other .hip file).
+#include "cross_gram.hip"

@@ -19,6 +19,15 @@ constexpr uint32_t kSweepSliceWords = 4 * kSweepThreads;
 
 inline uint32_t sweep_slices(uint64_t words) { return uint32_t((words + kSweepSliceWords - 1) / kSweepSliceWords); }
 
+// The slices of the Gram kernels (gram.hip, cross_gram.hip): sweep_slices' up to kGramSlices of them, beyond which a thread
+// takes more words (from n = 20 on more than 4).  Both kernels use this one count, which is what makes their sums meet the
+// same way.
+constexpr uint32_t kGramSlices = 256;
+inline uint32_t gram_slices(uint64_t words) {
+  const uint32_t slices = sweep_slices(words);
+  return slices < kGramSlices ? slices : kGramSlices;
+}
+
 // Sum over the workgroup's 256 threads (every thread gets it); sh: 256 doubles of LDS.  A second call on the same sh
 // needs a barrier in between: a fast thread's store would race a slow thread's read of sh[0].
 __device__ __forceinline__ double sweep_block_sum(double v, double* sh) {

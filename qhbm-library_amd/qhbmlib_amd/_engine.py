@@ -53,6 +53,7 @@ ABI_SYMBOLS = (
     "qhbm_reduced_density_scratch_bytes", "qhbm_reduced_density",
     "qhbm_subsystem_apply_scratch_bytes", "qhbm_subsystem_apply",
     "qhbm_gram_vjp_scratch_bytes", "qhbm_weighted_gram_vjp",
+    "qhbm_cross_gram_scratch_bytes", "qhbm_cross_gram",
     "qhbm_sample_parities", "qhbm_sample_parities_scratch_bytes", "qhbm_sample_parities_states",
 )
 
@@ -166,6 +167,8 @@ def load_library():
                                                 ctypes.c_uint32, vp, vp, vp]
     lib.qhbm_gram_vjp_scratch_bytes.argtypes = [i32, i32, ctypes.POINTER(ctypes.c_size_t)]
     lib.qhbm_weighted_gram_vjp.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.qhbm_cross_gram_scratch_bytes.argtypes = [i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
+    lib.qhbm_cross_gram.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp]
   except AttributeError:  # an older library given through QHBM_ENGINE_LIB (A/B runs): the probe is optional there
     pass
   _lib = lib
@@ -410,6 +413,51 @@ def weighted_gram(states, table=None):
     _check_global(load_library().qhbm_weighted_gram(states.data_ptr(), num, n, None if table is None else table.data_ptr(),
                                                     scratch.data_ptr(), out.data_ptr(),
                                                     torch.cuda.current_stream().cuda_stream))
+  return torch.view_as_complex(out)
+
+
+def cross_gram_scratch_bytes(num_bras, num_kets, n_qubits):
+  """Bytes of scratch one `qhbm_cross_gram` of `num_bras` x `num_kets` states of `n_qubits` qubits needs (no device needed)."""
+  out = ctypes.c_size_t()
+  _check_global(load_library().qhbm_cross_gram_scratch_bytes(int(num_bras), int(num_kets), int(n_qubits), ctypes.byref(out)))
+  return int(out.value)
+
+
+def cross_gram(bras, kets, table=None):
+  """C[i, j] = sum_x table[x] conj(bras[i, x]) kets[j, x] (table None: 1) for M bras [M, 2^n] and K kets [K, 2^n], both
+  device-resident and only read (views of one buffer are fine): complex128 [M, K], every entry summed on its own in float64
+  in `weighted_gram`'s order of additions (include/qhbm_engine.h qhbm_cross_gram).  complex128 states and a float64 table
+  are cast to complex64 / float32; the scratch is this call's own.  Not differentiable."""
+  for name, states in (("bras", bras), ("kets", kets)):
+    if not (torch.is_tensor(states) and states.is_cuda and states.dim() == 2 and states.is_complex()):
+      raise EngineError(f"cross_gram needs complex CUDA {name} [M, 2^n]: the engine has no CPU fallback")
+  if kets.device != bras.device:
+    raise EngineError("cross_gram needs bras and kets on one device")
+  bras = bras.detach().to(torch.complex64).contiguous()
+  kets = kets.detach().to(torch.complex64).contiguous()
+  if bras.data_ptr() % 16:  # (a view at an odd offset: the kernel loads 16-byte words)
+    bras = bras.clone()
+  if kets.data_ptr() % 16:
+    kets = kets.clone()
+  num, dim = (int(v) for v in bras.shape)
+  n = dim.bit_length() - 1
+  if dim != (1 << n) or n < 1:
+    raise ValueError(f"bras have {dim} amplitudes: not a power of two, or fewer than two")
+  if int(kets.shape[1]) != dim:
+    raise ValueError(f"bras have {dim} amplitudes, kets {int(kets.shape[1])}")
+  num_kets = int(kets.shape[0])
+  if table is not None:
+    if not (torch.is_tensor(table) and table.is_cuda and table.device == bras.device):
+      raise EngineError("cross_gram needs the table on the states' device")
+    if table.is_complex() or tuple(table.shape) != (dim,):
+      raise ValueError(f"table must be real and have shape [{dim}], got {table.dtype} {tuple(table.shape)}")
+    table = table.detach().to(torch.float32).contiguous()
+  with torch.cuda.device(bras.device):
+    scratch = torch.empty(cross_gram_scratch_bytes(num, num_kets, n) // 8, dtype=torch.float64, device=bras.device)
+    out = torch.empty((num, num_kets, 2), dtype=torch.float64, device=bras.device)
+    _check_global(load_library().qhbm_cross_gram(bras.data_ptr(), num, kets.data_ptr(), num_kets, n,
+                                                 None if table is None else table.data_ptr(), scratch.data_ptr(),
+                                                 out.data_ptr(), torch.cuda.current_stream().cuda_stream))
   return torch.view_as_complex(out)
 
 

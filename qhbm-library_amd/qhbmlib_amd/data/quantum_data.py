@@ -206,6 +206,19 @@ class StateVectorData(QuantumData):
     loss."""
     return self.metrics(model, **kwargs).relative_entropy
 
+  def fidelity_to(self, other):
+    """(tr sqrt(sqrt(sigma) tau sqrt(sigma)))^2 of this data sigma against another state ensemble tau (`StateVectorData`, a
+    `ThermalEnsemble` or a `(states, weights)` pair), both as given: `inference.ensemble_metrics(self, other).fidelity`
+    (DESIGN.md 6p).  Not differentiable."""
+    from qhbmlib_amd.inference.ensemble_metrics import ensemble_metrics  # pylint: disable=import-outside-toplevel
+    return ensemble_metrics(self, other).fidelity
+
+  def trace_distance_to(self, other):
+    """1/2 ||sigma - tau||_1 of this data against another state ensemble, both as given:
+    `inference.ensemble_metrics(self, other).trace_distance`.  Not differentiable."""
+    from qhbmlib_amd.inference.ensemble_metrics import ensemble_metrics  # pylint: disable=import-outside-toplevel
+    return ensemble_metrics(self, other).trace_distance
+
   def reduced(self, qubits, rtol=1e-10):
     """The quantum data of subsystem A = `qubits` (qubit objects of this data or integer positions in its sorted qubit
     list): the eigen-ensemble of rho_A = tr_B sigma, summed on the GPU without moving the states

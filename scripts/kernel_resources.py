@@ -1,4 +1,4 @@
-"""Register / LDS / occupancy table of the pass, observable, Gibbs-With-Gradients, parity-table, shot-parity, Krylov (with the streamed replay), Gram, Gram-VJP and reduced-density kernels as hipcc reports them, and WHERE their spills sit
+"""Register / LDS / occupancy table of the pass, observable, Gibbs-With-Gradients, parity-table, shot-parity, Krylov (with the streamed replay), Gram, cross-Gram, Gram-VJP and reduced-density kernels as hipcc reports them, and WHERE their spills sit
 (developer tool and CPU test, no GPU needed):
     python scripts/kernel_resources.py            # the table, then every spill site with its loop context
 `check()` is what tests/test_scripts_cpu.py runs: a kernel the DEFAULT planner can select must not spill a VGPR at all and
@@ -45,7 +45,7 @@ def resource_rows():
       cur[m.group(1).strip()] = int(m.group(2))
   for r in rows:
     r["name"] = _demangle(r["mangled"])
-  return [r for r in rows if any(k in r["name"] for k in ("pass_", "apply_obs", "observable_blocks", "gwg_chain", "wht_", "parity_scatter", "parity_gather", "krylov_", "gram_tile_", "gram_finish_", "rdm_tile_", "rdm_finish_", "shot_parity_", "gram_vjp_"))]
+  return [r for r in rows if any(k in r["name"] for k in ("pass_", "apply_obs", "observable_blocks", "gwg_chain", "wht_", "parity_scatter", "parity_gather", "krylov_", "gram_tile_", "gram_finish_", "cross_gram_", "rdm_tile_", "rdm_finish_", "shot_parity_", "gram_vjp_"))]
 
 
 def assembly(src):
@@ -137,6 +137,8 @@ def default_selectable(name):
   if name.startswith("observable_blocks_kernel"):
     return name.endswith(", 13>")    # (`<..., 12>`: the two-workgroups-per-CU shape, option "observable_block_bits" = 12)
   if "krylov_" in name or "gram_tile_" in name or "gram_finish_" in name or "rdm_tile_" in name or "rdm_finish_" in name:
+    return True
+  if "cross_gram_" in name:             # (cross_gram.hip: the tile and finish kernels of qhbm_cross_gram)
     return True
   if "gram_vjp_" in name:               # (gram_vjp.hip: the vector, planes and matrix kernels of qhbm_weighted_gram_vjp)
     return True
