@@ -594,6 +594,46 @@ int qhbm_cross_gram_scratch_bytes(int M, int K, int n_qubits, size_t* out);
 int qhbm_cross_gram(const void* d_bras, int M, const void* d_kets, int K, int n_qubits, const float* d_table, void* d_scratch,
                     double* d_out, void* stream);
 
+/* ---- The VJP of the cross-Gram matrix: two-ensemble metrics as losses ----
+ * Added WITHIN ABI version 5: purely additive, QHBM_ABI_VERSION stays 5.
+ *
+ * For a real loss L of C = qhbm_cross_gram's matrix with cotangent Gamma = dL/dRe C + i dL/dIm C, [M, K]
+ * (dL = Re sum conj(Gamma[i, j]) dC[i, j]), and c_j(x) = sum_i Gamma[i, j] a_i(x):
+ *   out_kets_j(x) = t(x) c_j(x)       out_bras_i(x) = t(x) sum_j conj(Gamma[i, j]) b_j(x)       table_grad(x) = sum_j Re(conj(c_j(x)) b_j(x))
+ * -- the cotangents of the kets, of the bras and of the table.  Gamma is used as given: nothing is symmetrised, so there is
+ * no factor 1/2 in table_grad.
+ *
+ *   qhbm_cross_gram_vjp      d_bras, d_out_bras [M, 2^n_qubits] and d_kets, d_out_kets [K, 2^n_qubits] complex64,
+ *                            interleaved, 16-byte aligned; d_table [2^n_qubits] float32, 8-byte aligned, or NULL for t = 1;
+ *                            d_cotangent = Gamma, [M, K] complex64, row-major, 8-byte aligned; d_table_grad [2^n_qubits]
+ *                            float64; all on the device.  Each of d_out_bras, d_out_kets and d_table_grad may be NULL and is
+ *                            then not computed; the others' bits do not change.  d_bras and d_kets are only read and may
+ *                            alias or overlap each other.  No engine: the current device.  Asynchronous on `stream`;
+ *                            allocates nothing, synchronises nothing.  d_scratch: qhbm_cross_gram_vjp_scratch_bytes bytes,
+ *                            8-byte aligned, which may hold anything.
+ *                            Each state output is one sweep out_s(x) = t(x) sum_r W[r, s] src_r(x): for the kets src = bras
+ *                            and W = Gamma, for the bras src = kets and W[r, s] = conj(Gamma[s, r]).  The sum is an f32
+ *                            fused-multiply-add chain over r ascending of the real embedding Re = W_r s_r - W_i s_i,
+ *                            Im = W_r s_i + W_i s_r (up to 8 source rows vector code, from 9 on v_mfma_f32_16x16x4_f32,
+ *                            which is such a chain bit for bit; the switch looks at the SOURCE side's row count only);
+ *                            out = t times it, one rounding per part.  table_grad: the unscaled c times b, float x float
+ *                            in float64 (exact), Re then Im, j ascending in one accumulator; one workgroup finishes an x,
+ *                            so there are no partials and no floating-point atomics: two calls give the same bits.
+ *                            Error, per part: |d out_s(x)| <= (2 R + 4) 2^-24 |t(x)| sum_r (|Re W_rs| + |Im W_rs|)
+ *                            (|Re src_r(x)| + |Im src_r(x)|), R the number of source rows.
+ *                            Refused, each with a message and before anything is launched: the shapes qhbm_cross_gram
+ *                            refuses; d_bras, d_kets, d_cotangent or d_scratch NULL; all three outputs NULL; a misaligned
+ *                            pointer (states and state outputs 16 bytes, the rest 8); a state output overlapping either
+ *                            input or the other state output.
+ *   qhbm_cross_gram_vjp_scratch_bytes  *out = the bytes of d_scratch such a call needs (csrc/cross_gram_vjp_plan.h
+ *                            cgv_plan): per side with 9 or more source rows, W as two zero-padded float planes of
+ *                            16 ceil(R / 16) x Ps floats, Ps = 16 ceil(S / 16) up to 64 and 64 ceil(S / 64) beyond; at
+ *                            least 16, never 0; needs no device.  Refused: M, K or n_qubits as above, out NULL. */
+int qhbm_cross_gram_vjp_scratch_bytes(int M, int K, int n_qubits, size_t* out);
+int qhbm_cross_gram_vjp(const void* d_bras, int M, const void* d_kets, int K, int n_qubits, const float* d_table,
+                        const void* d_cotangent, void* d_out_bras, void* d_out_kets, double* d_table_grad, void* d_scratch,
+                        void* stream);
+
 /* Computational-basis samples of the final states (tfq.layers.Sample as used at
  * qhbmlib/inference/qnn.py:169,177-181,286-291):
  *   d_out_samples [U, n_shots, n_qubits] int8 (device); shot j of state u is drawn from

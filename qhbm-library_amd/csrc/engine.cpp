@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/qhbm_engine.h"
+#include "cross_gram_vjp_plan.h"
 #include "gram_vjp_plan.h"
 #include "kernels.h"
 #include "plan_args.h"
@@ -2822,6 +2823,51 @@ int qhbm_cross_gram(const void* d_bras, int M, const void* d_kets, int K, int n_
                                    uint32_t(n_qubits), d_table, static_cast<double*>(d_scratch), d_out,
                                    static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return fail(nullptr, std::string("qhbm_cross_gram: ") + hipGetErrorString(e));
+  return 0;
+}
+
+// ---- the VJP of the cross-Gram matrix (include/qhbm_engine.h; cross_gram_vjp.hip, cross_gram_vjp_plan.h) ----
+int qhbm_cross_gram_vjp_scratch_bytes(int M, int K, int n_qubits, size_t* out) {
+  if (!out) return fail(nullptr, "out is NULL");
+  if (int rc = check_cross_gram_shape(M, K, n_qubits)) return rc;
+  *out = cgv_plan(n_qubits, M, K).scratch_bytes;
+  return 0;
+}
+
+int qhbm_cross_gram_vjp(const void* d_bras, int M, const void* d_kets, int K, int n_qubits, const float* d_table,
+                        const void* d_cotangent, void* d_out_bras, void* d_out_kets, double* d_table_grad, void* d_scratch,
+                        void* stream) {
+  if (int rc = check_cross_gram_shape(M, K, n_qubits)) return rc;
+  if (int rc = check_pointer(nullptr, d_bras, 16, "d_bras")) return rc;
+  if (int rc = check_pointer(nullptr, d_kets, 16, "d_kets")) return rc;
+  if (d_table)
+    if (int rc = check_pointer(nullptr, d_table, 8, "d_table")) return rc;
+  if (int rc = check_pointer(nullptr, d_cotangent, 8, "d_cotangent")) return rc;
+  if (!d_out_bras && !d_out_kets && !d_table_grad)
+    return fail(nullptr, "d_out_bras, d_out_kets and d_table_grad are all NULL: nothing to compute");
+  if (d_out_bras)
+    if (int rc = check_pointer(nullptr, d_out_bras, 16, "d_out_bras")) return rc;
+  if (d_out_kets)
+    if (int rc = check_pointer(nullptr, d_out_kets, 16, "d_out_kets")) return rc;
+  if (d_table_grad)
+    if (int rc = check_pointer(nullptr, d_table_grad, 8, "d_table_grad")) return rc;
+  if (int rc = check_pointer(nullptr, d_scratch, 8, "d_scratch")) return rc;
+  const size_t bra_bytes = size_t(M) * (size_t(8) << n_qubits), ket_bytes = size_t(K) * (size_t(8) << n_qubits);
+  if (d_out_bras) {
+    if (ranges_overlap(d_out_bras, bra_bytes, d_bras, bra_bytes)) return fail(nullptr, "d_out_bras overlaps d_bras");
+    if (ranges_overlap(d_out_bras, bra_bytes, d_kets, ket_bytes)) return fail(nullptr, "d_out_bras overlaps d_kets");
+  }
+  if (d_out_kets) {
+    if (ranges_overlap(d_out_kets, ket_bytes, d_bras, bra_bytes)) return fail(nullptr, "d_out_kets overlaps d_bras");
+    if (ranges_overlap(d_out_kets, ket_bytes, d_kets, ket_bytes)) return fail(nullptr, "d_out_kets overlaps d_kets");
+  }
+  if (d_out_bras && d_out_kets && ranges_overlap(d_out_bras, bra_bytes, d_out_kets, ket_bytes))
+    return fail(nullptr, "d_out_bras overlaps d_out_kets");
+  hipError_t e = launch_cross_gram_vjp(static_cast<const float2*>(d_bras), uint32_t(M), static_cast<const float2*>(d_kets), uint32_t(K),
+                                       uint32_t(n_qubits), d_table, static_cast<const float2*>(d_cotangent),
+                                       static_cast<float2*>(d_out_bras), static_cast<float2*>(d_out_kets), d_table_grad, d_scratch,
+                                       static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, std::string("qhbm_cross_gram_vjp: ") + hipGetErrorString(e));
   return 0;
 }
 

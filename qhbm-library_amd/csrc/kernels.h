@@ -1,5 +1,5 @@
 // kernels.h -- launch entry points of the kernel objects (host side): kernels.hip (the pass kernels, with gwg.hip and
-// parity_table.hip), observable.hip (with energy_table.hip, cotangent.hip, subsystem_apply.hip, gram_vjp.hip and cross_gram.hip) and states.hip (import_states.hip, thermal.hip, krylov.hip,
+// parity_table.hip), observable.hip (with energy_table.hip, cotangent.hip, subsystem_apply.hip, gram_vjp.hip, cross_gram.hip and cross_gram_vjp.hip) and states.hip (import_states.hip, thermal.hip, krylov.hip,
 // gram.hip, reduced.hip).  A .hip file reaches another one's kernels through these declarations only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -345,6 +345,16 @@ size_t cross_gram_parts_count(uint32_t n, uint32_t M, uint32_t K);
 // M, K in [1, kGramMaxStates], n in [1, 31].  Every partial that is read is written first: `parts` may hold anything.
 hipError_t launch_cross_gram(const float2* bras, uint32_t M, const float2* kets, uint32_t K, uint32_t n, const float* table,
                              double* parts, double* out, hipStream_t stream);
+
+// ---- the VJP of the cross-Gram matrix (cross_gram_vjp.hip; the plan is cross_gram_vjp_plan.h's) ----
+// For a cotangent gamma [M, K] (complex64, row-major, used as given) of launch_cross_gram's matrix, c_j(x) = sum_i gamma[i, j]
+// bras[i, x] in f32: out_kets[j, x] = table[x] c_j(x), out_bras[i, x] = table[x] sum_j conj(gamma[i, j]) kets[j, x] (table NULL:
+// 1), complex64 [K, 2^n] and [M, 2^n]; table_grad[x] = sum_j Re(conj(c_j(x)) kets[j, x]), fp64 in a fixed order, [2^n].  Each
+// output may be NULL (not all three).  Shape limits as launch_cross_gram.  `scratch`: cgv_plan(n, M, K).scratch_bytes bytes,
+// which may hold anything.
+hipError_t launch_cross_gram_vjp(const float2* bras, uint32_t M, const float2* kets, uint32_t K, uint32_t n, const float* table,
+                                 const float2* gamma, float2* out_bras, float2* out_kets, double* table_grad, void* scratch,
+                                 hipStream_t stream);
 
 // ---- the reduced density matrix of M states (reduced.hip; the plan is rdm_index.h's) ----
 // rho[a, a'] = sum_m weights[m] sum_b phi_m(a, b) conj(phi_m(a', b)) (weights NULL: 1), complex fp64 in a fixed order,

@@ -708,3 +708,7 @@ hipError_t launch_observable_blocks(int mode, int block_bits, const float2* psi,
 // same flags, so the thread's chain of fused multiply-adds comes out as gram.hip's does there (it shares state_sweep.h with
 // gram.hip and no name with any other .hip file).
 #include "cross_gram.hip"
+
+// The VJP of the cross-Gram matrix -- the cotangents of bras, kets and table of a two-ensemble metric -- likewise (its plan is
+// cross_gram_vjp_plan.h's, which reads gram_vjp_plan.h's helpers; it shares no name with any other .hip file).
+#include "cross_gram_vjp.hip"

@@ -54,6 +54,7 @@ ABI_SYMBOLS = (
     "qhbm_subsystem_apply_scratch_bytes", "qhbm_subsystem_apply",
     "qhbm_gram_vjp_scratch_bytes", "qhbm_weighted_gram_vjp",
     "qhbm_cross_gram_scratch_bytes", "qhbm_cross_gram",
+    "qhbm_cross_gram_vjp_scratch_bytes", "qhbm_cross_gram_vjp",
     "qhbm_sample_parities", "qhbm_sample_parities_scratch_bytes", "qhbm_sample_parities_states",
 )
 
@@ -169,6 +170,8 @@ def load_library():
     lib.qhbm_weighted_gram_vjp.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.qhbm_cross_gram_scratch_bytes.argtypes = [i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
     lib.qhbm_cross_gram.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp]
+    lib.qhbm_cross_gram_vjp_scratch_bytes.argtypes = [i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
+    lib.qhbm_cross_gram_vjp.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
   except AttributeError:  # an older library given through QHBM_ENGINE_LIB (A/B runs): the probe is optional there
     pass
   _lib = lib
@@ -459,6 +462,66 @@ def cross_gram(bras, kets, table=None):
                                                  None if table is None else table.data_ptr(), scratch.data_ptr(),
                                                  out.data_ptr(), torch.cuda.current_stream().cuda_stream))
   return torch.view_as_complex(out)
+
+
+def cross_gram_vjp_scratch_bytes(num_bras, num_kets, n_qubits):
+  """Bytes of scratch one `qhbm_cross_gram_vjp` of `num_bras` x `num_kets` states of `n_qubits` qubits needs (no device
+  needed)."""
+  out = ctypes.c_size_t()
+  _check_global(load_library().qhbm_cross_gram_vjp_scratch_bytes(int(num_bras), int(num_kets), int(n_qubits), ctypes.byref(out)))
+  return int(out.value)
+
+
+def cross_gram_vjp(bras, kets, table, cotangent, want_bras=True, want_kets=True, want_table=True):
+  """The VJP of `cross_gram` for M bras [M, 2^n], K kets [K, 2^n], its table (None: ones) and torch's cotangent Gamma [M, K]
+  of C (used as given): with c[j] = sum_i Gamma[i, j] bras[i],
+  (table * sum_j conj(Gamma[i, j]) kets[j] as complex64 [M, 2^n], table * c as complex64 [K, 2^n],
+  sum_j Re(conj(c[j]) kets[j]) as float64 [2^n]) -- the cotangents of the bras, of the kets and of the table, from one call
+  of the HIP engine (include/qhbm_engine.h qhbm_cross_gram_vjp); an output that is not wanted is None and is not computed.
+  complex128 inputs are cast to complex64 and a float64 table to float32; the scratch is this call's own.  Not
+  differentiable."""
+  for name, states in (("bras", bras), ("kets", kets)):
+    if not (torch.is_tensor(states) and states.is_cuda and states.dim() == 2 and states.is_complex()):
+      raise EngineError(f"cross_gram_vjp needs complex CUDA {name} [M, 2^n]: the engine has no CPU fallback")
+  if kets.device != bras.device:
+    raise EngineError("cross_gram_vjp needs bras and kets on one device")
+  if not (want_bras or want_kets or want_table):
+    raise ValueError("cross_gram_vjp: no output is wanted")
+  bras = bras.detach().to(torch.complex64).contiguous()
+  kets = kets.detach().to(torch.complex64).contiguous()
+  if bras.data_ptr() % 16:  # (a view at an odd offset: the entry point asks for 16-byte alignment)
+    bras = bras.clone()
+  if kets.data_ptr() % 16:
+    kets = kets.clone()
+  num, dim = (int(v) for v in bras.shape)
+  n = dim.bit_length() - 1
+  if dim != (1 << n) or n < 1:
+    raise ValueError(f"bras have {dim} amplitudes: not a power of two, or fewer than two")
+  if int(kets.shape[1]) != dim:
+    raise ValueError(f"bras have {dim} amplitudes, kets {int(kets.shape[1])}")
+  num_kets = int(kets.shape[0])
+  if table is not None:
+    if not (torch.is_tensor(table) and table.is_cuda and table.device == bras.device):
+      raise EngineError("cross_gram_vjp needs the table on the states' device")
+    if table.is_complex() or tuple(table.shape) != (dim,):
+      raise ValueError(f"table must be real and have shape [{dim}], got {table.dtype} {tuple(table.shape)}")
+    table = table.detach().to(torch.float32).contiguous()
+    if table.data_ptr() % 8:
+      table = table.clone()
+  cotangent = torch.as_tensor(cotangent)
+  if not cotangent.is_complex() or tuple(cotangent.shape) != (num, num_kets):
+    raise ValueError(f"cotangent must be complex of shape [{num}, {num_kets}], got {cotangent.dtype} {tuple(cotangent.shape)}")
+  cotangent = cotangent.detach().to(device=bras.device, dtype=torch.complex64).contiguous()
+  with torch.cuda.device(bras.device):
+    scratch = torch.empty(cross_gram_vjp_scratch_bytes(num, num_kets, n) // 8, dtype=torch.float64, device=bras.device)
+    out_bras = torch.empty_like(bras) if want_bras else None
+    out_kets = torch.empty_like(kets) if want_kets else None
+    grad = torch.empty(dim, dtype=torch.float64, device=bras.device) if want_table else None
+    _check_global(load_library().qhbm_cross_gram_vjp(
+        bras.data_ptr(), num, kets.data_ptr(), num_kets, n, None if table is None else table.data_ptr(), cotangent.data_ptr(),
+        None if out_bras is None else out_bras.data_ptr(), None if out_kets is None else out_kets.data_ptr(),
+        None if grad is None else grad.data_ptr(), scratch.data_ptr(), torch.cuda.current_stream().cuda_stream))
+  return out_bras, out_kets, grad
 
 
 def reduced_density_scratch_bytes(num_states, n_qubits, keep_mask):

@@ -206,18 +206,19 @@ class StateVectorData(QuantumData):
     loss."""
     return self.metrics(model, **kwargs).relative_entropy
 
-  def fidelity_to(self, other):
+  def fidelity_to(self, other, differentiable=False):
     """(tr sqrt(sqrt(sigma) tau sqrt(sigma)))^2 of this data sigma against another state ensemble tau (`StateVectorData`, a
     `ThermalEnsemble` or a `(states, weights)` pair), both as given: `inference.ensemble_metrics(self, other).fidelity`
-    (DESIGN.md 6p).  Not differentiable."""
+    (DESIGN.md 6p).  `differentiable=True`: a 0-dim float64 tensor whose gradient reaches the states and weights of a
+    `(states, weights)` pair that require grad; this data is a constant."""
     from qhbmlib_amd.inference.ensemble_metrics import ensemble_metrics  # pylint: disable=import-outside-toplevel
-    return ensemble_metrics(self, other).fidelity
+    return ensemble_metrics(self, other, differentiable=differentiable).fidelity
 
-  def trace_distance_to(self, other):
+  def trace_distance_to(self, other, differentiable=False):
     """1/2 ||sigma - tau||_1 of this data against another state ensemble, both as given:
-    `inference.ensemble_metrics(self, other).trace_distance`.  Not differentiable."""
+    `inference.ensemble_metrics(self, other).trace_distance`.  `differentiable=True`: as `fidelity_to`."""
     from qhbmlib_amd.inference.ensemble_metrics import ensemble_metrics  # pylint: disable=import-outside-toplevel
-    return ensemble_metrics(self, other).trace_distance
+    return ensemble_metrics(self, other, differentiable=differentiable).trace_distance
 
   def reduced(self, qubits, rtol=1e-10):
     """The quantum data of subsystem A = `qubits` (qubit objects of this data or integer positions in its sorted qubit

@@ -5,7 +5,8 @@ from qhbmlib_amd.inference.ebm import (AnalyticEnergyInference, BernoulliEnergyI
                                        EnergyInference, EnergyInferenceBase,
                                        GibbsWithGradientsInference)
 from qhbmlib_amd.inference.ebm_utils import probabilities
-from qhbmlib_amd.inference.ensemble_metrics import EnsembleMetrics, ensemble_metrics, matrix_elements
+from qhbmlib_amd.inference.ensemble_metrics import (EnsembleMetrics, differentiable_cross_gram, ensemble_metrics,
+                                                    matrix_elements)
 from qhbmlib_amd.inference.information import information_matrix, natural_gradient
 from qhbmlib_amd.inference.krylov import (KrylovSpace, StreamedKrylovSpace, ThermalSweep, ground_state, krylov_space,
                                           spectrum_extremes, thermal_sweep)
@@ -26,7 +27,7 @@ from qhbmlib_amd._engine import cross_gram
 
 __all__ = ["AnalyticEnergyInference", "AnalyticQuantumInference", "BernoulliEnergyInference", "CapturedLoss",
            "EnergyInference", "EnergyInferenceBase", "EnsembleMetrics", "GibbsWithGradientsInference", "KrylovSpace", "QHBM", "QuantumInference",
-           "SampledQuantumInference", "StateMetrics", "StreamedKrylovSpace", "ThermalEnsemble", "ThermalSweep", "apply_operator", "cross_gram", "density_matrix", "ensemble_metrics",
+           "SampledQuantumInference", "StateMetrics", "StreamedKrylovSpace", "ThermalEnsemble", "ThermalSweep", "apply_operator", "cross_gram", "density_matrix", "differentiable_cross_gram", "ensemble_metrics",
            "fidelity", "ground_state", "imaginary_time_evolution", "information_matrix", "krylov_space", "matrix_elements", "mutual_information",
            "natural_gradient", "probabilities", "qmhl", "real_time_evolution", "reduced_density_matrix",
            "sampled_ensemble_reduced", "sampled_reduced_density_matrix", "spectrum_extremes", "state_metrics", "subsystem_entropy", "thermal_ensemble",

@@ -1,4 +1,4 @@
-"""Register / LDS / occupancy table of the pass, observable, Gibbs-With-Gradients, parity-table, shot-parity, Krylov (with the streamed replay), Gram, cross-Gram, Gram-VJP and reduced-density kernels as hipcc reports them, and WHERE their spills sit
+"""Register / LDS / occupancy table of the pass, observable, Gibbs-With-Gradients, parity-table, shot-parity, Krylov (with the streamed replay), Gram, cross-Gram, Gram-VJP, cross-Gram-VJP and reduced-density kernels as hipcc reports them, and WHERE their spills sit
 (developer tool and CPU test, no GPU needed):
     python scripts/kernel_resources.py            # the table, then every spill site with its loop context
 `check()` is what tests/test_scripts_cpu.py runs: a kernel the DEFAULT planner can select must not spill a VGPR at all and
@@ -138,7 +138,8 @@ def default_selectable(name):
     return name.endswith(", 13>")    # (`<..., 12>`: the two-workgroups-per-CU shape, option "observable_block_bits" = 12)
   if "krylov_" in name or "gram_tile_" in name or "gram_finish_" in name or "rdm_tile_" in name or "rdm_finish_" in name:
     return True
-  if "cross_gram_" in name:             # (cross_gram.hip: the tile and finish kernels of qhbm_cross_gram)
+  if "cross_gram_" in name:             # (cross_gram.hip: the tile and finish kernels of qhbm_cross_gram; cross_gram_vjp.hip:
+                                        # the vector, planes and matrix kernels of qhbm_cross_gram_vjp)
     return True
   if "gram_vjp_" in name:               # (gram_vjp.hip: the vector, planes and matrix kernels of qhbm_weighted_gram_vjp)
     return True
